@@ -9,6 +9,10 @@ refinement of K^-1 mu, S GEMM, Gram adjoint) + Adam.
   sharded over the ranks and the images split over them (lvae_amd.distributed.
   LatentShardedClosedStep): strong scaling, value = whole-job ELBO-steps/s.
 
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up and times that step alone; `--dump-outputs DIR`
+writes what its last timed step returned and left behind (dump_outputs).  The sub-records below and the CPU
+baselines (`cpu_baseline`, `vs_cpu_baseline`) are measured only with `--full`.
+
 Sub-record `regime_a` (BASELINE configs[3], the path config/LVAE_config_sample.txt selects), at every N:
 the Hensman SVI step (training.py:90-140) at L = 16, M = 120, P_b = 5 subjects x T = 16 per rank, data
 parallel over subject mini-batches for N > 1 (weak scaling: value = whole-job ELBO-steps/s, samples_per_sec
@@ -64,6 +68,36 @@ U2_NAMES = {False: "ci_update_kernel<0>", True: "ci_update_kernel<2>"}
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, out, modules, extra=None):
+    """--dump-outputs: what the last timed step returned (`out`, its loss terms -> losses.npy) and left behind
+    (every parameter of `modules` after the update and its gradient from that step, plus `extra` tensors) as
+    path/<name>.npy, in float64 or float32 as computed.  If they exceed DUMP_MAX_BYTES together, each array over
+    its equal share of it is cut to a fixed, seeded sample of its elements, so two runs keep the same ones."""
+    import numpy as np
+    arrays = {"losses": torch.stack([v.detach().double().reshape(()) for v in out])}
+    for mname, mod in modules.items():
+        for pname, p in mod.named_parameters():
+            key = f"{mname}_{pname}".replace(".", "_")
+            arrays[key] = p
+            if p.grad is not None:
+                arrays[key + "_grad"] = p.grad
+    arrays.update(extra or {})
+    os.makedirs(path, exist_ok=True)
+    fits = sum(t.numel() * max(t.element_size(), 4) for t in arrays.values()) <= DUMP_MAX_BYTES
+    share = DUMP_MAX_BYTES // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().cpu()
+        a = (a if a.dtype in (torch.float32, torch.float64) else a.float()).numpy()
+        if not fits and a.nbytes > share:
+            keep = np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(keep)]
+        np.save(os.path.join(path, name + ".npy"), a)
+    log(f"dumped {len(arrays)} arrays to {path}")
 
 
 def pmc_traffic(kernels, per_step=False):
@@ -420,6 +454,8 @@ def run_closed(args, world, rank, dev):
         clocks.__exit__(None, None, None)
     if use_graph:
         graph.check()
+    if args.dump_outputs and rank == 0:  # (before anything below steps again)
+        dump_outputs(args.dump_outputs, out, {"kernel": kernel, "vae": vae})
     phase = {}
     if not args.no_phase_timing:
         if use_graph:
@@ -573,7 +609,7 @@ def run_closed(args, world, rank, dev):
 # ------------------------------------------------------------------------------------------
 # Regime A: Hensman SVI step, HIP-graph replayed
 # ------------------------------------------------------------------------------------------
-def run_hensman(args, world, rank, dev, dp_hooks=False):
+def run_hensman(args, world, rank, dev, dp_hooks=False, dump=None):
     import lvae_amd as la
     from lvae_amd.data import health_mnist_batch
     from lvae_amd.samplers import check_same_permutation, hensman_batches, SubjectSampler
@@ -631,6 +667,8 @@ def run_hensman(args, world, rank, dev, dp_hooks=False):
     sync_barrier(world)
     elapsed = max_over_ranks(time.perf_counter() - t0, world, dev)
     graphed.check()
+    if dump and rank == 0:
+        dump_outputs(dump, out, {"k0": k0, "k1": k1, "vae": vae}, {"m": step.m, "H": step.H})
     log(f"rank {rank}: Hensman last step (net, recon, nll, kld) = {[round(float(v), 4) for v in out]}")
     value = args.h_steps / elapsed
     return {"metric": "ELBO-steps/sec (Hensman SVI step, training.py:90-140)", "value": value,
@@ -816,10 +854,17 @@ def main():
     ap.add_argument("--P_b", type=int, default=5, help="Regime A: subjects per batch per rank")
     ap.add_argument("--M", type=int, default=120, help="Regime A: inducing points")
     ap.add_argument("--h-steps", dest="h_steps", type=int, default=100, help="Regime A timed steps")
-    # default: both regimes at every N -- the exact-KL line (latent dims sharded over the ranks at N > 1) and its
+    # --full: both regimes at every N -- the exact-KL line (latent dims sharded over the ranks at N > 1) and its
     # `regime_a` sub-record (BASELINE configs[3]: the Hensman step data parallel over subject mini-batches, two HIP
     # graphs around the RCCL all-reduces at N > 1)
     ap.add_argument("--regime", choices=["auto", "both", "closed", "hensman"], default="auto")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline line: the regime_a sub-record (with its world-1 RCCL form), the c2 "
+                         "comparison with PyTorch-ROCm and the CPU baselines (each can still be switched off by its "
+                         "--no-... option); without it only the headline steps are set up, warmed up and timed")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step of the headline path returned and "
+                         "left behind (losses, parameters, gradients) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-phase-timing", action="store_true")
     ap.add_argument("--no-c2", action="store_true")
@@ -841,7 +886,7 @@ def main():
     world, rank, local = setup_dist(force_group=args.sharded_world1)
     dev = torch.device("cuda", local)
     if args.regime == "auto":
-        args.regime = "both"
+        args.regime = "both" if args.full else "closed"
     res = None
     if args.regime in ("both", "closed"):
         res = run_closed(args, world, rank, dev)
@@ -855,8 +900,8 @@ def main():
                     raise
                 ra = {"error": f"{type(e).__name__}: {e}"[:300]}
         else:
-            ra = run_hensman(args, world, rank, dev)
-        if world == 1 and args.dp_world1:
+            ra = run_hensman(args, world, rank, dev, dump=args.dump_outputs)
+        if world == 1 and args.full and args.dp_world1:
             try:
                 ra["dp_world1_rccl"] = run_hensman_dp_world1(args, dev)
             except Exception as e:  # (a record of the failure; the line itself stands)
@@ -869,9 +914,9 @@ def main():
         else:
             res["regime_a"] = ra
     if rank == 0:
-        if world == 1 and not args.no_c2 and args.regime != "hensman":
+        if world == 1 and args.full and not args.no_c2 and args.regime != "hensman":
             res["c2"] = run_c2(dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             if args.regime in ("both", "closed"):
                 res["cpu_baseline"] = cpu_baseline_closed(args.P, args.T, args.L)
                 res["vs_cpu_baseline"] = res["value"] / res["cpu_baseline"]["value"]

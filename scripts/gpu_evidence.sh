@@ -34,7 +34,7 @@ cp $OUT/pmc/pmc_summary.json profiles/${TAG}_pmc_summary.json
 cp $OUT/pmc/pmc_summary.txt profiles/${TAG}_pmc_summary.txt
 cp $OUT/mfma/mfma_summary.json profiles/${TAG}_mfma_pmc.json
 cp $OUT/mfma/mfma_summary.txt profiles/${TAG}_mfma_pmc.txt
-timeout -k 10 900 python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail -20 $OUT/bench_default.err; exit 1; }
+timeout -k 10 900 python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail -20 $OUT/bench_default.err; exit 1; }
 python3 -c "
 import json; d = json.load(open('$OUT/bench_default.json'))
 print('default bench', round(d['ms_per_step'], 3), 'ms', d['roofline']['kernel'][:40], 'frac', round(d['roofline']['frac'], 3))

@@ -27,7 +27,7 @@ cat $OUT/hbpmc.txt
 # the bench line reads profiles/r5_*: this run's files (the same ones get committed)
 cp $OUT/headline_kernel_stats.csv profiles/r5_headline_kernel_stats.csv
 cp $OUT/pmc/pmc_summary.json profiles/r5_pmc_summary.json
-timeout -k 10 600 python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail -20 $OUT/bench_default.err; exit 1; }
+timeout -k 10 600 python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail -20 $OUT/bench_default.err; exit 1; }
 python3 -c "
 import json; d = json.load(open('$OUT/bench_default.json'))
 print('default bench', round(d['ms_per_step'], 3), 'ms', d['roofline']['kernel'][:40], 'frac', round(d['roofline']['frac'], 3))

@@ -3,7 +3,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 2
 mkdir -p gpurun_out/n2
 LVAE_DIST_BACKEND=gloo timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-  --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 3 --warmup 2 --h-steps 20 \
+  --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --full --steps 3 --warmup 2 --h-steps 20 \
   > gpurun_out/n2/bench.json 2> gpurun_out/n2/bench.err || { tail -30 gpurun_out/n2/bench.err; exit 1; }
 python3 -c "
 import json; d = json.load(open('gpurun_out/n2/bench.json'))

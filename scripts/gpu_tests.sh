@@ -10,6 +10,6 @@ rc=$?; echo "pytest rc=$rc"; grep -E "PASSED|FAILED|ERROR|rel err|errors|passed|
 [ $rc -eq 0 ] || exit $rc
 [ "${SKIP_BENCH:-0}" = "1" ] && exit 0
 echo "[$(date +%T)] bench"
-timeout -k 10 300 python bench.py --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline $BENCH_ARGS > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 300 python bench.py --full --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline $BENCH_ARGS > $OUT/bench.json 2> $OUT/bench.err
 rc=$?; echo "bench rc=$rc"; cat $OUT/bench.json; tail -3 $OUT/bench.err
 exit $rc
