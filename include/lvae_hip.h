@@ -80,7 +80,10 @@ typedef struct lvae_xview {
 
 /* out[b, l, i, j] = sum_r s_r prod_f phi(x1[b,l,i], x2[b,l,j]) + (i == j ? diag[l] : 0)
  * for b < nb, l < L, i < n1, j < n2.  out element (b,l,i,j) at
- * out[b*ostride_b + l*ostride_l + i*ldo + j].  diag may be NULL.  params: [L, n_params] fp64.
+ * out[b*ostride_b + l*ostride_l + i*ldo + j] (nothing else of out is written).  diag may be NULL
+ * (it is added for i == j < min(n1, n2)).  params: [L, n_params] fp64.  -1: a spec outside
+ * LVAE_MAX_COMP / LVAE_MAX_FAC / n_params <= 64, or a factor dim >= 32; -4: nb < 1, L < 1, n1 < 0 or
+ * n2 < 0; n1 == 0 or n2 == 0: returns 0 and writes nothing.  The adjoint rejects the same.
  * Replaces covar_module(x1, x2).evaluate() (+ noise * I) in elbo_functions.py:22-23,171-174. */
 int lvae_gram_f64(const lvae_kernel_spec* spec, lvae_xview x1, lvae_xview x2, int nb, int L, int n1,
                   int n2, const double* params, const double* diag, double* out, int64_t ostride_b,
@@ -208,7 +211,8 @@ int lvae_potrf_f32(int n, int L, const float* A, int64_t lda, int64_t stride_a, 
  * triangular (e.g. lvae_potrf_*'s output).  Blocked over 64 rows: the 64 x 64 diagonal blocks are
  * inverted first into the workspace (lvae_trsm_workspace_size(n, L) bytes, 256-B aligned), then one
  * workgroup per 64 columns of B sweeps the block rows in dependency order on the fp64 matrix cores.
- * The f32 variant reads / writes fp32 and computes in fp64.                                      */
+ * The f32 variant reads / writes fp32 and computes in fp64.  The strict upper part of Lf is not
+ * read (lvae_potrs_* too); of B only the [n, nrhs] extent is written; nrhs == 0 returns 0.       */
 size_t lvae_trsm_workspace_size(int n, int L);
 int lvae_trsm_f64(int trans, int n, int nrhs, int L, const double* Lf, int64_t ldl, int64_t stride_l, double* B,
                   int64_t ldb, int64_t stride_b, void* workspace, void* stream);
@@ -226,12 +230,15 @@ int lvae_potrs_f32(int n, int nrhs, int L, const float* Lf, int64_t ldl, int64_t
 /* ---------------------------------------------------------------------------------------- */
 
 /* Batched SPD factor + inverse of small matrices (n <= 128), one workgroup per matrix:
- * Ainv[b] = A[b]^-1, logdet[b] = log|A[b]|, info[b].  A, Ainv element (b,i,j) at [b*stride + i*n + j]. */
+ * Ainv[b] = A[b]^-1, logdet[b] = log|A[b]|, info[b].  A, Ainv element (b,i,j) at [b*stride + i*n + j].
+ * Only the lower triangle of A (j <= i) is read; both triangles of Ainv are written, and Ainv is
+ * exactly symmetric (Ainv[i][j] and Ainv[j][i] are the same bits).                              */
 int lvae_spd_inv_small_f64(int n, int batch, const double* A, int64_t stride, double* Ainv,
                            int64_t stride_out, double* logdet, int32_t* info, void* stream);
 
 /* Batched small fp64 GEMM: C[b] = alpha op(A[b]) op(B[b]) + beta C[b],
- * with b = (b1, b2), b1 < nb1, b2 < nb2, offsets b1*s?1 + b2*s?2.  op = transpose when t? != 0. */
+ * with b = (b1, b2), b1 < nb1, b2 < nb2, offsets b1*s?1 + b2*s?2.  op = transpose when t? != 0.
+ * beta == 0 overwrites C (it is not read).  -3 / -4 / -5: m / n / k < 0; -20 / -21: nb1 / nb2 < 1. */
 int lvae_gemm_small_f64(int ta, int tb, int m, int n, int k, double alpha, const double* A, int lda,
                         int64_t sa1, int64_t sa2, const double* B, int ldb, int64_t sb1, int64_t sb2,
                         double beta, double* C, int ldc, int64_t sc1, int64_t sc2, int nb1, int nb2,

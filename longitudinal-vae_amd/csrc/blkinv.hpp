@@ -216,7 +216,7 @@ struct BlkInvLds {
 // consecutive 16x16 tiles (tr, tc0 .. tc0+TPW-1) of one tile row.  Matrix padded to 16 TS with
 // the identity.
 //   in : element (i, j) at in[i * ldi + j], i, j < n; only the lower triangle is read
-//   out: A^-1 element (i, j) at out[i * ldo + j]
+//   out: A^-1 element (i, j) at out[i * ldo + j], both triangles, exactly symmetric
 //   logdet: log|A| (accumulate = 1: +=);  info: first bad pivot column + col_offset
 //   MODE 1 (the N x N potrf's diagonal blocks, potrf.hip): stop after pass 2 -- L into lout (lower, i >= j),
 //   Y = L^-1's strict lower part TRANSPOSED into out's strict upper triangle (out[j * ldo + i], i > j; out may be
@@ -411,12 +411,17 @@ __device__ inline void blk_inverse(int n, const T* in, int64_t ldi, T* out, int6
     }
   }
 #undef LVAE_BI_ROW_SOLVE
+  // A^-1 is symmetric, but the substitution reaches (i, j) and (j, i) by different sums, equal only to rounding:
+  // the lower triangle's value goes to both, so the inverse is EXACTLY symmetric (each pair has one writer)
 #pragma unroll
   for (int u = 0; u < TPW; ++u)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int i = tr * 16 + rw[r], j = (tc0 + u) * 16 + lc;
-      if (i < n && j < n) out[(int64_t)i * ldo + j] = acc[u][r];
+      if (i < n && j <= i) {
+        out[(int64_t)i * ldo + j] = acc[u][r];
+        if (j < i) out[(int64_t)j * ldo + i] = acc[u][r];
+      }
     }
   }
   // log|A| = 2 sum log L_jj over the pivot blocks (off the step critical path)

@@ -1782,7 +1782,8 @@ size_t lvae_gram_bwd_workspace_size(int nb, int L, int n1, int n2) {
 int lvae_gram_bwd_f64(const lvae_kernel_spec* spec, lvae_xview x1, lvae_xview x2, int nb, int L, int n1, int n2,
                       const double* params, const double* G, int64_t gsb, int64_t gsl, int64_t ldg, double* dparams,
                       double* ddiag, void* workspace, void* stream) {
-  if (!spec) return -1;
+  // (the forward's limits: a spec no template bucket holds, a factor on a covariate column >= kMaxQ)
+  if (!spec || !lvae::spec_bucket(spec) || lvae::spec_qs(spec) > lvae::kMaxQ) return -1;
   if (nb < 1 || L < 1 || n1 < 0 || n2 < 0) return -4;
   if (!params) return -8;
   if (!G) return -9;

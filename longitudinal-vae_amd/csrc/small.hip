@@ -128,8 +128,11 @@ int spd_inv_small_f64(int n, int batch, const double* A, int64_t stride, double*
 int gemm_small_f64(int ta, int tb, int m, int n, int k, double alpha, const double* A, int lda, int64_t sa1,
                    int64_t sa2, const double* B, int ldb, int64_t sb1, int64_t sb2, double beta, double* C, int ldc,
                    int64_t sc1, int64_t sc2, int nb1, int nb2, hipStream_t st) {
-  if (m < 0 || n < 0 || k < 0) return -3;
-  if (nb1 < 1 || nb2 < 1) return -20;
+  if (m < 0) return -3;
+  if (n < 0) return -4;
+  if (k < 0) return -5;
+  if (nb1 < 1) return -20;
+  if (nb2 < 1) return -21;
   if (m == 0 || n == 0) return 0;
   dim3 grid(cdiv(n, kGS), cdiv(m, kGS), nb1 * nb2);
   gemm_small_kernel<<<grid, 256, 0, st>>>(ta, tb, m, n, k, alpha, A, lda, sa1, sa2, B, ldb, sb1, sb2, beta, C, ldc,

@@ -182,3 +182,172 @@ def test_kl_closed_through_linalg_matches_oracle(hip):
     ref = 0.5 * ((torch.exp(lv) * torch.diagonal(iKr, dim1=-2, dim2=-1)).sum(-1)
                  + (mu * (iKr @ mu.unsqueeze(-1)).squeeze(-1)).sum(-1) - n + ldr - lv.sum(-1))
     assert rel(kld, ref) < 1e-11
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# The solves and factors called directly through the C ABI at their edges: n below / at / above one 64-block,
+# ld > the row length and padded batch strides in NaN-filled buffers (the padding must come back untouched), the
+# strict upper triangle of every triangular or symmetric input NaN (the header: it is not read), and the 1-based
+# argument-index return codes.  Tolerances: this file's own (above).
+# ------------------------------------------------------------------------------------------------------------------
+import ctypes  # noqa: E402
+
+import abi_util as U  # noqa: E402
+
+
+def _solve_operands(n, nrhs, L, dtype):
+    """fp64 CPU (Lf, B) already rounded to dtype, and their padded device buffers (Lf's strict upper part NaN)"""
+    A = U.spd(L, n, seed=100 * n + nrhs, cond=1e3 if dtype == torch.float64 else 1e2)
+    Lf = O.potrf(A)[0].to(dtype)
+    B = torch.randn(L, n, max(nrhs, 1), generator=torch.Generator().manual_seed(n + nrhs), dtype=torch.float64)
+    B = B[:, :, :nrhs].to(dtype)
+    ldl, ldb = n + 3, nrhs + 3
+    ls, bs = (n * ldl + 5, ldl, 1), (n * ldb + 7, ldb, 1)
+    Lbuf, _ = U.padded(U.nan_upper(Lf), ls)
+    return Lf.double(), B.double(), Lbuf, ls, bs
+
+
+def _solve(fn, lead, n, nrhs, L, Lbuf, ls, B, bs, dtype, hip):
+    """one lvae_trsm_* (lead = (trans,)) or lvae_potrs_* (lead = ()) call on a fresh padded copy of B"""
+    from lvae_amd import _lib as P
+    if nrhs:
+        Bbuf, _ = U.padded(B.to(dtype), bs)
+    else:
+        Bbuf = U.sentinel(L * bs[0] + 5, dtype)
+    ws, tail = U.workspace(hip.lvae_trsm_workspace_size(n, L))
+    rc = fn(*lead, n, nrhs, L, P.ptr(Lbuf), ls[1], ls[0], P.ptr(Bbuf), bs[1], bs[0], P.ptr(ws), P.stream_ptr())
+    torch.cuda.synchronize()
+    assert rc == 0
+    assert U.tail_untouched(tail)
+    if not nrhs:
+        assert U.all_sentinel(Bbuf)   # nrhs = 0: ok, nothing written
+        return None
+    assert U.untouched_outside(Bbuf, B.shape, bs)
+    return U.view(Bbuf, B.shape, bs).cpu().double()
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+@pytest.mark.parametrize("nrhs", [0, 1, 63, 64, 65])
+@pytest.mark.parametrize("n", [1, 17, 63, 64, 65, 130])
+def test_trsm_potrs_abi_edges(hip, n, nrhs, dtype):
+    L = 2
+    f64 = dtype == torch.float64
+    tol = 1e-11 if f64 else 1e-5
+    trsm = hip.lvae_trsm_f64 if f64 else hip.lvae_trsm_f32
+    potrs = hip.lvae_potrs_f64 if f64 else hip.lvae_potrs_f32
+    Lf, B, Lbuf, ls, bs = _solve_operands(n, nrhs, L, dtype)
+    refs = [((0,), trsm, lambda: torch.linalg.solve_triangular(Lf, B, upper=False)),
+            ((1,), trsm, lambda: torch.linalg.solve_triangular(Lf.transpose(-1, -2), B, upper=True)),
+            ((), potrs, lambda: O.potrs(B, Lf))]
+    for lead, fn, ref in refs:
+        got = _solve(fn, lead, n, nrhs, L, Lbuf, ls, B, bs, dtype, hip)
+        if nrhs:
+            assert rel(got, ref()) < tol, (lead, rel(got, ref()))
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+@pytest.mark.parametrize("n", [1, 65, 300])
+def test_potrf_abi_edges(hip, n, dtype):
+    """lda > n, ldo > n, padded batch strides, A's strict upper triangle NaN: only the lower triangle is read, the
+    factor's strict upper part is zero, nothing outside the [n, n] extents is written"""
+    from lvae_amd import _lib as P
+    L = 2
+    f64 = dtype == torch.float64
+    A = U.spd(L, n, seed=n + 2, cond=1e3 if f64 else 1e2)
+    Lr, ldr = O.potrf(A)
+    lda, ldo = n + 3, n + 5
+    sa, so = (n * lda + 5, lda, 1), (n * ldo + 7, ldo, 1)
+    Abuf, _ = U.padded(U.nan_upper(A).to(dtype), sa)
+    Obuf = U.sentinel(U.extent((L, n, n), so) + 5, dtype)
+    ld = U.sentinel(L + 2)
+    info = U.sentinel(L + 2, torch.int32)
+    if f64:
+        rc = hip.lvae_potrf_f64(n, L, P.ptr(Abuf), lda, sa[0], P.ptr(Obuf), ldo, so[0], P.ptr(ld), P.ptr(info),
+                                P.stream_ptr())
+    else:
+        ws, tail = U.workspace(hip.lvae_potrf_f32_workspace_size(n, L))
+        rc = hip.lvae_potrf_f32(n, L, P.ptr(Abuf), lda, sa[0], P.ptr(Obuf), ldo, so[0], P.ptr(ld), P.ptr(info),
+                                P.ptr(ws), P.stream_ptr())
+    torch.cuda.synchronize()
+    assert rc == 0
+    assert f64 or U.tail_untouched(tail)
+    assert U.untouched_outside(Obuf, (L, n, n), so) and U.all_sentinel(ld[L:]) and U.all_sentinel(info[L:])
+    assert info[:L].tolist() == [0] * L
+    Lg = U.view(Obuf, (L, n, n), so).cpu()
+    assert torch.equal(torch.triu(Lg, 1), torch.zeros(L, n, n, dtype=dtype))
+    assert rel(Lg, Lr) < (1e-11 if f64 else 2e-5)
+    assert rel(ld[:L], ldr) < (1e-12 if f64 else 1e-5) or (n == 1 and float((ld[:L].cpu() - ldr).abs().max()) < 1e-12)
+
+
+def _rc_fixture(dtype):
+    n, nrhs, L = 8, 4, 1
+    A = U.spd(L, n, seed=1, cond=10.0)
+    Ad = A.to(DEV, dtype).contiguous()
+    Lf = O.potrf(A)[0].to(DEV, dtype).contiguous()
+    B = torch.arange(n * nrhs, dtype=dtype, device=DEV).reshape(L, n, nrhs) + 1
+    return n, nrhs, L, Ad, Lf, B
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+def test_potrf_return_codes(hip, dtype):
+    """-(1-based index of the offending argument); nothing is written"""
+    from lvae_amd import _lib as P
+    f64 = dtype == torch.float64
+    n, _, L, Ad, _, _ = _rc_fixture(dtype)
+    A0 = Ad.clone()
+    out = U.sentinel(L * n * n, dtype)
+    ld, info = U.sentinel(L), U.sentinel(L, torch.int32)
+    ws, _ = U.workspace(hip.lvae_potrf_f32_workspace_size(n, L))
+    good = dict(n=n, L=L, A=P.ptr(Ad), lda=n, sa=n * n, Lo=P.ptr(out), ldo=n, so=n * n, ld=P.ptr(ld), info=P.ptr(info),
+                ws=P.ptr(ws))
+
+    def call(**kw):
+        a = dict(good, **kw)
+        lead = (a["n"], a["L"], a["A"], a["lda"], a["sa"], a["Lo"], a["ldo"], a["so"], a["ld"], a["info"])
+        rc = (hip.lvae_potrf_f64(*lead, P.stream_ptr()) if f64 else hip.lvae_potrf_f32(*lead, a["ws"], P.stream_ptr()))
+        torch.cuda.synchronize()
+        return rc
+    cases = [(dict(n=0), -1), (dict(L=0), -2), (dict(A=None), -3), (dict(lda=n - 1), -4), (dict(Lo=None), -6),
+             (dict(ldo=n - 1), -7), (dict(ld=None), -9), (dict(info=None), -10)]
+    if f64:
+        cases.append((dict(Lo=P.ptr(Ad), ldo=n + 1), -7))   # in place needs ldo == lda
+    else:
+        cases += [(dict(ws=None), -11), (dict(ws=ctypes.c_void_p(ws.data_ptr() + 8)), -11),
+                  (dict(n=16385, lda=16385, ldo=16385), -1)]   # n <= 16384
+    for kw, want in cases:
+        assert call(**kw) == want, (kw, want)
+        assert U.all_sentinel(out) and U.all_sentinel(ld) and U.all_sentinel(info) and torch.equal(Ad, A0), kw
+    assert call() == 0 and not U.all_sentinel(out)
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+def test_trsm_potrs_return_codes(hip, dtype):
+    """lvae_trsm_*: trans is argument 1, so n .. workspace are 2 .. 11; lvae_potrs_* has no trans: the same checks
+    report one less.  B is unchanged after a rejected call."""
+    from lvae_amd import _lib as P
+    f64 = dtype == torch.float64
+    n, nrhs, L, _, Lf, B = _rc_fixture(dtype)
+    B0 = B.clone()
+    ws, _ = U.workspace(hip.lvae_trsm_workspace_size(n, L))
+    good = dict(trans=0, n=n, nrhs=nrhs, L=L, Lf=P.ptr(Lf), ldl=n, sl=n * n, B=P.ptr(B), ldb=nrhs, sb=n * nrhs,
+                ws=P.ptr(ws))
+    trsm = hip.lvae_trsm_f64 if f64 else hip.lvae_trsm_f32
+    potrs = hip.lvae_potrs_f64 if f64 else hip.lvae_potrs_f32
+
+    def call(fn, **kw):
+        a = dict(good, **kw)
+        rest = (a["n"], a["nrhs"], a["L"], a["Lf"], a["ldl"], a["sl"], a["B"], a["ldb"], a["sb"], a["ws"])
+        rc = fn(a["trans"], *rest, P.stream_ptr()) if fn is trsm else fn(*rest, P.stream_ptr())
+        torch.cuda.synchronize()
+        return rc
+    assert call(trsm, trans=2) == -1 and torch.equal(B, B0)
+    assert call(trsm, trans=-1) == -1 and torch.equal(B, B0)
+    cases = [(dict(n=0), -2), (dict(nrhs=-1), -3), (dict(L=0), -4), (dict(Lf=None), -5), (dict(ldl=n - 1), -6),
+             (dict(B=None), -8), (dict(ldb=nrhs - 1), -9), (dict(ws=None), -11),
+             (dict(ws=ctypes.c_void_p(ws.data_ptr() + 8)), -11)]
+    for kw, want in cases:
+        assert call(trsm, **kw) == want, (kw, want)
+        assert call(potrs, **kw) == want + 1, (kw, want + 1)
+        assert torch.equal(B, B0), kw
+    assert call(trsm) == 0 and not torch.equal(B, B0)
+    assert call(potrs) == 0
