@@ -255,10 +255,17 @@ typedef struct lvae_hensman_dims {
                            /* SUM all-reduce of the per-rank directions equals the union batch */
   const int32_t* seg_len;  /* varying T (minibatch_KLD_upper_bound_iter, elbo_functions.py:219-307): */
                            /* device [P_b] valid rows per subject, rows T_p..T-1 of subject p are  */
-                           /* padding (masked out of every term); NULL = all T rows valid          */
+                           /* padding (masked out of every term); NULL = all T rows valid.         */
+                           /* Padding rows of x are any finite covariates; padding rows of mu /    */
+                           /* logv are not read (they may hold anything, NaN included); padding    */
+                           /* rows of dmu / dlogv are written as 0.  A subject with seg_len == 0   */
+                           /* contributes nothing to any sum (it still counts in P_b: pass         */
+                           /* P_tot = P P_b / (subjects with rows) for the scale P / P_in_batch)   */
   double n_total;          /* N of the constant -L N / 2; 0 -> P_tot * T                          */
 } lvae_hensman_dims;
 
+/* The two size functions read *d unchecked (d must not be NULL; sizes are only meaningful for dims that the
+ * calls below accept). */
 size_t lvae_hensman_workspace_size(const lvae_hensman_dims* d);
 /* Byte offset inside the Hensman workspace of H^-1 [L, M, M] as left by lvae_hensman_fwd_f64
  * (valid until the workspace is reused; lets the natural-gradient update skip re-inverting H). */
@@ -266,7 +273,14 @@ size_t lvae_hensman_iH_offset(const lvae_hensman_dims* d);
 
 /* Forward of minibatch_KLD_upper_bound: kld (scalar, sum over L), grad_m [L,M], grad_H [L,M,M]
  * (natural_gradient only; may be NULL otherwise).  x [P_b*T, Q], z [L, M, Q], m [L, M], H [L, M, M],
- * mu / logv [P_b*T, L] (fp64, row-major), params0 [L, P0], params1 [L, P1], noise [L].          */
+ * mu / logv [P_b*T, L] (fp64, row-major), params0 [L, P0], params1 [L, P1], noise [L].
+ * info [L] (may be NULL): 0, or the first failed factorisation of dim l in the order K0zz (10000 + col),
+ * B_p (20000 + col, the first such subject), H (30000 + col), col the 1-based failing column; kld and the
+ * gradients of such a call mean nothing.
+ * Return codes of the three Hensman calls (all checked before any launch, nothing is written): -1 / -2: spec0 /
+ * spec1 NULL or outside every template bucket; -3: d NULL, L < 1, M or T outside 1..128, P_b < 1 or Q < 1; then,
+ * forward: -18: part outside 0..2, -17: workspace NULL or not 256-byte aligned; backward: -21: workspace NULL
+ * or not 256-byte aligned.  0 = ok.                                                             */
 int lvae_hensman_fwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1,
                          const lvae_hensman_dims* d, const double* x, const double* z, const double* m,
                          const double* H, const double* mu, const double* logv, const double* params0,
@@ -275,7 +289,10 @@ int lvae_hensman_fwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* 
 /* The same forward in two parts on one workspace (part 0: both): part 1 needs neither mu nor logv
  * (Grams, the K0zz / B_p / H inverses, iK m, K0xz iK m, Q = K0xz^T B^-1 K0xz, iK H iK and the
  * data-independent natural-gradient terms incl. grad_H) and can run beside the encoder; part 2 (the
- * residual, the sums -> kld, grad_m, info) then reads mu / logv.  Same results as the one call.    */
+ * residual, the sums -> kld, grad_m, info) then reads mu / logv.  Same results as the one call, bit for bit.
+ * Part 1 may get NULL mu / logv (and kld / info, which part 2 writes).  Both parts must receive the same
+ * grad_m / grad_H pointers (NULL in both, or the same buffers): part 1 writes grad_H and decides by them
+ * whether to prepare the terms of grad_m, which part 2 writes.                                       */
 int lvae_hensman_fwd_part_f64(int part, const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1,
                               const lvae_hensman_dims* d, const double* x, const double* z, const double* m,
                               const double* H, const double* mu, const double* logv, const double* params0,
@@ -284,7 +301,9 @@ int lvae_hensman_fwd_part_f64(int part, const lvae_kernel_spec* spec0, const lva
 
 /* Backward given dL/dkld = *gkld (device scalar): dmu, dlogv [P_b*T, L]; dparams0 [L,P0],
  * dparams1 [L,P1], dnoise [L]; dm [L,M], dH [L,M,M] when !natural_gradient (else may be NULL).
- * Outputs are OVERWRITTEN.                                                                   */
+ * Outputs are OVERWRITTEN (whatever they held); dnoise may be NULL; with natural_gradient dm / dH are not
+ * touched, and without it the forward does not touch grad_m / grad_H.  Runs on the workspace the forward
+ * left.                                                                                         */
 int lvae_hensman_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1,
                          const lvae_hensman_dims* d, const double* x, const double* z, const double* m,
                          const double* H, const double* mu, const double* logv, const double* params0,
@@ -375,7 +394,11 @@ int lvae_deconv4s2_relu_bwd_f32(const float* gy, const float* y, const float* x,
  * (seg_len [P] valid rows each; padding rows of x are any finite covariates, of mu must be 0),
  * x [P*T, Q], mu [P*T, L]; include [P] = 1 for subjects that also appear in test_x (the k1 term);
  * z [L, M, Q]; test_x [Nt, Q]; out [Nt, L].  info[l]: 10000/20000/30000 + col for a failed
- * K0zz / B_p / H factorisation.  workspace: lvae_predict_workspace_size(L, M, P, T, Nt) bytes. */
+ * K0zz / B_p / H factorisation, the first of them in that order (info may be NULL; it is written for
+ * Nt == 0 too, out is not).  workspace: lvae_predict_workspace_size(L, M, P, T, Nt) bytes.
+ * Return codes (all checked before any launch): -1: spec0 / spec1 NULL or outside every template bucket;
+ * -3: L < 1 or M outside 1..128; -6: P < 1, T outside 1..128 or Q < 1; -8: seg_len or include NULL;
+ * -13: Nt < 0; -20: workspace NULL or not 256-byte aligned.  0 = ok.                              */
 size_t lvae_predict_workspace_size(int L, int M, int P, int T, int Nt);
 int lvae_predict_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, int L, int M, int Q, int P,
                      int T, const int32_t* seg_len, const int32_t* include, const double* x,

@@ -117,6 +117,16 @@ __global__ void resid_kernel(const double* __restrict__ y, const double* __restr
   r[e] = seg_valid(seg, i / T, i % T) ? y[e] - mu[(int64_t)i * L + l] : 0.0;
 }
 
+// mm[l][i] = mu[i][l] on the valid rows, 0 on the padding rows whatever mu holds there (varying T only: the
+// natural-gradient branch's u = iB mu must not read them, 0 * NaN from iB's identity padding would reach grad_m)
+__global__ void masked_mu_kernel(const double* __restrict__ mu, int B, int L, int T, const int32_t* __restrict__ seg,
+                                 double* __restrict__ mm) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= B * L) return;
+  const int l = e / B, i = e % B;
+  mm[e] = seg_valid(seg, i / T, i % T) ? mu[(int64_t)i * L + l] : 0.0;
+}
+
 // per-dim partial sums, each dim's elements split over kHnSlices workgroups (more reads in flight than one
 // workgroup per dim): part[l][slice][0..] = A, Bt, C, D1, D2, E, F, tr1, qf1, ldK, ldH
 __global__ __launch_bounds__(256) void hn_reduce_kernel(int M, int P_b, int T, int L, const double* __restrict__ r,
@@ -394,8 +404,14 @@ int lvae_hensman_fwd_part_f64(int part, const lvae_kernel_spec* spec0, const lva
                                         w.t, w.ldK, w.ldH, d.seg_len, w.part);
     hn_final_kernel<<<1, 64, 0, st>>>(L, M, d.P_tot, P_b, d.n_total > 0.0 ? d.n_total : d.P_tot * T, w.part, kld);
     if (ng) {  // u = iB mu ; w = K0xz^T u ; a = iK w ; grad_m = Bn m - a
-      LVAE_TRY(gemm_small_f64(0, 0, T, 1, T, 1.0, w.iB, T, P_b * TT, TT, mu, L, 1, (int64_t)T * L, 0.0, w.u, 1, B,
-                              T, L, P_b, st));
+      if (d.seg_len) {  // padding rows of mu are not read: a masked copy [L,B] in tBM (free until the backward)
+        masked_mu_kernel<<<blocks((int64_t)B * L), 256, 0, st>>>(mu, B, L, T, d.seg_len, w.tBM);
+        LVAE_TRY(gemm_small_f64(0, 0, T, 1, T, 1.0, w.iB, T, P_b * TT, TT, w.tBM, 1, B, T, 0.0, w.u, 1, B, T, L, P_b,
+                                st));
+      } else {
+        LVAE_TRY(gemm_small_f64(0, 0, T, 1, T, 1.0, w.iB, T, P_b * TT, TT, mu, L, 1, (int64_t)T * L, 0.0, w.u, 1, B,
+                                T, L, P_b, st));
+      }
       LVAE_TRY(gemm_small_f64(1, 0, M, 1, B, 1.0, w.K0xz, M, BM, 0, w.u, 1, B, 0, 0.0, w.w, 1, M, 0, L, 1, st));
       LVAE_TRY(gemm_small_f64(0, 0, M, 1, M, 1.0, w.iK, M, MM, 0, w.w, 1, M, 0, 0.0, w.a, 1, M, 0, L, 1, st));
       lincomb_kernel<<<blocks((int64_t)L * M), 256, 0, st>>>((int64_t)L * M, 1.0, w.tM, -1.0, w.a, grad_m, nullptr,

@@ -7,6 +7,8 @@
 //   B_p = k1(x_p, x_p) + noise I,  iB = B^-1 (block diagonal),  H = K0zz + K0xz^T iB K0xz
 //   mu~ = iB mu - iB K0xz H^-1 K0xz^T iB mu
 //   Z(X*) = K0X*z K0zz^-1 K0xz^T mu~ + k1(X*, x[test subjects]) mu~[test subjects]
+// H^-1 and K0zz^-1 are applied as explicit inverses followed by one residual refinement step each (the reference
+// solves; the bare product is cond(.) ulps worse than that).
 // The reference's per-subject Python loops become one batched pass (padding rows of K0xz zeroed,
 // padding blocks of B set to I, padding rows of mu zeroed by the caller).  The k1 term is the
 // reference's dense product over all prediction rows of the test subjects (include[p] = 1),
@@ -30,7 +32,7 @@ namespace {
 constexpr int64_t kPredChunkElems = 1 << 24;  // k1(X*, x) chunk: <= 128 MiB of fp64
 
 struct PWs {
-  double *K0xz, *iBK, *K0zz, *Hm, *iK, *iH, *Bst, *iB, *iBmu, *t, *muT, *muTm, *w, *v, *a, *b, *K0Xz, *out1, *K1;
+  double *K0xz, *iBK, *K0zz, *Hm, *iK, *iH, *Bst, *iB, *iBmu, *t, *muT, *muTm, *w, *v, *a, *b, *rr, *K0Xz, *out1, *K1;
   double *ldK, *ldH, *ldB;
   int32_t* info;
   int64_t chunk_rows;
@@ -59,6 +61,7 @@ struct PWs {
     v = take((size_t)L * M);
     a = take((size_t)L * M);
     b = take((size_t)L * M);
+    rr = take((size_t)L * M);
     K0Xz = take((size_t)L * Nt * M);
     out1 = take((size_t)L * Nt);
     int64_t rows = kPredChunkElems / ((int64_t)L * (int64_t)NP);
@@ -117,7 +120,8 @@ __global__ void pr_eye_add_kernel(int L, int M, double eps, double* __restrict__
   Hm[e] += k;
 }
 
-// info[l]: first failing factorisation: K0zz (10000 + col), H (30000 + col), B_p (20000 + col)
+// info[l]: first failing factorisation in the order K0zz (10000 + col), B_p (20000 + col), H (30000 + col); w holds
+// the raw codes as [K0zz: L][H: L][B_p: L*P]
 __global__ void pr_info_kernel(int L, int P, const int32_t* __restrict__ w, int32_t* __restrict__ info) {
   const int l = blockIdx.x * blockDim.x + threadIdx.x;
   if (l >= L) return;
@@ -154,7 +158,7 @@ int lvae_predict_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec
                      const int32_t* seg_len, const int32_t* include, const double* x, const double* mu,
                      const double* z, int Nt, const double* test_x, const double* params0, const double* params1,
                      const double* noise, double eps, double* out, int32_t* info, void* workspace, void* stream) {
-  if (!spec0 || !spec1) return -1;
+  if (!spec0 || !spec1 || !spec_bucket(spec0) || !spec_bucket(spec1)) return -1;  // (before any launch)
   if (L < 1 || M < 1 || M > 128) return -3;
   if (P < 1 || T < 1 || T > 128 || Q < 1) return -6;
   if (!seg_len || !include) return -8;
@@ -184,12 +188,21 @@ int lvae_predict_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec
   // mu~ = iB mu - iB K0xz H^-1 K0xz^T iB mu
   LVAE_TRY(gemm_small_f64(1, 0, M, 1, NP, 1.0, w.K0xz, M, NPM, 0, w.iBmu, 1, NP, 0, 0.0, w.w, 1, M, 0, L, 1, st));
   LVAE_TRY(gemm_small_f64(0, 0, M, 1, M, 1.0, w.iH, M, MM, 0, w.w, 1, M, 0, 0.0, w.v, 1, M, 0, L, 1, st));
+  // one refinement step, v += H^-1 (w - H v): the product with the explicit inverse alone loses cond(H) ulps where
+  // the reference's solve (utils.py:183) does not; rr = w again (the same GEMM), then rr -= H v
+  LVAE_TRY(gemm_small_f64(1, 0, M, 1, NP, 1.0, w.K0xz, M, NPM, 0, w.iBmu, 1, NP, 0, 0.0, w.rr, 1, M, 0, L, 1, st));
+  LVAE_TRY(gemm_small_f64(0, 0, M, 1, M, -1.0, w.Hm, M, MM, 0, w.v, 1, M, 0, 1.0, w.rr, 1, M, 0, L, 1, st));
+  LVAE_TRY(gemm_small_f64(0, 0, M, 1, M, 1.0, w.iH, M, MM, 0, w.rr, 1, M, 0, 1.0, w.v, 1, M, 0, L, 1, st));
   LVAE_TRY(gemm_small_f64(0, 0, NP, 1, M, 1.0, w.iBK, M, NPM, 0, w.v, 1, M, 0, 0.0, w.t, 1, NP, 0, L, 1, st));
   pr_mutilde_kernel<<<nblk((int64_t)L * NP), 256, 0, st>>>(L, P, T, seg_len, include, w.iBmu, w.t, w.muT, w.muTm);
   if (Nt > 0) {
     // K0X*z K0zz^-1 K0xz^T mu~
     LVAE_TRY(gemm_small_f64(1, 0, M, 1, NP, 1.0, w.K0xz, M, NPM, 0, w.muT, 1, NP, 0, 0.0, w.a, 1, M, 0, L, 1, st));
     LVAE_TRY(gemm_small_f64(0, 0, M, 1, M, 1.0, w.iK, M, MM, 0, w.a, 1, M, 0, 0.0, w.b, 1, M, 0, L, 1, st));
+    // the same refinement step for b = K0zz^-1 a (utils.py:190 solves)
+    LVAE_TRY(gemm_small_f64(1, 0, M, 1, NP, 1.0, w.K0xz, M, NPM, 0, w.muT, 1, NP, 0, 0.0, w.rr, 1, M, 0, L, 1, st));
+    LVAE_TRY(gemm_small_f64(0, 0, M, 1, M, -1.0, w.K0zz, M, MM, 0, w.b, 1, M, 0, 1.0, w.rr, 1, M, 0, L, 1, st));
+    LVAE_TRY(gemm_small_f64(0, 0, M, 1, M, 1.0, w.iK, M, MM, 0, w.rr, 1, M, 0, 1.0, w.b, 1, M, 0, L, 1, st));
     LVAE_TRY(gemm_small_f64(0, 0, Nt, 1, M, 1.0, w.K0Xz, M, (int64_t)Nt * M, 0, w.b, 1, M, 0, 0.0, w.out1, 1, Nt, 0, L,
                             1, st));
     // + k1(X*, x) mu~[test subjects], chunked over test rows (utils.py:191-209)

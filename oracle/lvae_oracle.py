@@ -220,27 +220,27 @@ def hensman_kld_iter(spec0, params0, spec1, params1, noise, m, H, x, mu, logv, z
     """minibatch_KLD_upper_bound_iter (elbo_functions.py:219-307): the same bound for subjects of
     varying length, a loop over the batch's subjects (torch.unique order, elbo_functions.py:249)."""
     Lh, M = H.shape[0], H.shape[-1]
-    dt = x.dtype
+    dt, dev = x.dtype, x.device  # device-agnostic, as hensman_kld
     K0xz = gram(spec0, params0, x, z)
-    K0zz = gram(spec0, params0, z, z) + eps * torch.eye(M, dtype=dt)
+    K0zz = gram(spec0, params0, z, z) + eps * torch.eye(M, dtype=dt, device=dev)
     LK = torch.linalg.cholesky(K0zz)
-    iK = torch.cholesky_solve(torch.eye(M, dtype=dt), LK)
+    iK = torch.cholesky_solve(torch.eye(M, dtype=dt, device=dev), LK)
     LH = torch.linalg.cholesky(H)
-    iH = torch.cholesky_solve(torch.eye(M, dtype=dt), LH)
+    iH = torch.cholesky_solve(torch.eye(M, dtype=dt, device=dev), LH)
     Apart = ((K0xz @ (iK @ m)).squeeze(-1) - mu.T).unsqueeze(2)          # [L, B, 1]
     Epart = iK @ H @ iK
-    A = Bt = C = D = E = torch.zeros((), dtype=dt)
-    P1 = torch.zeros(Lh, M, 1, dtype=dt)
-    P2 = torch.zeros(Lh, M, M, dtype=dt)
+    A = Bt = C = D = E = torch.zeros((), dtype=dt, device=dev)
+    P1 = torch.zeros(Lh, M, 1, dtype=dt, device=dev)
+    P2 = torch.zeros(Lh, M, M, dtype=dt, device=dev)
     for s in torch.unique(x[:, id_col]).tolist():
         sel = x[:, id_col] == s
         tx = x[sel]
         T = tx.shape[0]
         st = tx.unsqueeze(0).expand(Lh, T, tx.shape[-1])
         K0 = gram(spec0, params0, st, st)
-        Bm = gram(spec1, params1, st, st) + torch.eye(T, dtype=dt) * noise.reshape(Lh, 1, 1)
+        Bm = gram(spec1, params1, st, st) + torch.eye(T, dtype=dt, device=dev) * noise.reshape(Lh, 1, 1)
         LB = torch.linalg.cholesky(Bm)
-        iB = torch.cholesky_solve(torch.eye(T, dtype=dt), LB)
+        iB = torch.cholesky_solve(torch.eye(T, dtype=dt, device=dev), LB)
         Ks = K0xz[:, sel]
         Qs = Ks.transpose(1, 2) @ iB @ Ks
         ap = Apart[:, sel]
@@ -268,13 +268,13 @@ def hensman_kld_iter(spec0, params0, spec1, params1, noise, m, H, x, mu, logv, z
 def batch_predict_varying_T(spec0, params0, spec1, params1, noise, pred_x, test_x, mu, z, id_col, eps):
     """GP posterior mean of the latents at test_x (utils.py:115-211): Z_pred [N_test, L]."""
     Lh, M = z.shape[0], z.shape[1]
-    dt = pred_x.dtype
+    dt, dev = pred_x.dtype, pred_x.device  # device-agnostic, as hensman_kld
     K0xz = gram(spec0, params0, pred_x, z)
-    K0zz = gram(spec0, params0, z, z) + eps * torch.eye(M, dtype=dt)
+    K0zz = gram(spec0, params0, z, z) + eps * torch.eye(M, dtype=dt, device=dev)
     K0Xz = gram(spec0, params0, test_x, z)
     K0zx = K0xz.transpose(-1, -2)
     H = K0zz
-    iB_mu = torch.zeros(Lh, pred_x.shape[0], 1, dtype=dt)
+    iB_mu = torch.zeros(Lh, pred_x.shape[0], 1, dtype=dt, device=dev)
     iBs = []
     subjects = torch.unique(pred_x[:, id_col]).tolist()
     for s in subjects:
@@ -282,8 +282,8 @@ def batch_predict_varying_T(spec0, params0, spec1, params1, noise, pred_x, test_
         xs = pred_x[sel]
         T = xs.shape[0]
         st = xs.unsqueeze(0).expand(Lh, T, xs.shape[-1])
-        Bm = gram(spec1, params1, st, st) + torch.eye(T, dtype=dt) * noise.reshape(Lh, 1, 1)
-        iB = torch.cholesky_solve(torch.eye(T, dtype=dt), torch.linalg.cholesky(Bm))
+        Bm = gram(spec1, params1, st, st) + torch.eye(T, dtype=dt, device=dev) * noise.reshape(Lh, 1, 1)
+        iB = torch.cholesky_solve(torch.eye(T, dtype=dt, device=dev), torch.linalg.cholesky(Bm))
         Ks = K0xz[:, sel]
         H = H + Ks.transpose(-1, -2) @ iB @ Ks
         iB_mu[:, sel] = iB @ mu[sel].T.unsqueeze(2)
@@ -296,7 +296,7 @@ def batch_predict_varying_T(spec0, params0, spec1, params1, noise, pred_x, test_
     mu_tilde = iB_mu - corr
     out = K0Xz @ torch.linalg.solve(K0zz, K0zx @ mu_tilde)
     test_subjects = torch.unique(test_x[:, id_col]).tolist()
-    mask = torch.isin(pred_x[:, id_col], torch.tensor(test_subjects, dtype=dt))
+    mask = torch.isin(pred_x[:, id_col], torch.tensor(test_subjects, dtype=dt, device=dev))
     pm = pred_x[mask]
     for s in test_subjects:
         sel = test_x[:, id_col] == s

@@ -1,6 +1,8 @@
 """Helpers of the C-ABI edge tests (test_gpu_gram_abi.py, test_gpu_small_abi.py, the solve / factor
-edge tests of test_gpu_linalg.py): sentinel-filled device buffers with strided logical views, and the
-checks that a call wrote its logical extent only.
+edge tests of test_gpu_linalg.py, test_gpu_hensman_abi.py, test_gpu_predict_abi.py): sentinel-filled device
+buffers with strided logical views, the checks that a call wrote its logical extent only, and the inputs the
+two composite modules share (spec pairs, subject-layout covariates, hyper-parameter draws, the perturbation of
+their tolerance yardstick).
 
 Sentinel rule: a buffer passed with padding (ld > columns, padded batch strides) is allocated whole,
 filled with NaN (floats) or 0x7f bytes (integers); after the call every element outside the logical
@@ -89,3 +91,93 @@ def workspace(nbytes, tail=256):
 
 def tail_untouched(tail):
     return bool((tail == 0x7F).all())
+
+
+# ------------------------------------------------------------------------------------------------------
+# shared inputs of the composite edge tests (test_gpu_hensman_abi.py, test_gpu_predict_abi.py)
+# ------------------------------------------------------------------------------------------------------
+# Covariates (Q = 8) in the subject layout [P, T, Q]: column 0 time (half-integer steps + a sub-step offset per
+# subject), 1 and 6 reals in [-2, 2], 2 the subject id (0..P-1, the id covariate), 3 a category in 0..2 and 4 a
+# category in 0..3 (both per subject), 5 a 0/1 flag per subject, 7 a 0/1 flag per row.  `bin` factors sit on
+# columns 5 and 7 only (0/1-valued: 1[a + b == 2] = a b there, positive semi-definite).
+QC = 8
+ID_COL = 2
+_REF_CFG = dict(cat_kernel=[2], bin_kernel=[], sqexp_kernel=[0],
+                cat_int_kernel=[{'cont_covariate': 0, 'cat_covariate': 2}, {'cont_covariate': 0, 'cat_covariate': 3},
+                                {'cont_covariate': 1, 'cat_covariate': 4}],
+                bin_int_kernel=[], covariate_missing_val=[])   # CFG of test_gpu_regime_a.py
+
+
+def spec_pairs():
+    """{name: (spec0, spec1)}: the reference split (both in template bucket (8, 2)); mix1 = bucket (8, 2) with a
+    (16, 4) id kernel (3 factors in a component); mix2 = a (16, 4) kernel (9 components) with a (8, 2) id kernel.
+    gram_multi_f64 / gram_bwd_multi_f64 run both specs of a pair in the larger bucket."""
+    from oracle import lvae_oracle as O
+    ref = O.spec_split(**_REF_CFG, id_covariate=ID_COL)
+    mix1 = ([[("rbf", 0)], [("rbf", 6)], [("cat", 3), ("rbf", 0)], [("bin", 5), ("rbf", 1)], [("cat", 4)]],
+            [[("cat", 2)], [("cat", 2), ("rbf", 0)], [("cat", 2), ("rbf", 0), ("bin", 7)], [("cat", 2), ("rbf", 6)]])
+    mix2 = ([[("rbf", 0)], [("rbf", 1)], [("rbf", 6)], [("cat", 3)], [("cat", 4)], [("cat", 3), ("rbf", 0)],
+             [("cat", 4), ("rbf", 1)], [("bin", 5), ("rbf", 0)], [("bin", 7), ("rbf", 6)]],
+            [[("cat", 2)], [("cat", 2), ("rbf", 0)], [("cat", 2), ("rbf", 1)]])
+    return {"ref": ref, "mix1": mix1, "mix2": mix2}
+
+
+def bucket(spec):
+    """(components, most factors in a component) -> the template bucket the library picks: (8, 2) or (16, 4)"""
+    return (8, 2) if len(spec) <= 8 and max(len(c) for c in spec) <= 2 else (16, 4)
+
+
+def subject_covariates(rng, P, T, ids=None):
+    """[P, T, QC] fp64 covariates of P subjects x T rows (ids: the subject ids, default 0..P-1)"""
+    X = np.empty((P, T, QC))
+    X[..., 0] = 0.5 * np.arange(T)[None, :] + rng.uniform(0.0, 0.5, (P, 1))
+    X[..., 1] = rng.uniform(-2.0, 2.0, (P, T))
+    X[..., 2] = (np.arange(P) if ids is None else np.asarray(ids))[:, None]
+    X[..., 3] = rng.integers(0, 3, (P, 1))
+    X[..., 4] = rng.integers(0, 4, (P, 1))
+    X[..., 5] = rng.integers(0, 2, (P, 1))
+    X[..., 6] = rng.uniform(-2.0, 2.0, (P, T))
+    X[..., 7] = rng.integers(0, 2, (P, T))
+    return torch.tensor(X)
+
+
+def inducing_points(rng, L, M, T):
+    """[L, M, QC]: M distinct points per latent dim over the covariates' range (an id no subject has)"""
+    Z = subject_covariates(rng, L * M, 1, ids=np.full(L * M, -1.0)).reshape(L, M, QC)
+    Z[..., 0] = torch.tensor(rng.uniform(0.0, 0.5 * T, (L, M)))
+    return Z
+
+
+def draw_hypers(rng, L, n):
+    """[L, n] hyper-parameters (or noise with n = None -> [L]) per latent dim, uniform in [0.5, 2]"""
+    return torch.tensor(rng.uniform(0.5, 2.0, (L,) if n is None else (L, n)))
+
+
+def perturbed(t, gen):
+    """t (1 + 2^-50 s), s = +-1 at random: the input perturbation of the tolerance yardstick"""
+    s = torch.randint(0, 2, t.shape, generator=gen, dtype=torch.int64).to(t.dtype) * 2.0 - 1.0
+    return t * (1.0 + 2.0 ** -50 * s)
+
+
+def bit_equal(a, b):
+    return a.shape == b.shape and bool((bits(a.contiguous()) == bits(b.contiguous())).all())
+
+
+def info_problem():
+    """L = 3, M = T = 3, P_b = 2, the reference split; covariates 10 apart in columns 0 and 1 (the Grams are
+    diagonally dominant); every hyper-parameter 2 in dims 0 and 2, 0.5 in dim 1: K0zz[l] ~ 6 I, 1.5 I, 6 I and
+    k1(x_p, x_p) has the diagonal 4, 1, 4."""
+    from oracle import lvae_oracle as O
+    s0, s1 = spec_pairs()["ref"]
+    L, M, T, P_b = 3, 3, 3, 2
+    rng = np.random.default_rng(5)
+    x = subject_covariates(rng, P_b, T)
+    x[..., 0] = 10.0 * torch.arange(T)[None, :]
+    x[..., 1] = 10.0 * torch.arange(T)[None, :]
+    z = inducing_points(rng, L, M, T)
+    z[..., 0] = 10.0 * torch.arange(M)[None, :] + 5.0
+    z[..., 1] = 10.0 * torch.arange(M)[None, :] + 5.0
+    scale = torch.tensor([2.0, 0.5, 2.0], dtype=torch.float64)
+    return dict(s0=s0, s1=s1, L=L, M=M, T=T, P_b=P_b, x=x.reshape(P_b * T, QC), z=z,
+                p0=scale[:, None].expand(L, O.n_params(s0)).contiguous(),
+                p1=scale[:, None].expand(L, O.n_params(s1)).contiguous())
