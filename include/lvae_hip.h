@@ -111,8 +111,30 @@ int lvae_gram_bwd_f64(const lvae_kernel_spec* spec, lvae_xview x1, lvae_xview x2
 /* to Np = lvae_kl_closed_padded_n(n) (identity on the padding).                              */
 /* ---------------------------------------------------------------------------------------- */
 int lvae_kl_closed_padded_n(int n);
-/* bytes of device workspace the fwd+bwd pair needs (kept between the two calls) */
+/* bytes of device workspace the fwd+bwd pair needs (kept between the two calls); 0 for n <= 0, n > 16384
+ * (the blocked inverse handles 64 blocks of 256) or L <= 0.
+ * Env LVAE_KL_EARLY=1 (opt-in early reduce) adds that route's buffers.  The variable is read here and again by
+ * the factor (lvae_kl_closed_factor_f32 / _fwd_f32) on that workspace: it must hold the same value at both calls.
+ * The factor's decision is kept per workspace pointer for the reduce and the backward on it, so what any other
+ * caller sizes or factors in between does not matter; a workspace no factor has run on takes the default route. */
 size_t lvae_kl_closed_workspace_size(int n, int L);
+
+/* Return codes of lvae_kl_closed_*: 0, LVAE_ERR_LAUNCH, or -(1-based index of the offending argument in the entry
+ * point's own list), checked in that order before anything is launched or written:
+ *   spec NULL or its n_comp / n_fac / dim out of range; x NULL; ldx < 1 + the largest covariate the spec reads; n <= 0 or n > 16384; L <= 0; params NULL;
+ *   noise NULL; mu NULL; logv NULL; ld_mu < L; kl NULL; info NULL (info is required); gkl / dmu / dlogv / dparams /
+ *   dnoise NULL; workspace NULL or not 256-B aligned.
+ *   _factor_f32: -1 -2 -3 -4 -5 -6 -7 (noise) -8 (info) -9 (workspace)
+ *   _reduce_f32: -1 .. -7, -8 (mu) -9 (logv) -10 (ld_mu) -11 (kl) -12 (workspace)
+ *   _fwd_f32:    -1 .. -7, -8 (mu) -9 (logv) -10 (ld_mu) -11 (kl) -12 (info) -13 (workspace)
+ *   _bwd_f32:    -1 .. -6, -8 (logv) -9 (ld_mu) -10 (gkl) -11 (dmu) -12 (dlogv) -13 (dparams) -14 (dnoise)
+ *                -15 (workspace); mu is not read and may be NULL.  Both halves' arguments are checked before
+ *                either half runs.
+ *   _bwd_latent_f32 / _bwd_hyper_f32: the codes of the same arguments in _bwd_f32's list.
+ *   _refine_state: -1 (n) -2 (L) -3 (workspace) -4 (est) -5 (flag);  _hyper_state: -1 -2 -3 (NULL) -4 (on);
+ *   _resid_state: -1 (n) -2 (L) -3 (workspace) -4 (covflag) -5 (binned).
+ * A spec outside the supported kernel family is rejected by the Gram fill (-1) before any other work.
+ * A matrix that is not positive definite is not an error of the call: info[l] > 0 (first bad column + 1).     */
 
 /* kl[l] = 1/2 (tr(K^-1 V) + mu^T K^-1 mu - n + log|K| - sum log v),  K = Gram_l(x, x) + noise_l I.
  * x: [n, ldx] fp64 covariates; mu, logv: element (i, l) at mu[i*ld_mu + l] (fp64);
@@ -173,16 +195,28 @@ int lvae_kl_closed_refine_state(int n, int L, const void* workspace, double* est
  * factor's choice (int32: 1 = binned) to a device buffer, on `stream`.  No reference counterpart (diagnostic). */
 int lvae_kl_closed_hyper_state(int n, int L, const void* workspace, int32_t* on, void* stream);
 
+/* The fp64 residual mu - K alpha0 behind the K^-1 mu refinement likewise takes one of two routes: binned O(N W)
+ * (kl_resid_bins.hip: integer-coded covariates, a time window of at most 64 values) or tiled O(N^2).  This copies,
+ * on `stream`, the last factor's covariate flag (int32; 0: some covariate is not an integer below 2^22, the Gram
+ * kernels read fp64 covariates; 1: integer-coded, fp32 covariates; 2: integer-coded and every distance covariate
+ * spans fewer than 64 values, the table kernels) and whether the binned residual runs (int32, 1 = binned; 0 also
+ * when the host's gate is off: env LVAE_RESID_BINS=0 or a kernel outside the binned family).  No reference
+ * counterpart (diagnostic). */
+int lvae_kl_closed_resid_state(int n, int L, const void* workspace, int32_t* covflag, int32_t* binned,
+                               void* stream);
+
 /* A^-1 and log|A| of L padded SPD matrices by a blocked Cholesky factorisation, triangular inverse
  * and product (LAPACK potrf + trtri + lauum, 256-wide blocks; the inverse lvae_kl_closed_* use):
  * potrf's pivot blocks factored and inverted in LDS (fp32 MFMA), its panel / rank-256 trailing
  * updates and trtri / lauum's whole-block GEMMs on the f16 cores with the 3-product split; the next
- * pivot runs on a side stream beside each trailing update.  np % 256 == 0; A [L, np, np] (lower
+ * pivot runs on a side stream beside each trailing update.  np % 256 == 0, np <= 16384; A [L, np, np] (lower
  * 256-block tiles read, overwritten); Ainv [L, np, np] full symmetric out; logdet [L]; info [L]
  * LAPACK-style (first bad column + 1); scratch: lvae_spd_inv_chol_scratch_size(np, L) bytes, 256-B
  * aligned.  Backward-stable in the Cholesky sense: |I - A Ainv| ~ cond(A) 2^-24 (the rounds 1-2 block
  * Gauss-Jordan sweep, ~100x less accurate at cond 1e5, is retired: csrc/retired/spd_sweep.hip, not built).
- * Replaces torch.cholesky + cholesky_solve(I) + the log-det (elbo_functions.py:26-29).         */
+ * Replaces torch.cholesky + cholesky_solve(I) + the log-det (elbo_functions.py:26-29).
+ * Returns 0, LVAE_ERR_LAUNCH, or before any launch: -3 (A NULL) -4 (scratch NULL or misaligned) -5 (Ainv NULL)
+ * -6 (logdet NULL) -7 (info NULL) -1 (np <= 0, np % 256 != 0 or np > 16384) -2 (L <= 0), checked in that order. */
 size_t lvae_spd_inv_chol_scratch_size(int np_, int L);
 int lvae_spd_inv_chol_f32(int np_, int L, float* A, void* scratch, float* Ainv, double* logdet, int32_t* info,
                           void* stream);

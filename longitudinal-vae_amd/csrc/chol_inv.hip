@@ -1758,7 +1758,8 @@ __global__ __launch_bounds__(512) void ci_pair_kernel(CiGemmArgs g1, CiGemmArgs 
 //       side:  pivot(0);  [wait ev_u2(m-1) (ev_c = prep0 for m = 0);  pivot(m+1);  record ev_piv(m+1)]...
 //       main:  prep0;  record ev_c;  [wait ev_piv(m);  panel(m);  U1(m) (without the pivot block) + U2(m), one launch;
 //              record ev_u2(m)]...
-// (b) many latent dims (the headline L = 16): the chain runs whole on the side stream beside U2:
+// (b) many latent dims (L > kCiFuseMaxL; the headline L = 16 is still (a)): the chain runs whole on the side stream
+//     beside U2:
 //       side:  prep0;  pivot(0);  panel(0);  record ev_prep
 //       main:  [wait ev_prep;  U1(k) (with the pivot block);  record ev_c;  U2(k)]...
 //       side:  [wait ev_c;  pivot(k+1);  panel(k+1);  record ev_prep]...
@@ -1816,8 +1817,8 @@ int ci_factor_f32(int np_, int L, float* A, void* scratch, _Float16* YT, float* 
     // 5.70 vs 5.59 ms, L = 8 3.60 vs 3.53, L = 4 2.85 vs 2.87; profiles/r4_lookahead_ab.txt): the second
     // launch's tail and the extra launch outweigh the earlier pivot start.  Off by default.
     static const bool la = getenv("LVAE_CI_LOOKAHEAD") && atoi(getenv("LVAE_CI_LOOKAHEAD")) != 0;
-    // LVAE_CI_U128=0: the trailing update as whole 256-tiles fused with column m+1's (ci_update_kernel<kCiU12>)
-    // instead of the 128 x 128 sub-tile kernel (ci_update128_kernel)
+    // LVAE_CI_U128=1 (opt-in): the trailing update by the 128 x 128 sub-tile kernel (ci_update128_kernel) instead of
+    // whole 256-tiles fused with column m+1's (ci_update_kernel<kCiU12>, the default)
     const bool u128 = getenv("LVAE_CI_U128") && atoi(getenv("LVAE_CI_U128")) != 0;
     // LVAE_CI_URING=1: the fused update on the 16-deep ring (ci_update_ring_kernel) instead of the double-buffered
     // 32-deep stages (ci_update_kernel).  Both opt-in forms measured slower (r6, profiles/r6_update_ab.txt): the ring
@@ -2051,7 +2052,8 @@ int lvae_spd_inv_chol_f32(int np_, int L, float* A, void* scratch, float* Ainv, 
   if (!Ainv) return -5;
   if (!logdet) return -6;
   if (!info) return -7;
-  if (np_ <= 0 || np_ % lvae::kSwB) return -1;
+  if (np_ <= 0 || np_ % lvae::kSwB || np_ / lvae::kSwB > 64) return -1;
+  if (L <= 0) return -2;
   char* yt = (char*)scratch + lvae::ci_scratch_bytes(np_, L);
   return lvae::ci_inverse_f32(np_, L, A, scratch, (_Float16*)yt, Ainv, logdet, info, (hipStream_t)stream);
 }

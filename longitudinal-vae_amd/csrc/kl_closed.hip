@@ -35,7 +35,7 @@
 #include "prof.hpp"
 #include "x3_c16.hpp"  // c16_off: the chunk-major Y / Y^T planes
 
-#include <atomic>
+#include <unordered_set>
 
 
 #ifndef LVAE_ALPHA_WG
@@ -72,6 +72,7 @@ size_t kl_resid_bins_bytes(int np_, int L, int ncomp);
 bool kl_resid_bins_enabled(const lvae_kernel_spec* spec, int n);
 int kl_resid_bins_plan(const lvae_kernel_spec* spec, const double* x, int ldx, int n, int np_, int L, void* wsbuf,
                        hipStream_t st);
+int* kl_resid_bins_okflag(void* wsbuf);
 size_t kl_refine_bytes(int np_, int L);
 int kl_refine_gate(const lvae_kernel_spec* spec, const double* x, int ldx, int n, int np_, int L, const double* params,
                    const double* noise, const double* kdiag, double* est, int* flag, hipStream_t st);
@@ -391,7 +392,47 @@ static bool kl_early_env() {
   const char* e = getenv("LVAE_KL_EARLY");
   return e && atoi(e) != 0;
 }
-static std::atomic<bool> g_kl_early_sized{false};  // LVAE_KL_EARLY at the last workspace-size query
+
+// The workspaces whose last factor chose the early reduce (kl_early below), under side_mutex().  The choice is the
+// factor's, from LVAE_KL_EARLY at that call, and the reduce, the backward halves and nothing else follow it by
+// workspace pointer: what another caller sizes or factors in between does not matter.  A workspace without a
+// record gets the late route (which needs no buffer past bytes_base).
+static std::unordered_set<const void*>& kl_early_set() {
+  static std::unordered_set<const void*> s;
+  return s;
+}
+static void kl_early_record(const void* workspace, bool early) {
+  std::lock_guard<std::recursive_mutex> lock(side_mutex());
+  if (early) kl_early_set().insert(workspace);
+  else kl_early_set().erase(workspace);
+}
+static bool kl_early(const void* workspace) {
+  std::lock_guard<std::recursive_mutex> lock(side_mutex());
+  return kl_early_set().count(workspace) != 0;
+}
+
+// Argument checks of the family, before any launch: -(index of the argument in the entry point's own list; the
+// backward halves use lvae_kl_closed_bwd_f32's list).  n is bounded by the blocked inverse's 64 blocks of 256.
+constexpr int kKlMaxN = 64 * 256;
+static int kl_check_problem(const lvae_kernel_spec* spec, const double* x, int ldx, int n, int L,
+                            const double* params) {
+  if (!spec || spec->n_comp < 1 || spec->n_comp > LVAE_MAX_COMP) return -1;
+  int qmin = 1;  // 1 + the largest covariate the spec reads
+  for (int r = 0; r < spec->n_comp; ++r) {
+    if (spec->n_fac[r] < 0 || spec->n_fac[r] > LVAE_MAX_FAC) return -1;
+    for (int f = 0; f < spec->n_fac[r]; ++f) {
+      if (spec->dim[r][f] < 0) return -1;
+      qmin = spec->dim[r][f] + 1 > qmin ? spec->dim[r][f] + 1 : qmin;
+    }
+  }
+  if (!x) return -2;
+  if (ldx < qmin) return -3;
+  if (n <= 0 || n > kKlMaxN) return -4;
+  if (L <= 0) return -5;
+  if (!params) return -6;
+  return 0;
+}
+static bool kl_bad_ws(const void* workspace) { return !workspace || ((uintptr_t)workspace & 255); }
 
 // (kl_hyper.hip's state query: where the workspace keeps the binned hyper-gradient's region)
 size_t kl_hyper_offset_in_kl_ws(int np_, int L) {
@@ -402,27 +443,26 @@ size_t kl_hyper_offset_in_kl_ws(int np_, int L) {
 
 size_t lvae_kl_closed_workspace_size(int n, int L) {
   const int np_ = lvae_kl_closed_padded_n(n);
+  if (n <= 0 || n > kKlMaxN || L <= 0) return 0;
   const KLWorkspace ws(nullptr, np_, L);
   // the early reduce's buffers (the workspace's tail, ~0.3-0.6 GB) only when LVAE_KL_EARLY is on at this call; the
-  // decision is kept for the calls on the workspace sized here (kl_early)
-  const bool early = kl_early_env();
-  g_kl_early_sized.store(early);
-  return early ? ws.bytes : ws.bytes_base;
+  // factor on the workspace sized here reads the variable again and must find the same value (kl_early)
+  return kl_early_env() ? ws.bytes : ws.bytes_base;
 }
 
 int lvae_kl_closed_factor_f32(const lvae_kernel_spec* spec, const double* x, int ldx, int n, int L,
                               const double* params, const double* noise, int32_t* info, void* workspace,
                               void* stream) {
-  if (!spec) return -1;
-  if (!x) return -2;
-  if (n <= 0) return -4;
-  if (L <= 0) return -5;
-  if (!params) return -6;
+  LVAE_TRY(kl_check_problem(spec, x, ldx, n, L, params));
   if (!noise) return -7;
-  if (!workspace || ((uintptr_t)workspace & 255)) return -9;
+  if (!info) return -8;
+  if (kl_bad_ws(workspace)) return -9;
   hipStream_t st = (hipStream_t)stream;
   const int np_ = lvae_kl_closed_padded_n(n);
   KLWorkspace ws((char*)workspace, np_, L);
+  // the early reduce: this call's LVAE_KL_EARLY, non-pipelined factors only; recorded for the calls that follow on
+  // this workspace
+  kl_early_record(workspace, kl_early_env() && ci_pipe_mode_of(np_, L) == 0);
   // the binned residual's plan (x only) goes on the side stream behind the Cholesky's pivot chain, beside
   // the trailing updates / trtri; the reduce waits for it (event rb)
   const bool rb_on = kl_resid_bins_enabled(spec, n);
@@ -442,7 +482,10 @@ int lvae_kl_closed_factor_f32(const lvae_kernel_spec* spec, const double* x, int
   // the binned hyper-gradient's plan (covariates and the fill's covariate flag; the reduce's lauum and the
   // backward read its flag): beside trtri on the side stream with the residual's plan when that runs (behind the
   // last pivot, so after the fill), else here
-  if (!rb_on) LVAE_TRY(kl_hyper_plan(spec, x, ldx, n, np_, L, ws.hb, ws.covflag, st));
+  if (!rb_on) {
+    LVAE_TRY(kl_hyper_plan(spec, x, ldx, n, np_, L, ws.hb, ws.covflag, st));
+    LVAE_TRY(zero_async(kl_resid_bins_okflag(ws.rb), sizeof(int), st));  // (lvae_kl_closed_resid_state: not binned)
+  }
   // Y = L^-1 and log|K|: blocked Cholesky + trtri (chol_inv.hip; phases POTRF / POTRI inside); lauum
   // runs in the reduce
   LVAE_TRY(ci_factor_f32(np_, L, ws.A, ws.chol, ws.planes, ws.Kinv, ws.logdet, info, st));
@@ -466,9 +509,9 @@ int lvae_kl_closed_factor_f32(const lvae_kernel_spec* spec, const double* x, int
 // Measured (r6, same box, headline step): d kl / d (mu, log v) 0.7 ms earlier, but the step 9.32-9.37 vs 9.20-9.25
 // ms: the encoder backward then runs beside lauum + the slab pass, whose grids hold every CU, and the four
 // mat-vec passes (~0.45 ms) add to a step that is bound by its total GPU work (profiles/r6_kl_early_ab.txt).
-// The variable is read when the workspace is sized (tests compare both routes in one process) and that decision
-// holds for the forward and the backward on it: the early buffers exist only in a workspace sized with it on.
-static bool kl_early(int np_, int L) { return g_kl_early_sized.load() && ci_pipe_mode_of(np_, L) == 0; }
+// The variable is read when the workspace is sized and again by the factor (tests compare both routes in one
+// process), which records its decision for the reduce and the backward on that workspace (kl_early_record): the
+// early buffers exist only in a workspace sized with it on, so the two reads must agree.
 
 // t = Y x (lower) or a = base + Y^T x (upper, + the row sums of squares of Y^T: diag K^-1 into sumsq)
 static void kl_ymv(const KLWorkspace& ws, const float* ysc, int np_, int L, bool upper, const double* x,
@@ -495,22 +538,20 @@ static void kl_ymv(const KLWorkspace& ws, const float* ysc, int np_, int L, bool
 int lvae_kl_closed_reduce_f32(const lvae_kernel_spec* spec, const double* x, int ldx, int n, int L,
                               const double* params, const double* noise, const double* mu, const double* logv,
                               int ld_mu, double* kl, void* workspace, int need_bwd, void* stream) {
-  if (!spec) return -1;
-  if (!x) return -2;
-  if (n <= 0) return -4;
-  if (L <= 0) return -5;
-  if (!params) return -6;
+  LVAE_TRY(kl_check_problem(spec, x, ldx, n, L, params));
   if (!noise) return -7;
-  if (!mu || !logv || ld_mu < L) return -8;
+  if (!mu) return -8;
+  if (!logv) return -9;
+  if (ld_mu < L) return -10;
   if (!kl) return -11;
-  if (!workspace || ((uintptr_t)workspace & 255)) return -12;
+  if (kl_bad_ws(workspace)) return -12;
   hipStream_t st = (hipStream_t)stream;
   const int np_ = lvae_kl_closed_padded_n(n);
   KLWorkspace ws((char*)workspace, np_, L);
   ProfScope ps(LVAE_PH_KL_REDUCE, st);
   kl_prep_kernel<<<dim3(cdiv(np_, 256), L), 256, 0, st>>>(mu, logv, ld_mu, n, np_, L, ws.mu, ws.v, ws.sv);
   const bool rb_on = kl_resid_bins_enabled(spec, n);  // (the plan: the factor call's, joined on `st`)
-  if (kl_early(np_, L)) {
+  if (kl_early(workspace)) {
     // a0 = Y^T (Y mu) and d = diag K^-1 (the row sums of squares of Y^T); r = mu - K a0 in fp64 from the
     // covariates; a = a0 + Y^T (Y r); the refinement gate on d, and for the flagged dims (if any) their K^-1 alone
     // (the other dims' lauum workgroups exit) and the fp64 diag refinement; the KL.  No K^-1 for unflagged dims.
@@ -555,15 +596,14 @@ int lvae_kl_closed_reduce_f32(const lvae_kernel_spec* spec, const double* x, int
 int lvae_kl_closed_fwd_f32(const lvae_kernel_spec* spec, const double* x, int ldx, int n, int L, const double* params,
                            const double* noise, const double* mu, const double* logv, int ld_mu, double* kl,
                            int32_t* info, void* workspace, int need_bwd, void* stream) {
-  if (!spec) return -1;
-  if (!x) return -2;
-  if (n <= 0) return -4;
-  if (L <= 0) return -5;
-  if (!params) return -6;
+  LVAE_TRY(kl_check_problem(spec, x, ldx, n, L, params));
   if (!noise) return -7;
-  if (!mu || !logv || ld_mu < L) return -8;
+  if (!mu) return -8;
+  if (!logv) return -9;
+  if (ld_mu < L) return -10;
   if (!kl) return -11;
-  if (!workspace || ((uintptr_t)workspace & 255)) return -13;
+  if (!info) return -12;
+  if (kl_bad_ws(workspace)) return -13;
   LVAE_TRY(lvae_kl_closed_factor_f32(spec, x, ldx, n, L, params, noise, info, workspace, stream));
   return lvae_kl_closed_reduce_f32(spec, x, ldx, n, L, params, noise, mu, logv, ld_mu, kl, workspace, need_bwd, stream);
 }
@@ -572,12 +612,15 @@ int lvae_kl_closed_fwd_f32(const lvae_kernel_spec* spec, const double* x, int ld
 int lvae_kl_closed_bwd_hyper_f32(const lvae_kernel_spec* spec, const double* x, int ldx, int n, int L,
                                  const double* params, const double* gkl, double* dparams, double* dnoise,
                                  void* workspace, void* stream) {
-  if (!spec) return -1;
-  if (!workspace || ((uintptr_t)workspace & 255)) return -15;
+  LVAE_TRY(kl_check_problem(spec, x, ldx, n, L, params));
+  if (!gkl) return -10;
+  if (!dparams) return -13;
+  if (!dnoise) return -14;
+  if (kl_bad_ws(workspace)) return -15;
   hipStream_t st = (hipStream_t)stream;
   const int np_ = lvae_kl_closed_padded_n(n);
   KLWorkspace ws((char*)workspace, np_, L);
-  if (kl_early(np_, L)) {
+  if (kl_early(workspace)) {
     // the early reduce left K^-1 to this half: lauum now (+ the B planes for the S GEMM when the binned route is off;
     // the a0 partials it also writes are unused), beside the encoder's backward on the caller's other stream
     ProfScope ps(LVAE_PH_KL_REDUCE, st);
@@ -602,11 +645,14 @@ int lvae_kl_closed_bwd_hyper_f32(const lvae_kernel_spec* spec, const double* x, 
 // d kl / d (mu, logv): elementwise from K^-1 mu and diag K^-1 (the forward's)
 int lvae_kl_closed_bwd_latent_f32(int n, int L, const double* logv, int ld_mu, const double* gkl, double* dmu,
                                   double* dlogv, void* workspace, void* stream) {
-  if (n <= 0) return -4;
+  if (n <= 0 || n > kKlMaxN) return -4;
   if (L <= 0) return -5;
-  if (!logv || ld_mu < L) return -8;
-  if (!gkl || !dmu || !dlogv) return -10;
-  if (!workspace || ((uintptr_t)workspace & 255)) return -15;
+  if (!logv) return -8;
+  if (ld_mu < L) return -9;
+  if (!gkl) return -10;
+  if (!dmu) return -11;
+  if (!dlogv) return -12;
+  if (kl_bad_ws(workspace)) return -15;
   hipStream_t st = (hipStream_t)stream;
   const int np_ = lvae_kl_closed_padded_n(n);
   KLWorkspace ws((char*)workspace, np_, L);
@@ -620,21 +666,47 @@ int lvae_kl_closed_bwd_latent_f32(int n, int L, const double* logv, int ld_mu, c
 int lvae_kl_closed_bwd_f32(const lvae_kernel_spec* spec, const double* x, int ldx, int n, int L, const double* params,
                            const double* mu, const double* logv, int ld_mu, const double* gkl, double* dmu,
                            double* dlogv, double* dparams, double* dnoise, void* workspace, void* stream) {
-  (void)mu;
+  (void)mu;  // (not read: the forward kept its copy in the workspace; may be NULL)
+  // every argument of both halves first, in the order of this list: the latent half never runs before a rejection
+  LVAE_TRY(kl_check_problem(spec, x, ldx, n, L, params));
+  if (!logv) return -8;
+  if (ld_mu < L) return -9;
+  if (!gkl) return -10;
+  if (!dmu) return -11;
+  if (!dlogv) return -12;
+  if (!dparams) return -13;
+  if (!dnoise) return -14;
+  if (kl_bad_ws(workspace)) return -15;
   LVAE_TRY(lvae_kl_closed_bwd_latent_f32(n, L, logv, ld_mu, gkl, dmu, dlogv, workspace, stream));
   return lvae_kl_closed_bwd_hyper_f32(spec, x, ldx, n, L, params, gkl, dparams, dnoise, workspace, stream);
 }
 
 int lvae_kl_closed_refine_state(int n, int L, const void* workspace, double* est, int32_t* flag, void* stream) {
-  if (n <= 0) return -1;
+  if (n <= 0 || n > kKlMaxN) return -1;
   if (L <= 0) return -2;
-  if (!workspace || ((uintptr_t)workspace & 255)) return -3;
-  if (!est || !flag) return -4;
+  if (kl_bad_ws(workspace)) return -3;
+  if (!est) return -4;
+  if (!flag) return -5;
   const int np_ = lvae_kl_closed_padded_n(n);
   KLWorkspace ws((char*)workspace, np_, L);
   hipStream_t st = (hipStream_t)stream;
   if (copy_words_async(est, ws.rest, (size_t)L * sizeof(double), st) != 0 ||
       copy_words_async(flag, ws.rflag, (size_t)L * sizeof(int32_t), st) != 0)
+    return LVAE_ERR_LAUNCH;
+  return 0;
+}
+
+int lvae_kl_closed_resid_state(int n, int L, const void* workspace, int32_t* covflag, int32_t* binned, void* stream) {
+  if (n <= 0 || n > kKlMaxN) return -1;
+  if (L <= 0) return -2;
+  if (kl_bad_ws(workspace)) return -3;
+  if (!covflag) return -4;
+  if (!binned) return -5;
+  const int np_ = lvae_kl_closed_padded_n(n);
+  KLWorkspace ws((char*)workspace, np_, L);
+  hipStream_t st = (hipStream_t)stream;
+  if (copy_words_async(covflag, ws.covflag, sizeof(int32_t), st) != 0 ||
+      copy_words_async(binned, kl_resid_bins_okflag(ws.rb), sizeof(int32_t), st) != 0)
     return LVAE_ERR_LAUNCH;
   return 0;
 }

@@ -26,9 +26,8 @@
 // Conditions (hb_plan_kernel, on the device; otherwise `on` = 0 and the S GEMM + table adjoint run as before):
 // the table path's (covariate flag 2); the Cat gate covariate of the widest range (> 4 values) is "big" (the id),
 // the other Cat gates span <= 16 values; its values non-decreasing over the points (runs contiguous) with runs of
-// <= 64 points; far binnings <= 4, with <= 128 bins in all, <= 4 blocks of 32 bins and sum nbins^2 <= 4096; <= 8
-// parameter slots on near
-// components; Bin gate values within 64 of their minimum, distance values within 65535 of theirs (the row keys);
+// <= 64 points; far binnings <= 4, with <= 128 bins in all, <= 4 blocks of 32 bins and sum nbins^2 <= 4096; <= 4
+// parameter slots on near components (kHbNear); Bin gate values within 64 of their minimum, distance values within 65535 of theirs (the row keys);
 // on the host: the slab kernel's LDS fits (hb_slab_lds).
 #include "blkinv.hpp"
 #include "gram_tab.hpp"

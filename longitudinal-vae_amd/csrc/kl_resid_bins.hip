@@ -65,6 +65,8 @@ struct RbWs {
 };
 
 size_t kl_resid_bins_bytes(int np_, int L, int ncomp) { return RbWs(nullptr, np_, L, ncomp).bytes; }
+// the plan's device flag (its place does not depend on the sizes); the factor zeroes it when the host gate is off
+int* kl_resid_bins_okflag(void* wsbuf) { return RbWs((char*)wsbuf, kRbMaxW, 1, 1).ok; }
 
 // structure the host can check: every component at most one continuous factor, at most kRbMaxGates gates
 bool kl_resid_bins_spec_ok(const lvae_kernel_spec* s, int n) {

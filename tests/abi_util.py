@@ -1,5 +1,5 @@
 """Helpers of the C-ABI edge tests (test_gpu_gram_abi.py, test_gpu_small_abi.py, the solve / factor
-edge tests of test_gpu_linalg.py, test_gpu_hensman_abi.py, test_gpu_predict_abi.py): sentinel-filled device
+edge tests of test_gpu_linalg.py, test_gpu_hensman_abi.py, test_gpu_predict_abi.py, test_gpu_kl_closed_abi.py): sentinel-filled device
 buffers with strided logical views, the checks that a call wrote its logical extent only, and the inputs the
 two composite modules share (spec pairs, subject-layout covariates, hyper-parameter draws, the perturbation of
 their tolerance yardstick).

@@ -197,12 +197,12 @@ def _spd_inverse(hip, kind, n, L, Ad):
 
 @pytest.mark.parametrize("kind", INV_KINDS)
 @pytest.mark.parametrize("n,L", [(256, 3), (512, 2), (768, 2), (1280, 2), (4096, 1), (256, 9), (512, 9), (768, 10),
-                                 (1280, 9)])
+                                 (1280, 9), (512, 17), (768, 17)])
 def test_spd_inverse(hip, kind, n, L):
     """The two blocked SPD inverses vs fp64 torch: A^-1 (both triangles written) and log|A|.
     nt = n / 256 = 1, 2, 3, 5, 16 blocks (3 and 5: trtri's recursive doubling with a ragged last
-    group), under both host schedules (L <= 8: pivots back to back, each updating its own block; L > 8:
-    the whole chain on the side stream); the upper triangle of A is garbage (never read) and A's scale
+    group), under both host schedules (L <= 16, kCiFuseMaxL: pivots back to back, each updating its own block;
+    L > 16, here 17: the whole chain on the side stream); the upper triangle of A is garbage (never read) and A's scale
     is uneven (diagonal 0.5 .. 50)."""
     gen = torch.Generator().manual_seed(n + L)
     Xm = torch.randn(L, n, n, generator=gen, dtype=torch.float64) / n ** 0.5
