@@ -102,6 +102,28 @@ int lvae_gram_bwd_f64(const lvae_kernel_spec* spec, lvae_xview x1, lvae_xview x2
                       int64_t gstride_l, int64_t ldg, double* dparams, double* ddiag, void* workspace,
                       void* stream);
 
+/* Fused cross-Gram x vector in fp64, the [L, n1, n2] Gram never written:
+ *   out[i, l] = sum_{j < n2} k_l(x1_i, x2_j) v[j, l] + (diag ? diag[l] v[i, l] : 0)      i < n1, l < L
+ * x1 [n1, ld1] and x2 [n2, ld2] are the covariates of every latent dim; params [L, n_params]; v element (j, l)
+ * at v[j*ld_v + l], out element (i, l) at out[i*ld_out + l] (nothing else of out is written).  diag [L] is
+ * allowed only when n1 == n2.  The kernel family is lvae_gram_f64's: every factor kind, both template buckets,
+ * factor dims below 32.  n1, n2 are arbitrary (edge tiles are masked).
+ * One workgroup per 64 rows of x1 sweeps 64-column tiles of x2; when there are few row tiles the columns are cut
+ * into S slabs (S a function of (n1, n2, L) alone), the partials [L, S, n1] go to the workspace and are summed in
+ * slab order: no atomics, the same bits on every run.  workspace: lvae_gram_matvec_workspace_size(n1, n2, L)
+ * bytes (0 when S == 1; then it may be NULL), 256-B aligned.
+ * Returns 0, LVAE_ERR_LAUNCH, or before any launch, checked in this order:
+ *   -1 (spec NULL, outside every template bucket, or a factor dim outside 0 .. 31)
+ *   -4 (n1 < 0) -7 (n2 < 0) -8 (L < 1); then n1 == 0 returns 0 and writes nothing;
+ *   -2 (x1 NULL) -3 (ld1 < 1 + the largest column the spec reads) -5 (x2 NULL) -6 (ld2, as ld1) -9 (params NULL)
+ *   -10 (diag given and n1 != n2) -11 (v NULL) -12 (ld_v < L) -13 (out NULL) -14 (ld_out < L)
+ *   -15 (workspace NULL or misaligned when S > 1).  x2, ld2, v and ld_v are not checked when n2 == 0: the call then
+ *   writes zeros to out [n1, L] and returns 0.                                                           */
+size_t lvae_gram_matvec_workspace_size(int n1, int n2, int L);
+int lvae_gram_matvec_f64(const lvae_kernel_spec* spec, const double* x1, int64_t ld1, int n1, const double* x2,
+                         int64_t ld2, int n2, int L, const double* params, const double* diag, const double* v,
+                         int64_t ld_v, double* out, int64_t ld_out, void* workspace, void* stream);
+
 /* ---------------------------------------------------------------------------------------- */
 /* Regime B: exact KL over the full N x N covariance (elbo_functions.py:8-34), batched over L */
 /* latent dims.  Arithmetic: fp32 storage; every GEMM on the f16 matrix cores with the       */
@@ -439,6 +461,29 @@ int lvae_predict_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec
                      const double* mu, const double* z, int Nt, const double* test_x,
                      const double* params0, const double* params1, const double* noise, double eps,
                      double* out, int32_t* info, void* workspace, void* stream);
+
+/* Exact-GP posterior mean of the latents at test covariates (model_test.py:11-17 predict_gp as MSE_test calls it,
+ * model_test.py:19-82), all in fp64:
+ *   out[t, l] = k_l(tx_t, x) (k_l(x, x) + noise_l I)^-1 mu[:, l]         t < nt, l < L
+ * x [n, ldx] the prediction set's covariates, mu element (i, l) at mu[i*ld_mu + l], tx [nt, ldt], out element
+ * (t, l) at out[t*ld_out + l].  Kernel launches only, enqueued on the caller's stream, nothing allocated
+ * (capture into a HIP graph is not covered by a test):
+ * lvae_gram_f64 with diag = noise into the workspace, lvae_potrf_f64 in place (info[l] LAPACK-style: a dim that
+ * is not positive definite leaves info[l] > 0, its outputs are then meaningless and every other dim's are
+ * unaffected), lvae_potrs_f64 for a0 = K^-1 mu, one refinement step a = a0 + K^-1 (mu - K a0) with K a0 from
+ * lvae_gram_matvec_f64's kernel (K is gone after the in-place factor), and that kernel again for k(tx, x) a.
+ * The reference forms the explicit inverse instead (torch.cholesky_solve(eye, L)).  nt == 0: the factor runs
+ * (info is written), out is untouched.  workspace: lvae_predict_exact_workspace_size(n, nt, L) bytes (about
+ * 8 L n^2; 0 for n < 1, nt < 0 or L < 1), 256-B aligned.
+ * Returns 0, LVAE_ERR_LAUNCH, or before any launch, checked in this order: -1 (spec NULL or outside the family of
+ * lvae_gram_matvec_f64) -2 (x NULL) -3 (ldx < 1 + the largest column the spec reads) -4 (n < 1) -5 (L < 1)
+ * -6 (params NULL) -7 (noise NULL) -8 (mu NULL) -9 (ld_mu < L) -12 (nt < 0); with nt > 0: -10 (tx NULL)
+ * -11 (ldt, as ldx) -13 (out NULL) -14 (ld_out < L); -15 (info NULL) -16 (workspace NULL or misaligned).   */
+size_t lvae_predict_exact_workspace_size(int n, int nt, int L);
+int lvae_predict_exact_f64(const lvae_kernel_spec* spec, const double* x, int64_t ldx, int n, int L,
+                           const double* params, const double* noise, const double* mu, int64_t ld_mu,
+                           const double* tx, int64_t ldt, int nt, double* out, int64_t ld_out, int32_t* info,
+                           void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------- */
 /* Phase timing (profiling aid; the only process-wide state of the library).  When enabled, */

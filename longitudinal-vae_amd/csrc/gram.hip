@@ -1302,6 +1302,7 @@ __device__ inline double factor64_at(int kind, double ad, const double* __restri
   return exp_nonpos64(-2.0 / (pf[0] * pf[0]) * sn * sn, tab);
 }
 
+template <int NTAB = kIntTab>
 __device__ inline void apply_factor64(int kind, int d, const double* __restrict__ pf, const double* __restrict__ sx1,
                                       const double* __restrict__ sx2, int tr, int tc, int hf, double (&v)[2][4],
                                       const double* __restrict__ tab, const double* __restrict__ itab) {
@@ -1326,7 +1327,7 @@ __device__ inline void apply_factor64(int kind, int d, const double* __restrict_
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         const double ad = fabs(xr[a] - xc[c]);
-        const bool hit = ad < (double)kIntTab && ad == floor(ad);
+        const bool hit = ad < (double)NTAB && ad == floor(ad);
         v[a][c] *= hit ? itab[hit ? (int)ad : 0] : factor64_at(kind, ad, pf, tab);
       }
   } else {  // LVAE_LIN
@@ -1334,6 +1335,69 @@ __device__ inline void apply_factor64(int kind, int d, const double* __restrict_
     for (int a = 0; a < 2; ++a)
 #pragma unroll
       for (int c = 0; c < 4; ++c) v[a][c] *= xr[a] * xc[c];
+  }
+}
+
+// The two helpers below are gram_matvec_tiles' (further down).  kl_resid_tiles keeps its own text of the same two
+// loops: calling either helper from it changed its register allocation (142 VGPRs and 48 B / lane of scratch against
+// 150 and none), and it is on the training path.
+// integer-distance tables of a workgroup: itab[(r MF + f) NTAB + m] = the RBF / periodic factor (r, f) at distance m
+// (0 for the other kinds); sp = the dim's parameters in LDS.  The caller's next barrier publishes them.
+template <int MC, int MF, int NTAB>
+__device__ __attribute__((always_inline)) inline void build_itab64(const DevSpec& s, const double* __restrict__ sp,
+                                                                   const double* __restrict__ tab,
+                                                                   double* __restrict__ itab) {
+  for (int e = threadIdx.x; e < MC * MF * NTAB; e += 256) {
+    const int r = e / (MF * NTAB), f = (e / NTAB) % MF, m = e % NTAB;
+    double val = 0.0;
+    if (r < s.n_comp && f < s.n_fac[r] && (s.kind[r][f] == LVAE_RBF || s.kind[r][f] == LVAE_PER))
+      val = factor64_at(s.kind[r][f], (double)m, sp + s.param_idx[r][f], tab);
+    itab[e] = val;
+  }
+}
+
+// k[a][c] += the additive kernel on half hf of the thread's 4 x 4 micro-tile (rows 4 tr + 2 hf + a, columns
+// 4 tc + c of the staged tiles): per component the gates first (cheap, exact), then the transcendental factors
+// unless the gates zeroed the whole wave
+template <int MC, int MF, int NTAB>
+__device__ __attribute__((always_inline)) inline void kernel_half64(const DevSpec& s, const double* __restrict__ sp,
+                                                                    const double* __restrict__ sx1,
+                                                                    const double* __restrict__ sx2, int tr, int tc,
+                                                                    int hf, const double* __restrict__ tab,
+                                                                    const double* __restrict__ itab,
+                                                                    double (&k)[2][4]) {
+#pragma unroll 1
+  for (int r = 0; r < s.n_comp; ++r) {
+    double v[2][4];
+    const double sc = sp[s.scale_idx[r]];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) v[a][c] = sc;
+#pragma unroll 1
+    for (int f = 0; f < s.n_fac[r]; ++f) {
+      const int kind = s.kind[r][f];
+      if (kind != LVAE_CAT && kind != LVAE_BIN) continue;
+      apply_factor64<NTAB>(kind, s.dim[r][f], sp, sx1, sx2, tr, tc, hf, v, tab, itab);
+    }
+    bool any = false;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) any |= v[a][c] != 0.0;
+    if (!__any(any)) continue;
+#pragma unroll 1
+    for (int f = 0; f < s.n_fac[r]; ++f) {
+      const int kind = s.kind[r][f];
+      if (kind == LVAE_CAT || kind == LVAE_BIN) continue;
+      const int pi = s.param_idx[r][f];
+      apply_factor64<NTAB>(kind, s.dim[r][f], sp + (pi < 0 ? 0 : pi), sx1, sx2, tr, tc, hf, v, tab,
+                           itab + (r * MF + f) * NTAB);
+    }
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) k[a][c] += v[a][c];
   }
 }
 
@@ -1467,6 +1531,103 @@ __global__ __launch_bounds__(256) void kl_resid_reduce(const double* __restrict_
   double acc = 0.0;
   for (int s = 0; s < nt; ++s) acc += part[((int64_t)l * nt + s) * np_ + i];
   res[(int64_t)l * np_ + i] = i < n ? muc[(int64_t)l * np_ + i] - acc : 0.0;
+}
+
+// Fused rectangular cross-Gram x vector in fp64 (the exact-GP predictor, predict.hip: k(X*, X) alpha and the
+// refinement residual K alpha0): out[i][l] = sum_j k_l(x1_i, x2_j) v[j][l] (+ diag[l] v[i][l]), the [L, n1, n2]
+// Gram never written.  kl_resid_tiles' arithmetic (kernel_half64: apply_factor64, exp_nonpos64, the integer-distance
+// tables, the gates before the exp / sin factors) on its 4 x 4 micro-tile in two halves; one workgroup owns the 64-row tile I
+// of x1 (staged once) and sweeps the 64-column tiles of its slab of x2, the row sums in registers, covariates and
+// v staged in LDS per tile; each output is written once (no atomics: the same bits every run).  Grid
+// (row tiles x S, L): slab sl covers column tiles [sl tps, (sl + 1) tps); S == 1 writes out, S > 1 writes
+// part[l][sl][i], summed in slab order by gram_matvec_sum.  Rows >= n1 and columns >= n2 of the edge tiles are
+// masked.  The spec's dims arrive remapped to the staged slots 0 .. qc.nq - 1 (source columns qc.col[]); QMAX slots
+// fit in LDS, with integer-distance tables of NTAB entries (a distance beyond the table is evaluated directly: the
+// same function of the same argument, so the table's length does not change a bit of the result).
+struct MvCols {
+  int32_t nq;
+  int32_t col[kMaxQ];
+};
+
+template <int MC, int MF, int QMAX, int NTAB>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void gram_matvec_tiles(
+    DevSpec s, MvCols qc, const double* __restrict__ x1, int64_t ld1, int n1, const double* __restrict__ x2,
+    int64_t ld2, int n2, const double* __restrict__ params, const double* __restrict__ diag,
+    const double* __restrict__ v, int64_t v_rs, int64_t v_ls, double* __restrict__ out, int64_t o_rs, int64_t o_ls,
+    double* __restrict__ part, int S, int tps) {
+  __shared__ double sx1[kGT * QMAX];
+  __shared__ double sx2[kGT * QMAX];
+  __shared__ double sp[64];
+  __shared__ double sv[kGT];
+  __shared__ double tab[64];
+  __shared__ double itab[MC * MF * NTAB];  // integer-distance tables (distances < NTAB), slot r * MF + f
+  const int l = blockIdx.y, I = blockIdx.x / S, sl = blockIdx.x % S, tid = threadIdx.x, tr = tid >> 4, tc = tid & 15;
+  if (tid < 64) tab[tid] = exp2((double)tid / 64.0);
+  if (tid < s.n_params) sp[tid] = params[(int64_t)l * s.n_params + tid];
+  __syncthreads();
+  build_itab64<MC, MF, NTAB>(s, sp, tab, itab);
+  const int i0 = I * kGT, ntc = (n2 + kGT - 1) / kGT;
+  const int J0 = sl * tps, J1 = min(J0 + tps, ntc);
+  for (int e = tid; e < kGT * qc.nq; e += 256) {
+    const int r = e / qc.nq, q = e % qc.nq;
+    sx1[q * kGT + cov_slot(r)] = (i0 + r < n1) ? x1[(int64_t)(i0 + r) * ld1 + qc.col[q]] : 0.0;
+  }
+  const double dg = diag ? diag[l] : 0.0;
+  const double* vl = v + (int64_t)l * v_ls;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};  // this thread's 4 columns' share of rows 4 tr + (0 .. 3)
+  for (int J = J0; J < J1; ++J) {
+    const int j0 = J * kGT;
+    __syncthreads();  // the previous tile's LDS readers are done (first pass: sx1, sp, itab are written)
+    for (int e = tid; e < kGT * qc.nq; e += 256) {
+      const int r = e / qc.nq, q = e % qc.nq;
+      sx2[q * kGT + cov_slot(r)] = (j0 + r < n2) ? x2[(int64_t)(j0 + r) * ld2 + qc.col[q]] : 0.0;
+    }
+    if (tid < kGT) sv[tid] = (j0 + tid < n2) ? vl[(int64_t)(j0 + tid) * v_rs] : 0.0;
+    __syncthreads();
+#pragma unroll 1
+    for (int hf = 0; hf < 2; ++hf) {
+      double k[2][4] = {};
+      kernel_half64<MC, MF, NTAB>(s, sp, sx1, sx2, tr, tc, hf, tab, itab, k);
+#pragma unroll
+      for (int a = 0; a < 2; ++a) {
+        const int i = i0 + 4 * tr + 2 * hf + a;
+        double t = 0.0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const int j = j0 + 4 * tc + c;
+          double kv = k[a][c];
+          if (i >= n1 || j >= n2) kv = 0.0;
+          else if (i == j) kv += dg;
+          t += kv * sv[4 * tc + c];
+        }
+        if (hf == 0) acc[a] += t;
+        else acc[2 + a] += t;
+      }
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) acc[a] += __shfl_xor(acc[a], o, 64);
+  if (tc == 0) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      const int i = i0 + 4 * tr + a;
+      if (i >= n1) continue;
+      if (S == 1) out[(int64_t)i * o_rs + (int64_t)l * o_ls] = acc[a];
+      else part[((int64_t)l * S + sl) * n1 + i] = acc[a];
+    }
+  }
+}
+
+// out[i][l] = sum_s part[l][s][i] in slab order (S == 0: zeros, the product over no columns).  Grid (n1 / 256, L).
+__global__ __launch_bounds__(256) void gram_matvec_sum(const double* __restrict__ part, int S, int n1,
+                                                       double* __restrict__ out, int64_t o_rs, int64_t o_ls) {
+  const int i = blockIdx.x * 256 + threadIdx.x, l = blockIdx.y;
+  if (i >= n1) return;
+  double acc = 0.0;
+  for (int s = 0; s < S; ++s) acc += part[((int64_t)l * S + s) * n1 + i];
+  out[(int64_t)i * o_rs + (int64_t)l * o_ls] = acc;
 }
 
 // per-parameter derivative constants of kl_gram_bwd_tiles' raw sums (host-built from the spec):
@@ -1639,6 +1800,105 @@ int kl_gram_resid(const lvae_kernel_spec* spec, const double* x, int ldx, int n,
   return 0;
 }
 
+// Column slabs of the fused Gram x vector, a function of (n1, n2, L) alone: about 512 workgroups in all (two per
+// CU at gram_matvec_tiles' occupancy), a slab no shorter than 4 column tiles unless x2 has fewer (every workgroup
+// builds its tables and stages its rows of x1 first), every slab non-empty.
+static int matvec_slabs(int n1, int n2, int L, int* tps_out) {
+  const int64_t rows = (int64_t)cdiv(n1, kGT) * L;
+  const int ntc = cdiv(n2, kGT);
+  int64_t S = rows > 0 ? 512 / rows : 1;
+  const int cap = cdiv(ntc, 4);
+  S = S > cap ? cap : S;
+  S = S < 1 ? 1 : S;
+  const int tps = ntc > 0 ? cdiv(ntc, S) : 1;
+  if (tps_out) *tps_out = tps;
+  return ntc > 0 ? cdiv(ntc, tps) : 1;
+}
+
+// the covariate columns the spec reads, compacted to staged slots (ds.dim rewritten to the slots); false when a
+// factor's dim is outside 0 .. kMaxQ - 1 (lvae_gram_f64's limit, so at most kMaxQ distinct columns); *ld_min = 1 + the largest column
+static bool matvec_cols(const lvae_kernel_spec* spec, DevSpec& ds, MvCols& qc, int* ld_min) {
+  ds = to_dev(spec);
+  qc.nq = 0;
+  *ld_min = 1;
+  for (int r = 0; r < spec->n_comp; ++r)
+    for (int f = 0; f < spec->n_fac[r]; ++f) {
+      const int d = spec->dim[r][f];
+      if (d < 0 || d >= kMaxQ) return false;
+      int q = 0;
+      while (q < qc.nq && qc.col[q] != d) ++q;
+      if (q == qc.nq) {
+        if (qc.nq == kMaxQ) return false;
+        qc.col[qc.nq++] = d;
+      }
+      ds.dim[r][f] = q;
+      *ld_min = d + 1 > *ld_min ? d + 1 : *ld_min;
+    }
+  return true;
+}
+
+// 1 + the largest covariate column the fused product reads for this spec; 0: a spec it does not take
+int gram_matvec_spec_ld(const lvae_kernel_spec* spec) {
+  DevSpec ds;
+  MvCols qc;
+  int ld_min = 0;
+  return spec && spec_bucket(spec) && matvec_cols(spec, ds, qc, &ld_min) ? ld_min : 0;
+}
+
+size_t gram_matvec_ws_bytes(int n1, int n2, int L) {
+  if (n1 <= 0 || n2 <= 0 || L <= 0) return 0;
+  const int S = matvec_slabs(n1, n2, L, nullptr);
+  return S > 1 ? (size_t)L * S * n1 * sizeof(double) : 0;
+}
+
+// The fused product; v and out each in the public entry point's [n, ld] layout (v_t / o_t == 0: element (j, l) at
+// [j ld + l]) or transposed, [L, ld] (element (j, l) at [l ld + j]: the exact predictor's work vectors).
+// Argument codes are lvae_gram_matvec_f64's.
+int gram_matvec_f64(const lvae_kernel_spec* spec, const double* x1, int64_t ld1, int n1, const double* x2, int64_t ld2,
+                    int n2, int L, const double* params, const double* diag, const double* v, int64_t ld_v, int v_t,
+                    double* out, int64_t ld_out, int o_t, void* workspace, hipStream_t st) {
+  if (!spec) return -1;
+  const int bucket = spec_bucket(spec);
+  DevSpec ds;
+  MvCols qc;
+  int ld_min = 1;
+  if (!bucket || !matvec_cols(spec, ds, qc, &ld_min)) return -1;
+  if (n1 < 0) return -4;
+  if (n2 < 0) return -7;
+  if (L < 1) return -8;
+  if (n1 == 0) return 0;
+  if (!x1) return -2;
+  if (ld1 < ld_min) return -3;
+  if (n2 > 0 && !x2) return -5;
+  if (n2 > 0 && ld2 < ld_min) return -6;
+  if (!params) return -9;
+  if (diag && n1 != n2) return -10;
+  if (n2 > 0 && !v) return -11;
+  if (n2 > 0 && ld_v < (v_t ? n2 : L)) return -12;
+  if (!out) return -13;
+  if (ld_out < (o_t ? n1 : L)) return -14;
+  const int64_t v_rs = v_t ? 1 : ld_v, v_ls = v_t ? ld_v : 1, o_rs = o_t ? 1 : ld_out, o_ls = o_t ? ld_out : 1;
+  int tps = 1;
+  const int S = n2 > 0 ? matvec_slabs(n1, n2, L, &tps) : 0;
+  if (S > 1 && (!workspace || ((uintptr_t)workspace & 255))) return -15;
+  double* part = (double*)workspace;
+  if (S >= 1) {
+    const dim3 grid(cdiv(n1, kGT) * S, L);
+    // (8, 2) reads at most 16 columns; (16, 4) beyond 16 takes the 32-slot image with 16-entry distance tables
+    // (2 x 16 KiB of covariates + 8 KiB of tables, where 64-entry tables alone take 32 KiB of the 64 KiB of LDS)
+#define LVAE_MV_LAUNCH(MC, MF, Q, NT)                                                                               \
+  gram_matvec_tiles<MC, MF, Q, NT><<<grid, 256, 0, st>>>(ds, qc, x1, ld1, n1, x2, ld2, n2, params, diag, v, v_rs,   \
+                                                         v_ls, out, o_rs, o_ls, part, S, tps)
+    if (bucket == 1) LVAE_MV_LAUNCH(8, 2, kMaxQB, kIntTab);
+    else if (qc.nq <= kMaxQB) LVAE_MV_LAUNCH(16, 4, kMaxQB, kIntTab);
+    else LVAE_MV_LAUNCH(16, 4, kMaxQ, 16);
+#undef LVAE_MV_LAUNCH
+  }
+  if (S != 1) gram_matvec_sum<<<dim3(cdiv(n1, 256), L), 256, 0, st>>>(part, S, n1, out, o_rs, o_ls);
+  LVAE_CHECK_LAUNCH();
+  return 0;
+}
+
 // workgroups per latent dim of the adjoint: ~1536 in all, each looping over ~ntiles / G tiles
 static int kl_gram_bwd_groups(int np_, int L) {
   const int nt = np_ / kGT, ntiles = nt * (nt + 1) / 2;
@@ -1771,6 +2031,15 @@ int lvae_gram_f32(const lvae_kernel_spec* spec, lvae_xview x1, lvae_xview x2, in
                   const double* params, const double* diag, float* out, int64_t osb, int64_t osl, int64_t ldo,
                   void* stream) {
   return lvae::gram_launch<float>(spec, x1, x2, nb, L, n1, n2, params, diag, out, osb, osl, ldo, stream);
+}
+
+size_t lvae_gram_matvec_workspace_size(int n1, int n2, int L) { return lvae::gram_matvec_ws_bytes(n1, n2, L); }
+
+int lvae_gram_matvec_f64(const lvae_kernel_spec* spec, const double* x1, int64_t ld1, int n1, const double* x2,
+                         int64_t ld2, int n2, int L, const double* params, const double* diag, const double* v,
+                         int64_t ld_v, double* out, int64_t ld_out, void* workspace, void* stream) {
+  return lvae::gram_matvec_f64(spec, x1, ld1, n1, x2, ld2, n2, L, params, diag, v, ld_v, 0, out, ld_out, 0, workspace,
+                               (hipStream_t)stream);
 }
 
 size_t lvae_gram_bwd_workspace_size(int nb, int L, int n1, int n2) {

@@ -143,7 +143,57 @@ __global__ void pr_out_kernel(int L, int Nt, const double* __restrict__ out1, do
 
 inline int nblk(int64_t n) { return cdiv(n, 256); }
 
+// ---- exact-GP predictor (model_test.py:11-17 predict_gp, as MSE_test calls it, model_test.py:19-82) ----
+// workspace of lvae_predict_exact_f64: K [L, n, n] (factored in place), the work vectors a, r [L, n], the factor's
+// log-determinants, the solves' inverted diagonal blocks and the fused products' slab partials
+struct EWs {
+  double *K, *a, *r, *logdet;
+  char *trsm, *mv;
+  size_t bytes;
+  EWs(char* base, int n, int nt, int L) {
+    size_t off = 0;
+    auto take = [&](size_t b) {
+      char* p = base ? base + off : nullptr;
+      off += align256(b);
+      return p;
+    };
+    K = (double*)take((size_t)L * n * n * sizeof(double));
+    a = (double*)take((size_t)L * n * sizeof(double));
+    r = (double*)take((size_t)L * n * sizeof(double));
+    logdet = (double*)take((size_t)L * sizeof(double));
+    trsm = take(lvae_trsm_workspace_size(n, L));
+    const size_t m0 = lvae_gram_matvec_workspace_size(n, n, L), m1 = lvae_gram_matvec_workspace_size(nt, n, L);
+    mv = take(m0 > m1 ? m0 : m1);
+    bytes = off;
+  }
+};
+
+// a[l][i] = mu[i][l]
+__global__ void pe_gather_kernel(int L, int n, const double* __restrict__ mu, int64_t ld_mu, double* __restrict__ a) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (int64_t)L * n) return;
+  const int64_t l = e / n, i = e % n;
+  a[e] = mu[i * ld_mu + l];
+}
+// r[l][i] = mu[i][l] - r[l][i]   (r holds K a0 on entry)
+__global__ void pe_resid_kernel(int L, int n, const double* __restrict__ mu, int64_t ld_mu, double* __restrict__ r) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (int64_t)L * n) return;
+  const int64_t l = e / n, i = e % n;
+  r[e] = mu[i * ld_mu + l] - r[e];
+}
+// a += r
+__global__ void pe_add_kernel(int64_t m, double* __restrict__ a, const double* __restrict__ r) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < m) a[e] += r[e];
+}
+
 }  // namespace
+
+int gram_matvec_f64(const lvae_kernel_spec* spec, const double* x1, int64_t ld1, int n1, const double* x2, int64_t ld2,
+                    int n2, int L, const double* params, const double* diag, const double* v, int64_t ld_v, int v_t,
+                    double* out, int64_t ld_out, int o_t, void* workspace, hipStream_t st);
+int gram_matvec_spec_ld(const lvae_kernel_spec* spec);
 }  // namespace lvae
 
 using namespace lvae;
@@ -216,6 +266,58 @@ int lvae_predict_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec
     pr_out_kernel<<<nblk((int64_t)L * Nt), 256, 0, st>>>(L, Nt, w.out1, out);
   }
   if (info) pr_info_kernel<<<nblk(L), 256, 0, st>>>(L, P, w.info, info);
+  LVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+size_t lvae_predict_exact_workspace_size(int n, int nt, int L) {
+  if (n < 1 || nt < 0 || L < 1) return 0;
+  return EWs(nullptr, n, nt, L).bytes;
+}
+
+int lvae_predict_exact_f64(const lvae_kernel_spec* spec, const double* x, int64_t ldx, int n, int L,
+                           const double* params, const double* noise, const double* mu, int64_t ld_mu,
+                           const double* tx, int64_t ldt, int nt, double* out, int64_t ld_out, int32_t* info,
+                           void* workspace, void* stream) {
+  const int ld_min = spec ? gram_matvec_spec_ld(spec) : 0;
+  if (ld_min < 1 || ld_min > 32) return -1;  // (before any launch)
+  if (!x) return -2;
+  if (ldx < ld_min) return -3;
+  if (n < 1) return -4;
+  if (L < 1) return -5;
+  if (!params) return -6;
+  if (!noise) return -7;
+  if (!mu) return -8;
+  if (ld_mu < L) return -9;
+  if (nt < 0) return -12;
+  if (nt > 0 && !tx) return -10;
+  if (nt > 0 && ldt < ld_min) return -11;
+  if (nt > 0 && !out) return -13;
+  if (nt > 0 && ld_out < L) return -14;
+  if (!info) return -15;
+  if (!workspace || ((uintptr_t)workspace & 255)) return -16;
+  hipStream_t st = (hipStream_t)stream;
+  EWs w((char*)workspace, n, nt, L);
+  const int64_t nn = (int64_t)n * n;
+  // K = k(x, x) + noise I, factored in place (info[l] > 0: dim l is not positive definite; its outputs are
+  // then meaningless, every other dim's are unaffected)
+  const lvae_xview xv{x, 0, 0, ldx};
+  LVAE_TRY(lvae_gram_f64(spec, xv, xv, 1, L, n, n, params, noise, w.K, 0, nn, n, stream));
+  LVAE_TRY(lvae_potrf_f64(n, L, w.K, n, nn, w.K, n, nn, w.logdet, info, stream));
+  if (nt == 0) {
+    LVAE_CHECK_LAUNCH();
+    return 0;
+  }
+  // a0 = K^-1 mu, then one refinement step a = a0 + K^-1 (mu - K a0) with K a0 from the covariates again (K itself
+  // is overwritten by its factor): the solve alone is cond(K) ulps from the reference's explicit-inverse product
+  pe_gather_kernel<<<nblk((int64_t)L * n), 256, 0, st>>>(L, n, mu, ld_mu, w.a);
+  LVAE_TRY(lvae_potrs_f64(n, 1, L, w.K, n, nn, w.a, 1, n, w.trsm, stream));
+  LVAE_TRY(gram_matvec_f64(spec, x, ldx, n, x, ldx, n, L, params, noise, w.a, n, 1, w.r, n, 1, w.mv, st));
+  pe_resid_kernel<<<nblk((int64_t)L * n), 256, 0, st>>>(L, n, mu, ld_mu, w.r);
+  LVAE_TRY(lvae_potrs_f64(n, 1, L, w.K, n, nn, w.r, 1, n, w.trsm, stream));
+  pe_add_kernel<<<nblk((int64_t)L * n), 256, 0, st>>>((int64_t)L * n, w.a, w.r);
+  // Zpred = k(X*, x) a
+  LVAE_TRY(gram_matvec_f64(spec, tx, ldt, nt, x, ldx, n, L, params, nullptr, w.a, n, 1, out, ld_out, 0, w.mv, st));
   LVAE_CHECK_LAUNCH();
   return 0;
 }

@@ -1,0 +1,104 @@
+"""Test-set evaluation after training (model_test.py:11-143): ``MSE_test`` for models trained with the exact KL
+(the exact-GP predictor, lvae_predict_exact_f64) and ``MSE_test_GPapprox`` for the Hensman / GPapprox regimes
+(batch_predict_varying_T, lvae_predict_f64).  Reference names and signatures; both write the two-number
+``result_error.csv`` (mean masked MSE of the autoencoder's own reconstruction, and of the decoded GP prediction).
+
+Differences from the reference, none of which changes a result it can produce:
+  * the test set is read through the project's device-resident HealthMNISTDatasetConv and evaluated as one device
+    batch (no DataLoader workers), by the project's fp32 ConvVAE (the reference casts the images to fp64);
+  * MSE_test solves with the Cholesky factor and one refinement step instead of forming K^-1;
+  * the "more than 6040 prediction rows" rule draws its 6000 rows from 40..n-1 (model_test.py:60 draws from
+    0..n-1 and then adds 40, which can index past the end); an ``rng`` keyword seeds the draw, the default is
+    NumPy's global generator as in the reference;
+  * nothing is printed: the numbers are in the file.
+``VAEtest`` (model_test.py:145-167) is here because the reference's VAE.py imports it from this module; it
+returns the autoencoder's mean masked MSE, which the reference only prints.
+"""
+import os
+
+import numpy as np
+import torch
+
+from .data import HealthMNISTDatasetConv
+from .predict import batch_predict_varying_T, predict_exact
+
+KEEP_ROWS, SAMPLE_ROWS = 40, 6000   # model_test.py:59-61
+
+
+def predict_gp(kernel_component, full_kernel_inverse, z):
+    """Predictive mean kernel_component @ full_kernel_inverse @ z (model_test.py:11-17)."""
+    return torch.matmul(torch.matmul(kernel_component, full_kernel_inverse), z)
+
+
+def select_prediction_rows(n, rng=None):
+    """Row indices MSE_test keeps of an n-row prediction set: all of them up to 6040 rows (None), else rows
+    0..39 and 6000 distinct rows drawn from 40..n-1 (model_test.py:59-63)."""
+    if n <= KEEP_ROWS + SAMPLE_ROWS:
+        return None
+    r = (np.random if rng is None else rng).choice(n - KEEP_ROWS, SAMPLE_ROWS, replace=False) + KEEP_ROWS
+    return np.concatenate((np.arange(KEEP_ROWS), r))
+
+
+def _whole_set(dataset, model):
+    """(images, mask [B, 1296], labels [B, 6] fp64) of a device-resident dataset as one batch in the model's dtype"""
+    dtype = next(model.parameters()).dtype
+    everything = dataset.batch(torch.arange(len(dataset)))
+    images = everything["digit"].to(dtype)
+    return images, everything["mask"].reshape(images.shape[0], -1).to(dtype), everything["label"].to(torch.float64)
+
+
+def _mean_mse(model, recon, images, mask):
+    """The per-image masked MSE of ConvVAE.loss_function, averaged over the images"""
+    return float(model.loss_function(recon, images, mask)[0].mean())
+
+
+def _evaluate(files, root, type_nnet, model, out_file, predict):
+    """The body the two tests share: the autoencoder's own mean masked MSE over the test set and that of the
+    decoded latents ``predict(labels)``, written one per line to ``out_file``."""
+    if type_nnet != "conv":
+        raise NotImplementedError("lvae_amd evaluates the convolutional VAE only (type_nnet='conv')")
+    data_csv, label_csv, mask_csv = files
+    dataset = HealthMNISTDatasetConv(data_csv, label_csv, mask_csv, root, device=next(model.parameters()).device)
+    with torch.no_grad():
+        images, mask, labels = _whole_set(dataset, model)
+        own = _mean_mse(model, model(images)[0], images, mask)
+        latents = predict(labels).to(images.dtype)
+        gp = _mean_mse(model, model.decode(latents), images, mask)
+    np.savetxt(out_file, np.array([own, gp]))
+
+
+def MSE_test(csv_file_test_data, csv_file_test_label, test_mask_file, data_source_path, type_nnet, nnet_model,
+             covar_module, likelihoods, results_path, latent_dim, prediction_x, prediction_mu, rng=None):
+    """Mean squared error of the test set under the exact-GP predictor (model_test.py:19-82); writes
+    ``result_error.csv`` under ``results_path``."""
+    ind = select_prediction_rows(prediction_x.shape[0], rng)
+    if ind is not None:
+        prediction_x, prediction_mu = prediction_x[ind], prediction_mu[ind]
+    device = next(nnet_model.parameters()).device
+    px, pm = prediction_x.to(device), prediction_mu[:, :latent_dim].to(device)
+    if isinstance(covar_module, (list, tuple, torch.nn.ModuleList)):
+        covar_module, likelihoods = list(covar_module)[:latent_dim], list(likelihoods)[:latent_dim]
+    _evaluate((csv_file_test_data, csv_file_test_label, test_mask_file), data_source_path, type_nnet, nnet_model,
+              os.path.join(results_path, "result_error.csv"),
+              lambda labels: predict_exact(covar_module, likelihoods, px, labels, pm))
+
+
+def MSE_test_GPapprox(csv_file_test_data, csv_file_test_label, test_mask_file, data_source_path, type_nnet,
+                      nnet_model, covar_module0, covar_module1, likelihoods, results_path, latent_dim, prediction_x,
+                      prediction_mu, zt_list, P, T, id_covariate, varying_T=False, save_file='result_error.csv'):
+    """Mean squared error of the test set with the GP approximation (model_test.py:85-143); writes ``save_file``
+    under ``results_path``.  ``P``, ``T`` and ``varying_T`` are accepted and not used, as in the reference (the
+    predictor takes subjects of any length)."""
+    device = next(nnet_model.parameters()).device
+    px, pm = prediction_x.to(device), prediction_mu.to(device)
+    _evaluate((csv_file_test_data, csv_file_test_label, test_mask_file), data_source_path, type_nnet, nnet_model,
+              os.path.join(results_path, save_file),
+              lambda labels: batch_predict_varying_T(latent_dim, covar_module0, covar_module1, likelihoods, px,
+                                                     labels, pm, zt_list, id_covariate, eps=1e-6))
+
+
+def VAEtest(test_dataset, nnet_model, type_nnet, id_covariate):
+    """Mean masked MSE of the autoencoder alone over a device-resident dataset (model_test.py:145-167)."""
+    with torch.no_grad():
+        images, mask, _ = _whole_set(test_dataset, nnet_model)
+        return _mean_mse(nnet_model, nnet_model(images)[0], images, mask)

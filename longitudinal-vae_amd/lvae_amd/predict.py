@@ -1,8 +1,11 @@
 """GP posterior prediction of the latents (utils.py:115-211 batch_predict_varying_T), the step
 MSE_test_GPapprox (model_test.py:85-143) runs after training.  Same signature and return value;
 the computation is one batched HIP pass (lvae_predict_f64) instead of the reference's per-subject
-Python loops and its removed ``torch.solve``.
+Python loops and its removed ``torch.solve``.  ``predict_exact`` is the exact-GP predictor of MSE_test
+(model_test.py:19-82) for models trained with the exact KL (lvae_predict_exact_f64).
 """
+import ctypes
+
 import torch
 
 from . import _lib
@@ -58,4 +61,49 @@ def batch_predict_varying_T(latent_dim, covar_module0, covar_module1, likelihood
                               _lib.stream_ptr())
     _lib.check(rc, "predict")
     _check_info(info, "batch_predict_varying_T cholesky (10000+col: K0zz, 20000+col: B_st, 30000+col: H)")
+    return out
+
+
+def predict_exact(covar_module, likelihoods, prediction_x, test_x, prediction_mu, max_workspace_bytes=4 << 30):
+    """Z_pred [N_test, L] fp64: the exact-GP posterior mean k(X*, X) (k(X, X) + noise I)^-1 mu per latent dim
+    (model_test.py:11-17 predict_gp as MSE_test calls it, model_test.py:65-76), one HIP pass per group of dims
+    (lvae_predict_exact_f64) instead of the reference's per-dim explicit inverse and dense [N_test, N] Gram.
+
+    ``covar_module`` is a batched module or a per-dim list (as MSE_test passes), ``prediction_mu`` [N, L] the
+    encoder means at ``prediction_x`` [N, Q].  The dims are processed in groups whose workspace (about 8 N^2
+    bytes a dim) stays under ``max_workspace_bytes``; a non-positive-definite K raises LinAlgError."""
+    lib = _lib.lib()
+    spec, params = _stack_modules(covar_module)
+    L = int(prediction_mu.shape[1])
+    if params.shape[0] == 1 and L > 1:
+        params = params.expand(L, -1)
+    if params.shape[0] != L:
+        raise ValueError(f"kernel batch {params.shape[0]} != latent dims {L}")
+    for mod in (covar_module, likelihoods):
+        for m_ in (mod if isinstance(mod, (list, tuple, torch.nn.ModuleList)) else [mod]):
+            if hasattr(m_, "eval"):
+                m_.eval()
+    dev = prediction_mu.device
+    f64 = lambda t: t.detach().to(dev, torch.float64).contiguous()
+    x, tx, mu, p = f64(prediction_x), f64(test_x), f64(prediction_mu), f64(params)
+    noise = f64(_noise_vector(likelihoods, L)).reshape(L)
+    n, nt, n_params = int(x.shape[0]), int(tx.shape[0]), int(p.shape[1])
+    if n < 1 or mu.shape[0] != n:
+        raise ValueError(f"prediction_mu rows {mu.shape[0]} != prediction_x rows {n} (>= 1)")
+    size = lambda g: int(lib.lvae_predict_exact_workspace_size(n, nt, g))
+    group = L
+    while group > 1 and size(group) > max_workspace_bytes:
+        group -= 1
+    out = torch.empty(nt, L, dtype=torch.float64, device=dev)
+    info = torch.empty(L, dtype=torch.int32, device=dev)
+    ws = torch.empty(size(group), dtype=torch.uint8, device=dev)
+    at = lambda t, off: ctypes.c_void_p(t.data_ptr() + 8 * off)
+    for l0 in range(0, L, group):
+        g = min(group, L - l0)
+        rc = lib.lvae_predict_exact_f64(spec, _lib.ptr(x), x.stride(0), n, g, at(p, l0 * n_params), at(noise, l0),
+                                        at(mu, l0), L, _lib.ptr(tx) if nt else None, tx.stride(0), nt,
+                                        at(out, l0) if nt else None, L,
+                                        ctypes.c_void_p(info.data_ptr() + 4 * l0), _lib.ptr(ws), _lib.stream_ptr())
+        _lib.check(rc, "predict_exact")
+    _check_info(info, "predict_exact cholesky of k(X, X) + noise I")
     return out
