@@ -380,6 +380,40 @@ int lvae_natgrad_update_f64(int L, int M, double* m, double* H, const double* gr
                             const double* grad_H, double lr, const double* iH, int32_t* info,
                             void* workspace, void* stream);
 
+/* Full-batch deviance upper bound (DUBO, elbo_functions.py:86-142) of all L latent dims, and its adjoint.
+ * P subjects of T consecutive rows each (N = P T rows, no varying T), M inducing points, Q covariates.      */
+typedef struct lvae_dubo_dims {
+  int32_t L, M, P, T, Q;
+  double eps;              /* jitter on K0zz */
+} lvae_dubo_dims;
+
+/* Reads *d unchecked (d must not be NULL; the size is only meaningful for dims that the calls below accept). */
+size_t lvae_dubo_workspace_size(const lvae_dubo_dims* d);
+
+/* Forward: dubo [L], one value per latent dim.  x [P*T, Q], z [L, M, Q], mu / logv [P*T, L] (fp64, row-major),
+ * params0 [L, P0], params1 [L, P1], noise [L].  info [L] (may be NULL): 0, or the first failed factorisation of
+ * dim l in the order K0zz (10000 + col), B_p (20000 + col, the first such subject), W = K0zz + K0zx B^-1 K0xz
+ * (30000 + col), col the 1-based failing column; dubo[l] and that dim's gradients then mean nothing, the other
+ * dims are unaffected.  Kernel launches only, on the caller's stream; nothing is allocated; no atomics: the same
+ * inputs give the same bits on every call and every device (the split of the subjects over workgroups depends
+ * on P alone).  T <= 32 runs the fused subject pass, larger T batched small products.
+ * Return codes of both calls, checked in this order before any launch (nothing is written): -1 / -2: spec0 /
+ * spec1 NULL or outside every template bucket; -3: d NULL, L < 1, M or T outside 1..128, P < 1 or Q < 1;
+ * -4: workspace NULL or not 256-byte aligned.  0 = ok.                                               */
+int lvae_dubo_fwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, const lvae_dubo_dims* d,
+                      const double* x, const double* z, const double* mu, const double* logv,
+                      const double* params0, const double* params1, const double* noise, double* dubo,
+                      int32_t* info, void* workspace, void* stream);
+/* Backward given the cotangents gdubo [L] (device): dmu, dlogv [P*T, L]; dparams0 [L, P0], dparams1 [L, P1],
+ * dnoise [L] (may be NULL); each dim's gradients are scaled by its own gdubo[l].  Outputs are OVERWRITTEN
+ * (whatever they held).  Runs on the workspace the forward left (it may be called again on it).  z is not
+ * differentiated.                                                                                      */
+int lvae_dubo_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, const lvae_dubo_dims* d,
+                      const double* x, const double* z, const double* mu, const double* logv,
+                      const double* params0, const double* params1, const double* noise, const double* gdubo,
+                      double* dmu, double* dlogv, double* dparams0, double* dparams1, double* dnoise,
+                      void* workspace, void* stream);
+
 /* ConvVAE encoder (VAE.py:44-50): y = max_pool2d(relu(x), 2, 2) over planes = N*C planes of H x W
  * (H, W even) fp32, idx = argmax byte (0..3, row-major in the window, first strict maximum);
  * backward gx = the pooled gradient routed to the argmax where y > 0, 0 elsewhere.            */

@@ -1,0 +1,598 @@
+// dubo.hip -- full-batch deviance upper bound (DUBO, elbo_functions.py:86-142) of all L latent dims and its
+// analytic adjoint.  fp64 throughout; subjects are P blocks of T consecutive rows, N = P T.
+//
+// Per latent dim:
+//   X = k0(x, z) [N,M]   Kz = k0(z, z) + eps I   K0_p = k0(x_p, x_p)   B_p = k1(x_p, x_p) + noise I
+//   iK = Kz^-1, iB_p = B_p^-1 (+ log-dets)                                              spd_inv_small
+//   iBK_p = iB_p X_p   Q = sum_p X_p^T iBK_p   R = sum_p iBK_p^T D_p iBK_p   p = sum_p iBK_p^T m_p   (D = diag e^logv)
+//   W = sym(Kz + Q), iW = W^-1 (spd_inv_small + one Newton step on a double-double residual), w = iW p
+//   dubo = 1/2 [ sum diag(iB) v - sum iW.R + sum_p m_p^T iB_p m_p - p.w - N - log|Kz| + sum log|B_p| + log|W|
+//                - sum logv + sum iB.K0 - sum Q.iK ]
+// The data-sized products (iBK, Q, R, p and the per-subject sums) are ONE pass over the subjects
+// (dubo_subject_kernel): a workgroup walks kDuboS consecutive subjects with Q, R in MFMA accumulators and
+// writes one partial; dubo_reduce_kernel adds the partials in group order (no atomics: bit-reproducible).
+// T > 32 (X_p and iBK_p no longer fit the LDS tile) takes batched gemm_small launches instead.
+//
+// Adjoint (g = gdubo[l]; U = iBK iW, a = iB m - U p = Sigma^-1 m, F = iB D iBK, Z = iBK iK):
+//   dmu = g a      dlogv = g/2 ((iB_ii - sum_j U_ij iBK_ij) v_i - 1)
+//   dX  = g ((iBK + U R - F) iW - Z - a w^T)
+//   dKz = g (-1/2 (iK - iW - iW R iW - w w^T) + 1/2 iK Q iK)      dK0_p = g/2 iB_p
+//   dB_p = g/2 (iB - iB D iB - iB K0 iB - a a^T - (U - Z) iBK^T - (U R - 2 F) U^T)_p
+// (dB_p is the adjoint of the dense form up to an antisymmetric part, which the symmetric Gram adjoint and the
+// trace of dnoise do not see: F U^T + U F^T -> 2 F U^T.)
+#include "common.hpp"
+#include "blkinv.hpp"
+#include "gram_bwd.hpp"
+
+namespace lvae {
+
+int spd_inv_small_f64(int n, int batch, const double* A, int64_t stride, double* Ainv, int64_t stride_out,
+                      double* logdet, int32_t* info, hipStream_t st);
+int gemm_small_f64(int ta, int tb, int m, int n, int k, double alpha, const double* A, int lda, int64_t sa1,
+                   int64_t sa2, const double* B, int ldb, int64_t sb1, int64_t sb2, double beta, double* C, int ldc,
+                   int64_t sc1, int64_t sc2, int nb1, int nb2, hipStream_t st);
+
+namespace {
+
+constexpr int kDuboS = 16;     // subjects per workgroup of the fused pass (the group count is ceil(P / kDuboS))
+constexpr int kDuboT = 32;     // largest T of the fused pass
+constexpr int kDuboLD = 132;   // LDS row stride of the [T][M] tiles (128 + 4 doubles)
+constexpr int kDuboTPW = 5;    // lower 16 x 16 tiles of Q (and of R) per wave: 36 tiles at M = 128 over 8 waves
+constexpr int kDuboScal = 8;   // scalar slots per dim: m.iB.m, diag(iB).v, iB.K0, sum logv, sum log|B_p|
+
+inline int dubo_groups(int P) { return (P + kDuboS - 1) / kDuboS; }
+inline int dubo_tiles(int M) {
+  const int tm = (M + 15) / 16;
+  return tm * (tm + 1) / 2;
+}
+// doubles of one (dim, group) partial: Q and R lower tiles in accumulator order, p [128], the scalars
+inline int64_t dubo_part_stride(int M) { return (int64_t)2 * dubo_tiles(M) * 256 + 128 + kDuboScal; }
+
+struct DWs {
+  double *X, *iBK, *U, *UR, *F, *Z, *tNM, *dX;                                    // [L,N,M]
+  double *Kz, *iK, *Q, *R, *W, *iW0, *E, *iW, *iWR, *iWRiW, *iKQ, *iKQiK, *dKz;  // [L,M,M]
+  double *K0st, *Bst, *iB, *VB, *iBDiB, *K0iB, *iBK0iB, *GB, *GK0;               // [L,P,T,T]
+  double *p, *w;                                                                  // [L,M]
+  double *s, *y, *a;                                                              // [L,N]
+  double *ldK, *ldB, *ldW, *epsv, *scal, *part, *gpart;
+  int32_t* info;
+  size_t bytes;
+  DWs(char* base, const lvae_dubo_dims& d) {
+    size_t off = 0;
+    auto take = [&](size_t n) {
+      double* q = base ? (double*)(base + off) : nullptr;
+      off += align256(n * sizeof(double));
+      return q;
+    };
+    const size_t L = d.L, M = d.M, N = (size_t)d.P * d.T, TT = (size_t)d.P * d.T * d.T;
+    double** nm[] = {&X, &iBK, &U, &UR, &F, &Z, &tNM, &dX};
+    for (auto q : nm) *q = take(L * N * M);
+    double** mm[] = {&Kz, &iK, &Q, &R, &W, &iW0, &E, &iW, &iWR, &iWRiW, &iKQ, &iKQiK, &dKz};
+    for (auto q : mm) *q = take(L * M * M);
+    double** tt[] = {&K0st, &Bst, &iB, &VB, &iBDiB, &K0iB, &iBK0iB, &GB, &GK0};
+    for (auto q : tt) *q = take(L * TT);
+    p = take(L * M);
+    w = take(L * M);
+    s = take(L * N);
+    y = take(L * N);
+    a = take(L * N);
+    ldK = take(L);
+    ldB = take(L * d.P);
+    ldW = take(L);
+    epsv = take(L);
+    scal = take(L * kDuboScal);
+    part = take(L * (size_t)dubo_groups(d.P) * (size_t)dubo_part_stride(d.M));
+    info = (int32_t*)take(L * (2 + (size_t)d.P));
+    // Gram-adjoint partials of the four Grams (gram.hip: 1024 elements per chunk, <= 145 slots)
+    const size_t chunks = (N * M + 1023) / 1024 + (M * M + 1023) / 1024 + 2 * ((TT + 1023) / 1024);
+    gpart = take(L * chunks * 145);
+    bytes = off;
+  }
+};
+
+inline int blocks(int64_t n) { return cdiv(n, 256); }
+
+__global__ void dubo_fill_kernel(double* p, int n, double v) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) p[i] = v;
+}
+
+// lower tile t -> (row tile, column tile), row-major over the lower triangle
+__device__ inline void dubo_tile(int t, int& ti, int& tj) {
+  int i = 0;
+  while ((i + 1) * (i + 2) / 2 <= t) ++i;
+  ti = i;
+  tj = t - i * (i + 1) / 2;
+}
+
+// The fused subject pass: grid (groups, L), 512 threads.  Group g walks subjects [g kDuboS, (g + 1) kDuboS).
+// Per subject: iB_p [T,T], X_p [T,M], m_p, v_p into LDS (zero padded to whole MFMA steps); iBK_p = iB_p X_p on
+// v_mfma_f64_16x16x4 (C[(lane >> 4) + 4 r][lane & 15]) -> LDS and HBM; then Q += X_p^T iBK_p and
+// R += iBK_p^T D_p iBK_p on the lower 16 x 16 tiles, tile t = wave + 8 k in accumulators Qa[k] / Ra[k] for the
+// whole walk, p and the five scalar sums in plain registers.  One partial per (dim, group).
+__global__ __launch_bounds__(512) void dubo_subject_kernel(int M, int P, int T, int L, int nt, int64_t pstride,
+                                                           const double* __restrict__ X,
+                                                           const double* __restrict__ iB,
+                                                           const double* __restrict__ K0st,
+                                                           const double* __restrict__ ldB,
+                                                           const double* __restrict__ mu,
+                                                           const double* __restrict__ logv,
+                                                           double* __restrict__ iBK, double* __restrict__ part) {
+  __shared__ double sB[kDuboT][kDuboT + 1];
+  __shared__ double sX[kDuboT][kDuboLD];
+  __shared__ double sY[kDuboT][kDuboLD];
+  __shared__ double sm[kDuboT], sv[kDuboT];
+  __shared__ double red[8];
+  const int g = blockIdx.x, l = blockIdx.y, G = gridDim.x;
+  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
+  const int tM = (M + 15) >> 4, tT = (T + 15) >> 4, T4 = (T + 3) & ~3;
+  const int64_t N = (int64_t)P * T, TT = (int64_t)T * T;
+  int ti[kDuboTPW], tj[kDuboTPW];
+  bool on[kDuboTPW];
+  bi_f64x4 Qa[kDuboTPW], Ra[kDuboTPW];
+#pragma unroll
+  for (int k = 0; k < kDuboTPW; ++k) {
+    const int t = wv + 8 * k;
+    on[k] = t < nt;
+    dubo_tile(on[k] ? t : 0, ti[k], tj[k]);
+    Qa[k] = bi_f64x4{0.0, 0.0, 0.0, 0.0};
+    Ra[k] = bi_f64x4{0.0, 0.0, 0.0, 0.0};
+  }
+  double pj = 0.0, s_mbm = 0.0, s_dv = 0.0, s_bk0 = 0.0, s_lv = 0.0, s_ldb = 0.0;
+  // the padding (rows T.., columns M..) is zeroed once; the walk only rewrites the valid parts
+  for (int e = tid; e < kDuboT * (kDuboT + 1); e += 512) (&sB[0][0])[e] = 0.0;
+  for (int e = tid; e < kDuboT * kDuboLD; e += 512) {
+    (&sX[0][0])[e] = 0.0;
+    (&sY[0][0])[e] = 0.0;
+  }
+  if (tid < kDuboT) {
+    sm[tid] = 0.0;
+    sv[tid] = 0.0;
+  }
+  const int p0 = g * kDuboS, p1 = p0 + kDuboS < P ? p0 + kDuboS : P;
+  for (int p = p0; p < p1; ++p) {
+    __syncthreads();  // the previous subject's readers are done (and the zero fill is visible)
+    const double* ib = iB + ((int64_t)l * P + p) * TT;
+    const double* k0 = K0st + ((int64_t)l * P + p) * TT;
+    for (int e = tid; e < T * T; e += 512) {
+      const double b = ib[e];
+      sB[e / T][e % T] = b;
+      s_bk0 += b * k0[e];
+    }
+    const double* xp = X + ((int64_t)l * N + (int64_t)p * T) * M;
+    for (int e = tid; e < T * M; e += 512) sX[e / M][e % M] = xp[e];
+    if (tid < T) {
+      const int64_t q = ((int64_t)p * T + tid) * L + l;
+      const double lv = logv[q];
+      sm[tid] = mu[q];
+      sv[tid] = exp(lv);
+      s_lv += lv;
+    }
+    if (tid == 0) s_ldb += ldB[(int64_t)l * P + p];
+    __syncthreads();
+    for (int e = tid; e < T * T; e += 512) {
+      const int i = e / T, j = e % T;
+      const double b = sB[i][j];
+      s_mbm += sm[i] * b * sm[j];
+      if (i == j) s_dv += b * sv[i];
+    }
+    // iBK_p = iB_p X_p: tT x tM tiles over the 8 waves
+    double* yp = iBK + ((int64_t)l * N + (int64_t)p * T) * M;
+    for (int tt = wv; tt < tT * tM; tt += 8) {
+      const int r0 = (tt / tM) << 4, c0 = (tt % tM) << 4;
+      bi_f64x4 acc = {0.0, 0.0, 0.0, 0.0};
+      for (int kk = 0; kk < T4; kk += 4)
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(sB[r0 + li][kk + lk], sX[kk + lk][c0 + li], acc, 0, 0, 0);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int i = r0 + lk + 4 * r, j = c0 + li;
+        sY[i][j] = acc[r];
+        if (i < T && j < M) yp[(int64_t)i * M + j] = acc[r];
+      }
+    }
+    __syncthreads();
+    if (tid < M) {
+      double q = 0.0;
+      for (int r = 0; r < T; ++r) q += sY[r][tid] * sm[r];
+      pj += q;
+    }
+#pragma unroll
+    for (int k = 0; k < kDuboTPW; ++k) {
+      if (on[k]) {
+        const int ci = (ti[k] << 4) + li, cj = (tj[k] << 4) + li;
+        for (int kk = 0; kk < T4; kk += 4) {
+          const double yb = sY[kk + lk][cj];
+          Qa[k] = __builtin_amdgcn_mfma_f64_16x16x4f64(sX[kk + lk][ci], yb, Qa[k], 0, 0, 0);
+          Ra[k] = __builtin_amdgcn_mfma_f64_16x16x4f64(sv[kk + lk] * sY[kk + lk][ci], yb, Ra[k], 0, 0, 0);
+        }
+      }
+    }
+  }
+  double* pp = part + ((int64_t)l * G + g) * pstride;
+#pragma unroll
+  for (int k = 0; k < kDuboTPW; ++k) {
+    if (on[k]) {
+      const int t = wv + 8 * k;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        pp[((int64_t)t * 4 + r) * 64 + lane] = Qa[k][r];
+        pp[((int64_t)(nt + t) * 4 + r) * 64 + lane] = Ra[k][r];
+      }
+    }
+  }
+  double* pv = pp + (int64_t)2 * nt * 256;
+  if (tid < 128) pv[tid] = pj;
+  const double vals[5] = {s_mbm, s_dv, s_bk0, s_lv, s_ldb};
+#pragma unroll
+  for (int q = 0; q < 5; ++q) {
+    const double v = block_sum<512>(vals[q], red);
+    if (tid == 0) pv[128 + q] = v;
+  }
+}
+
+// The groups' partials in group order: grid (2 nt + 1, L), 256 threads.  Blocks [0, nt): a tile of Q, [nt, 2 nt):
+// of R (mirrored into the upper triangle; a diagonal tile holds both of its halves itself), the last: p, scalars.
+__global__ __launch_bounds__(256) void dubo_reduce_kernel(int M, int G, int nt, int64_t pstride,
+                                                          const double* __restrict__ part, double* __restrict__ Q,
+                                                          double* __restrict__ R, double* __restrict__ p,
+                                                          double* __restrict__ scal) {
+  const int b = blockIdx.x, l = blockIdx.y, tid = threadIdx.x;
+  const double* pl = part + (int64_t)l * G * pstride;
+  if (b < 2 * nt) {
+    double sum = 0.0;
+    for (int g = 0; g < G; ++g) sum += pl[g * pstride + (int64_t)b * 256 + tid];
+    const int t = b < nt ? b : b - nt, r = tid >> 6, lane = tid & 63;
+    int ti, tj;
+    dubo_tile(t, ti, tj);
+    const int i = (ti << 4) + (lane >> 4) + 4 * r, j = (tj << 4) + (lane & 15);
+    if (i < M && j < M) {
+      double* o = (b < nt ? Q : R) + (int64_t)l * M * M;
+      o[(int64_t)i * M + j] = sum;
+      if (ti != tj) o[(int64_t)j * M + i] = sum;
+    }
+  } else if (tid < 128 + 5) {
+    double sum = 0.0;
+    for (int g = 0; g < G; ++g) sum += pl[g * pstride + (int64_t)2 * nt * 256 + tid];
+    if (tid < 128) {
+      if (tid < M) p[(int64_t)l * M + tid] = sum;
+    } else {
+      scal[(int64_t)l * kDuboScal + tid - 128] = sum;
+    }
+  }
+}
+
+// the large-T route's scalar sums, one workgroup per dim: scal[l] = m.s, diag(iB).v, iB.K0, sum logv, sum log|B_p|
+__global__ __launch_bounds__(256) void dubo_scal_kernel(int P, int T, int L, const double* __restrict__ mu,
+                                                        const double* __restrict__ logv,
+                                                        const double* __restrict__ s, const double* __restrict__ iB,
+                                                        const double* __restrict__ K0st,
+                                                        const double* __restrict__ ldB, double* __restrict__ scal) {
+  __shared__ double red[4];
+  const int l = blockIdx.x, tid = threadIdx.x;
+  const int64_t N = (int64_t)P * T, TT = (int64_t)P * T * T;
+  double v0 = 0, v1 = 0, v2 = 0, v3 = 0, v4 = 0;
+  for (int64_t i = tid; i < N; i += 256) {
+    const int64_t p = i / T, q = i % T;
+    const double lv = logv[i * L + l];
+    v0 += mu[i * L + l] * s[l * N + i];
+    v1 += iB[l * TT + p * T * T + q * T + q] * exp(lv);
+    v3 += lv;
+  }
+  for (int64_t e = tid; e < TT; e += 256) v2 += iB[l * TT + e] * K0st[l * TT + e];
+  for (int p = tid; p < P; p += 256) v4 += ldB[(int64_t)l * P + p];
+  const double vals[5] = {v0, v1, v2, v3, v4};
+#pragma unroll
+  for (int q = 0; q < 5; ++q) {
+    const double v = block_sum<256>(vals[q], red);
+    if (tid == 0) scal[(int64_t)l * kDuboScal + q] = v;
+  }
+}
+
+// Y[l][i][:] = exp(logv[i][l]) X[l][i][:]   ([L,N,M])
+__global__ void dubo_rowscale_nm_kernel(int64_t N, int M, int L, const double* __restrict__ logv,
+                                        const double* __restrict__ X, double* __restrict__ Y) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (int64_t)L * N * M) return;
+  const int64_t l = e / (N * M), i = (e / M) % N;
+  Y[e] = exp(logv[i * L + l]) * X[e];
+}
+
+// W = 1/2 ((Kz + Q) + (Kz + Q)^T)
+__global__ void dubo_w_kernel(int L, int M, const double* __restrict__ Kz, const double* __restrict__ Q,
+                              double* __restrict__ W) {
+  const int64_t MM = (int64_t)M * M;
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= L * MM) return;
+  const int64_t b = (e / MM) * MM;
+  const int i = (int)((e % MM) / M), j = (int)(e % M);
+  const int64_t f = b + (int64_t)j * M + i;
+  W[e] = 0.5 * ((Kz[e] + Q[e]) + (Kz[f] + Q[f]));
+}
+
+// E = I - W Y with every dot product accumulated in double-double (two-product by fma, two-sum), rounded to
+// fp64 at the end, and Y1 = Y: the residual of the first inverse of W, for the one Newton step Y1 += Y E.
+// W = K0zz + Q has cond ~1e8..1e9 (K0zz's jitter), so Y = spd_inv_small(W) carries a forward error of ~1e-9
+// |Y|; the bound's W terms (sum iW.R, p.iW p) see it directly (2.3e-9 of the bound on the reference's golden
+// vector, whose own bound is 1e-9), while a residual formed in plain fp64 is as inexact as Y itself.
+__global__ void dubo_resid_kernel(int L, int M, const double* __restrict__ W, const double* __restrict__ Y,
+                                  double* __restrict__ E, double* __restrict__ Y1) {
+#pragma clang fp contract(off)  // the error-free transforms below need every product and sum rounded on its own
+  const int64_t MM = (int64_t)M * M;
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= L * MM) return;
+  const int64_t b = (e / MM) * MM;
+  const int i = (int)((e % MM) / M), j = (int)(e % M);
+  const double* wr = W + b + (int64_t)i * M;
+  const double* yc = Y + b + j;
+  double hi = (i == j) ? 1.0 : 0.0, lo = 0.0;
+  for (int k = 0; k < M; ++k) {
+    const double a = -wr[k], y = yc[(int64_t)k * M];
+    const double ph = a * y, pl = fma(a, y, -ph);  // a y = ph + pl exactly
+    const double s = hi + ph, bb = s - hi;
+    lo += ((hi - (s - bb)) + (ph - bb)) + pl;      // two-sum's error term + the product's
+    hi = s;
+  }
+  E[e] = hi + lo;
+  Y1[e] = Y[e];
+}
+
+// dubo[l] from the reduced sums, one workgroup per dim
+__global__ __launch_bounds__(256) void dubo_final_kernel(int M, double n_rows, const double* __restrict__ iW,
+                                                         const double* __restrict__ R, const double* __restrict__ Q,
+                                                         const double* __restrict__ iK, const double* __restrict__ p,
+                                                         const double* __restrict__ w,
+                                                         const double* __restrict__ scal,
+                                                         const double* __restrict__ ldK,
+                                                         const double* __restrict__ ldW, double* __restrict__ dubo) {
+  __shared__ double red[4];
+  const int l = blockIdx.x, tid = threadIdx.x;
+  const int64_t MM = (int64_t)M * M;
+  double a = 0, b = 0, c = 0;
+  for (int64_t e = tid; e < MM; e += 256) {
+    a += iW[l * MM + e] * R[l * MM + e];
+    b += Q[l * MM + e] * iK[l * MM + e];
+  }
+  for (int i = tid; i < M; i += 256) c += p[(int64_t)l * M + i] * w[(int64_t)l * M + i];
+  a = block_sum<256>(a, red);
+  b = block_sum<256>(b, red);
+  c = block_sum<256>(c, red);
+  if (tid == 0) {
+    const double* sc = scal + (int64_t)l * kDuboScal;
+    dubo[l] = 0.5 * ((sc[1] - a) + (sc[0] - c) - n_rows + (-ldK[l] + sc[4] + ldW[l]) - sc[3] + (sc[2] - b));
+  }
+}
+
+// info[l]: first failure among Kz[l] (10000 + col), B_{l,p} (20000 + col), W[l] (30000 + col)
+__global__ void dubo_info_kernel(int L, int P, const int32_t* __restrict__ w, int32_t* __restrict__ info) {
+  const int l = blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= L) return;
+  int v = 0;
+  if (w[l]) v = 10000 + w[l];
+  for (int p = 0; p < P && !v; ++p)
+    if (w[L + (int64_t)l * P + p]) v = 20000 + w[L + (int64_t)l * P + p];
+  if (!v && w[L + (int64_t)L * P + l]) v = 30000 + w[L + (int64_t)L * P + l];
+  info[l] = v;
+}
+
+// a = s - y;  dmu[i][l] = g_l a
+__global__ void dubo_a_kernel(int64_t N, int L, const double* __restrict__ g, const double* __restrict__ s,
+                              const double* __restrict__ y, double* __restrict__ a, double* __restrict__ dmu) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= N * L) return;
+  const int64_t l = e / N, i = e % N;
+  const double v = s[e] - y[e];
+  a[e] = v;
+  dmu[i * L + l] = g[l] * v;
+}
+
+// dlogv[i][l] = g_l / 2 ((iB_ii - sum_j U_ij iBK_ij) v_i - 1): one wave per row
+__global__ __launch_bounds__(256) void dubo_dlogv_kernel(int P, int T, int M, int L, const double* __restrict__ g,
+                                                         const double* __restrict__ U,
+                                                         const double* __restrict__ iBK,
+                                                         const double* __restrict__ iB,
+                                                         const double* __restrict__ logv,
+                                                         double* __restrict__ dlogv) {
+  const int64_t N = (int64_t)P * T;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= N * L) return;
+  const int64_t l = row / N, i = row % N, p = i / T, q = i % T;
+  double sum = 0.0;
+  for (int j = lane; j < M; j += 64) sum += U[row * M + j] * iBK[row * M + j];
+  sum = wave_sum(sum);
+  if (lane == 0) {
+    const double d = iB[((l * P + p) * T + q) * T + q];
+    dlogv[i * L + l] = 0.5 * g[l] * ((d - sum) * exp(logv[i * L + l]) - 1.0);
+  }
+}
+
+// tNM = iBK + UR - F
+__global__ void dubo_sum3_kernel(int64_t n, const double* __restrict__ iBK, const double* __restrict__ UR,
+                                 const double* __restrict__ F, double* __restrict__ out) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < n) out[e] = iBK[e] + UR[e] - F[e];
+}
+
+// dX = g_l (dX - Z - a w^T);  Z <- U - Z;  UR <- UR - 2 F
+__global__ void dubo_dx_kernel(int64_t N, int M, int L, const double* __restrict__ g, const double* __restrict__ a,
+                               const double* __restrict__ w, const double* __restrict__ U,
+                               const double* __restrict__ F, double* __restrict__ Z, double* __restrict__ UR,
+                               double* __restrict__ dX) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (int64_t)L * N * M) return;
+  const int64_t l = e / (N * M), i = (e / M) % N, j = e % M;
+  const double z = Z[e];
+  dX[e] = g[l] * (dX[e] - z - a[l * N + i] * w[l * M + j]);
+  Z[e] = U[e] - z;
+  UR[e] = UR[e] - 2.0 * F[e];
+}
+
+// dKz = g_l (-1/2 (iK - iW - iW R iW - w w^T) + 1/2 iK Q iK)
+__global__ void dubo_dkz_kernel(int L, int M, const double* __restrict__ g, const double* __restrict__ iK,
+                                const double* __restrict__ iW, const double* __restrict__ iWRiW,
+                                const double* __restrict__ w, const double* __restrict__ iKQiK,
+                                double* __restrict__ dKz) {
+  const int64_t MM = (int64_t)M * M;
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= L * MM) return;
+  const int64_t l = e / MM;
+  const int i = (int)((e % MM) / M), j = (int)(e % M);
+  dKz[e] = 0.5 * g[l] * (iW[e] + iWRiW[e] + w[l * M + i] * w[l * M + j] - iK[e] + iKQiK[e]);
+}
+
+// VB[l,p][i][j] = v_{l,p,i} iB[l,p][i][j]
+__global__ void dubo_rowscale_tt_kernel(int P, int T, int L, const double* __restrict__ logv,
+                                        const double* __restrict__ iB, double* __restrict__ VB) {
+  const int64_t TT = (int64_t)T * T;
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (int64_t)L * P * TT) return;
+  const int64_t lp = e / TT, l = lp / P, p = lp % P;
+  const int i = (int)((e % TT) / T);
+  VB[e] = exp(logv[(p * T + i) * L + l]) * iB[e];
+}
+
+// GB = g_l / 2 (iB - iBDiB - iBK0iB - a a^T - GB);  GK0 = g_l / 2 iB
+__global__ void dubo_gb_kernel(int P, int T, int L, const double* __restrict__ g, const double* __restrict__ iB,
+                               const double* __restrict__ a, const double* __restrict__ iBDiB,
+                               const double* __restrict__ iBK0iB, double* __restrict__ GB,
+                               double* __restrict__ GK0) {
+  const int64_t TT = (int64_t)T * T, N = (int64_t)P * T;
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (int64_t)L * P * TT) return;
+  const int64_t lp = e / TT, l = lp / P, p = lp % P;
+  const int i = (int)((e % TT) / T), j = (int)(e % T);
+  const double h = 0.5 * g[l];
+  const double ai = a[l * N + p * T + i], aj = a[l * N + p * T + j];
+  GB[e] = h * (iB[e] - iBDiB[e] - iBK0iB[e] - ai * aj - GB[e]);
+  GK0[e] = h * iB[e];
+}
+
+int dubo_check(const lvae_kernel_spec* s0, const lvae_kernel_spec* s1, const lvae_dubo_dims* d) {
+  if (!s0 || !spec_bucket(s0)) return -1;
+  if (!s1 || !spec_bucket(s1)) return -2;
+  if (!d || d->L < 1 || d->M < 1 || d->M > 128 || d->P < 1 || d->T < 1 || d->T > 128 || d->Q < 1) return -3;
+  return 0;
+}
+
+}  // namespace
+}  // namespace lvae
+
+using namespace lvae;
+
+extern "C" {
+
+size_t lvae_dubo_workspace_size(const lvae_dubo_dims* d) { return DWs(nullptr, *d).bytes; }
+
+int lvae_dubo_fwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, const lvae_dubo_dims* dp,
+                      const double* x, const double* z, const double* mu, const double* logv, const double* params0,
+                      const double* params1, const double* noise, double* dubo, int32_t* info, void* workspace,
+                      void* stream) {
+  LVAE_TRY(dubo_check(spec0, spec1, dp));
+  if (!workspace || ((uintptr_t)workspace & 255)) return -4;
+  hipStream_t st = (hipStream_t)stream;
+  const lvae_dubo_dims& d = *dp;
+  const int L = d.L, M = d.M, P = d.P, T = d.T, Q = d.Q, N = P * T;
+  const int64_t MM = (int64_t)M * M, TT = (int64_t)T * T, NM = (int64_t)N * M;
+  DWs w((char*)workspace, d);
+  // Grams
+  dubo_fill_kernel<<<blocks(L), 256, 0, st>>>(w.epsv, L, d.eps);
+  const lvae_xview xv{x, 0, 0, Q}, zv{z, 0, (int64_t)M * Q, Q}, xs{x, (int64_t)T * Q, 0, Q};
+  const lvae_kernel_spec* specs[2] = {spec0, spec1};
+  const GramFwdJob jobs[4] = {{0, 1, N, M, 0, 0, 0, xv, zv, params0, nullptr, w.X, 0, NM, M},
+                              {0, 1, M, M, 0, 0, 0, zv, zv, params0, w.epsv, w.Kz, 0, MM, M},
+                              {0, P, T, T, 0, 0, 0, xs, xs, params0, nullptr, w.K0st, TT, P * TT, T},
+                              {1, P, T, T, 0, 0, 0, xs, xs, params1, noise, w.Bst, TT, P * TT, T}};
+  LVAE_TRY(gram_multi_f64(specs, jobs, 4, L, st));
+  LVAE_TRY(spd_inv_small_f64(M, L, w.Kz, MM, w.iK, MM, w.ldK, w.info, st));
+  LVAE_TRY(spd_inv_small_f64(T, L * P, w.Bst, TT, w.iB, TT, w.ldB, w.info + L, st));
+  if (T <= kDuboT) {
+    const int G = dubo_groups(P), nt = dubo_tiles(M);
+    const int64_t ps = dubo_part_stride(M);
+    dubo_subject_kernel<<<dim3(G, L), 512, 0, st>>>(M, P, T, L, nt, ps, w.X, w.iB, w.K0st, w.ldB, mu, logv, w.iBK,
+                                                   w.part);
+    dubo_reduce_kernel<<<dim3(2 * nt + 1, L), 256, 0, st>>>(M, G, nt, ps, w.part, w.Q, w.R, w.p, w.scal);
+  } else {
+    // large T: iBK, Q, R = iBK^T (D iBK), p = iBK^T m, s = iB m as batched products
+    LVAE_TRY(gemm_small_f64(0, 0, T, M, T, 1.0, w.iB, T, P * TT, TT, w.X, M, NM, (int64_t)T * M, 0.0, w.iBK, M, NM,
+                            (int64_t)T * M, L, P, st));
+    LVAE_TRY(gemm_small_f64(1, 0, M, M, N, 1.0, w.X, M, NM, 0, w.iBK, M, NM, 0, 0.0, w.Q, M, MM, 0, L, 1, st));
+    dubo_rowscale_nm_kernel<<<blocks((int64_t)L * NM), 256, 0, st>>>(N, M, L, logv, w.iBK, w.tNM);
+    LVAE_TRY(gemm_small_f64(1, 0, M, M, N, 1.0, w.iBK, M, NM, 0, w.tNM, M, NM, 0, 0.0, w.R, M, MM, 0, L, 1, st));
+    LVAE_TRY(gemm_small_f64(1, 0, M, 1, N, 1.0, w.iBK, M, NM, 0, mu, L, 1, 0, 0.0, w.p, 1, M, 0, L, 1, st));
+    LVAE_TRY(gemm_small_f64(0, 0, T, 1, T, 1.0, w.iB, T, P * TT, TT, mu, L, 1, (int64_t)T * L, 0.0, w.s, 1, N, T, L, P,
+                            st));
+    dubo_scal_kernel<<<L, 256, 0, st>>>(P, T, L, mu, logv, w.s, w.iB, w.K0st, w.ldB, w.scal);
+  }
+  dubo_w_kernel<<<blocks(L * MM), 256, 0, st>>>(L, M, w.Kz, w.Q, w.W);
+  // iW = Y + Y (I - W Y), the residual in double-double (dubo_resid_kernel)
+  LVAE_TRY(spd_inv_small_f64(M, L, w.W, MM, w.iW0, MM, w.ldW, w.info + L + L * P, st));
+  dubo_resid_kernel<<<blocks(L * MM), 256, 0, st>>>(L, M, w.W, w.iW0, w.E, w.iW);
+  LVAE_TRY(gemm_small_f64(0, 0, M, M, M, 1.0, w.iW0, M, MM, 0, w.E, M, MM, 0, 1.0, w.iW, M, MM, 0, L, 1, st));
+  LVAE_TRY(gemm_small_f64(0, 0, M, 1, M, 1.0, w.iW, M, MM, 0, w.p, 1, M, 0, 0.0, w.w, 1, M, 0, L, 1, st));
+  dubo_final_kernel<<<L, 256, 0, st>>>(M, (double)N, w.iW, w.R, w.Q, w.iK, w.p, w.w, w.scal, w.ldK, w.ldW, dubo);
+  if (info) dubo_info_kernel<<<blocks(L), 256, 0, st>>>(L, P, w.info, info);
+  LVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+int lvae_dubo_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, const lvae_dubo_dims* dp,
+                      const double* x, const double* z, const double* mu, const double* logv, const double* params0,
+                      const double* params1, const double* noise, const double* gdubo, double* dmu, double* dlogv,
+                      double* dparams0, double* dparams1, double* dnoise, void* workspace, void* stream) {
+  (void)noise;
+  LVAE_TRY(dubo_check(spec0, spec1, dp));
+  if (!workspace || ((uintptr_t)workspace & 255)) return -4;
+  hipStream_t st = (hipStream_t)stream;
+  const lvae_dubo_dims& d = *dp;
+  const int L = d.L, M = d.M, P = d.P, T = d.T, Q = d.Q, N = P * T;
+  const int64_t MM = (int64_t)M * M, TT = (int64_t)T * T, NM = (int64_t)N * M, LTT = (int64_t)L * P * TT;
+  const int64_t TM = (int64_t)T * M;
+  DWs w((char*)workspace, d);
+  // U = iBK iW ; s = iB m ; y = U p ; a = s - y -> dmu ; dlogv
+  LVAE_TRY(gemm_small_f64(0, 0, N, M, M, 1.0, w.iBK, M, NM, 0, w.iW, M, MM, 0, 0.0, w.U, M, NM, 0, L, 1, st));
+  LVAE_TRY(gemm_small_f64(0, 0, T, 1, T, 1.0, w.iB, T, P * TT, TT, mu, L, 1, (int64_t)T * L, 0.0, w.s, 1, N, T, L, P,
+                          st));
+  LVAE_TRY(gemm_small_f64(0, 0, N, 1, M, 1.0, w.U, M, NM, 0, w.p, 1, M, 0, 0.0, w.y, 1, N, 0, L, 1, st));
+  dubo_a_kernel<<<blocks((int64_t)N * L), 256, 0, st>>>(N, L, gdubo, w.s, w.y, w.a, dmu);
+  dubo_dlogv_kernel<<<cdiv((int64_t)N * L, 4), 256, 0, st>>>(P, T, M, L, gdubo, w.U, w.iBK, w.iB, logv, dlogv);
+  // UR = U R ; F = iB (D iBK) ; Z = iBK iK ; dX = (iBK + UR - F) iW, then g (dX - Z - a w^T)
+  LVAE_TRY(gemm_small_f64(0, 0, N, M, M, 1.0, w.U, M, NM, 0, w.R, M, MM, 0, 0.0, w.UR, M, NM, 0, L, 1, st));
+  dubo_rowscale_nm_kernel<<<blocks((int64_t)L * NM), 256, 0, st>>>(N, M, L, logv, w.iBK, w.tNM);
+  LVAE_TRY(gemm_small_f64(0, 0, T, M, T, 1.0, w.iB, T, P * TT, TT, w.tNM, M, NM, TM, 0.0, w.F, M, NM, TM, L, P, st));
+  LVAE_TRY(gemm_small_f64(0, 0, N, M, M, 1.0, w.iBK, M, NM, 0, w.iK, M, MM, 0, 0.0, w.Z, M, NM, 0, L, 1, st));
+  dubo_sum3_kernel<<<blocks((int64_t)L * NM), 256, 0, st>>>((int64_t)L * NM, w.iBK, w.UR, w.F, w.tNM);
+  LVAE_TRY(gemm_small_f64(0, 0, N, M, M, 1.0, w.tNM, M, NM, 0, w.iW, M, MM, 0, 0.0, w.dX, M, NM, 0, L, 1, st));
+  dubo_dx_kernel<<<blocks((int64_t)L * NM), 256, 0, st>>>(N, M, L, gdubo, w.a, w.w, w.U, w.F, w.Z, w.UR, w.dX);
+  // dKz
+  LVAE_TRY(gemm_small_f64(0, 0, M, M, M, 1.0, w.iW, M, MM, 0, w.R, M, MM, 0, 0.0, w.iWR, M, MM, 0, L, 1, st));
+  LVAE_TRY(gemm_small_f64(0, 0, M, M, M, 1.0, w.iWR, M, MM, 0, w.iW, M, MM, 0, 0.0, w.iWRiW, M, MM, 0, L, 1, st));
+  LVAE_TRY(gemm_small_f64(0, 0, M, M, M, 1.0, w.iK, M, MM, 0, w.Q, M, MM, 0, 0.0, w.iKQ, M, MM, 0, L, 1, st));
+  LVAE_TRY(gemm_small_f64(0, 0, M, M, M, 1.0, w.iKQ, M, MM, 0, w.iK, M, MM, 0, 0.0, w.iKQiK, M, MM, 0, L, 1, st));
+  dubo_dkz_kernel<<<blocks(L * MM), 256, 0, st>>>(L, M, gdubo, w.iK, w.iW, w.iWRiW, w.w, w.iKQiK, w.dKz);
+  // dB_p, dK0_p (Z now holds U - Z, UR holds UR - 2 F)
+  dubo_rowscale_tt_kernel<<<blocks(LTT), 256, 0, st>>>(P, T, L, logv, w.iB, w.VB);
+  LVAE_TRY(gemm_small_f64(0, 0, T, T, T, 1.0, w.iB, T, P * TT, TT, w.VB, T, P * TT, TT, 0.0, w.iBDiB, T, P * TT, TT,
+                          L, P, st));
+  LVAE_TRY(gemm_small_f64(0, 0, T, T, T, 1.0, w.K0st, T, P * TT, TT, w.iB, T, P * TT, TT, 0.0, w.K0iB, T, P * TT, TT,
+                          L, P, st));
+  LVAE_TRY(gemm_small_f64(0, 0, T, T, T, 1.0, w.iB, T, P * TT, TT, w.K0iB, T, P * TT, TT, 0.0, w.iBK0iB, T, P * TT,
+                          TT, L, P, st));
+  LVAE_TRY(gemm_small_f64(0, 1, T, T, M, 1.0, w.Z, M, NM, TM, w.iBK, M, NM, TM, 0.0, w.GB, T, P * TT, TT, L, P, st));
+  LVAE_TRY(gemm_small_f64(0, 1, T, T, M, 1.0, w.UR, M, NM, TM, w.U, M, NM, TM, 1.0, w.GB, T, P * TT, TT, L, P, st));
+  dubo_gb_kernel<<<blocks(LTT), 256, 0, st>>>(P, T, L, gdubo, w.iB, w.a, w.iBDiB, w.iBK0iB, w.GB, w.GK0);
+  // hyper-parameter gradients through the four Grams
+  (void)zero_async(dparams0, sizeof(double) * L * spec0->n_params, st);
+  (void)zero_async(dparams1, sizeof(double) * L * spec1->n_params, st);
+  if (dnoise) (void)zero_async(dnoise, sizeof(double) * L, st);
+  const lvae_xview xv{x, 0, 0, Q}, zv{z, 0, (int64_t)M * Q, Q}, xs{x, (int64_t)T * Q, 0, Q};
+  const GramBwdJob jobs[4] = {{0, xv, zv, 1, N, M, 0, params0, w.dX, 0, NM, M, dparams0, nullptr, 0, 0},
+                              {0, zv, zv, 1, M, M, 0, params0, w.dKz, 0, MM, M, dparams0, nullptr, 0, 0},
+                              {0, xs, xs, P, T, T, 0, params0, w.GK0, TT, P * TT, T, dparams0, nullptr, 0, 0},
+                              {1, xs, xs, P, T, T, 0, params1, w.GB, TT, P * TT, T, dparams1, dnoise, 0, 0}};
+  const lvae_kernel_spec* specs[2] = {spec0, spec1};
+  LVAE_TRY(gram_bwd_multi_f64(specs, jobs, 4, L, w.gpart, st));
+  LVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // extern "C"

@@ -44,6 +44,11 @@ class HensmanDims(ctypes.Structure):
                 ("seg_len", ctypes.c_void_p), ("n_total", ctypes.c_double)]
 
 
+class DuboDims(ctypes.Structure):
+    _fields_ = [("L", ctypes.c_int32), ("M", ctypes.c_int32), ("P", ctypes.c_int32), ("T", ctypes.c_int32),
+                ("Q", ctypes.c_int32), ("eps", ctypes.c_double)]
+
+
 def make_spec(components):
     """components: list of lists of (kind, dim) factors, in parameter order (see oracle header).
     Returns (KernelSpec, n_params)."""
@@ -73,6 +78,7 @@ def make_spec(components):
 _VP, _I32, _I64, _D, _SZ = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_size_t
 _SPEC = ctypes.POINTER(KernelSpec)
 _DIMS = ctypes.POINTER(HensmanDims)
+_DDIMS = ctypes.POINTER(DuboDims)
 
 # name -> (restype, argtypes); every symbol include/lvae_hip.h declares
 SIGNATURES = {
@@ -120,6 +126,10 @@ SIGNATURES = {
     "lvae_natgrad_workspace_size": (_SZ, [_I32, _I32]),
     "lvae_natgrad_update_f64": (_I32, [_I32, _I32, _VP, _VP, _VP, _VP, _D, _VP, _VP, _VP, _VP]),
     "lvae_hensman_iH_offset": (_SZ, [_DIMS]),
+    "lvae_dubo_workspace_size": (_SZ, [_DDIMS]),
+    "lvae_dubo_fwd_f64": (_I32, [_SPEC, _SPEC, _DDIMS, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "lvae_dubo_bwd_f64": (_I32, [_SPEC, _SPEC, _DDIMS, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                 _VP, _VP, _VP]),
     "lvae_relu_maxpool2_fwd_f32": (_I32, [_VP, _I64, _I32, _I32, _VP, _VP, _VP]),
     "lvae_relu_maxpool2_bwd_f32": (_I32, [_VP, _VP, _VP, _I64, _I32, _I32, _VP, _VP]),
     "lvae_relu_maxpool2_bias_workspace_size": (_SZ, [_I32, _I32]),

@@ -1,13 +1,16 @@
 """Full-batch GP-approximation bounds of one latent dim: ``elbo`` (elbo_functions.py:36-84),
-``deviance_upper_bound`` (DUBO, elbo_functions.py:86-142) and the all-dims ``validation_dubo``
-(validation.py:8-68).  Same signatures and values as the reference.
+``deviance_upper_bound`` (DUBO, elbo_functions.py:86-142), and of all latent dims at once:
+``deviance_upper_bound_batched`` and ``validation_dubo`` (validation.py:8-68).  Same signatures and values as
+the reference.
 
 The additive-kernel Grams and every SPD factorisation (K0zz, the per-subject B_p, the M x M
 Woodbury matrix W) run in the HIP library: Grams through the differentiable ``covar_module(x1,
 x2).evaluate()``, the factorisations through ``spd_inverse`` (lvae_spd_inv_small_f64, one
 workgroup per matrix, returning A^-1 and log|A|).  The remaining M x M / T x M products are plain
 library GEMMs (rocBLAS via torch.matmul); autograd composes the gradients (d A^-1 = -A^-1 dA A^-1,
-d log|A| = tr(A^-1 dA)).
+d log|A| = tr(A^-1 dA)).  The all-dims DUBO is instead one batched HIP forward and one analytic HIP adjoint
+(lvae_dubo_fwd_f64 / lvae_dubo_bwd_f64, csrc/dubo.hip: a fused pass over the subjects); the per-dim functions
+stay as they are, as its baseline and comparison.
 """
 import math
 
@@ -105,44 +108,91 @@ def deviance_upper_bound(covar_module0, covar_module1, likelihood, train_xt, m, 
     return 0.5 * ((tr_iB_D - tr2) + _quad(c, m, P, T) - P * T + c["logdet"] - log_v.sum() + c["tr"])
 
 
+class _DuboFn(torch.autograd.Function):
+    """dubo [L] of all latent dims in one batched HIP pass (lvae_dubo_fwd_f64) with its analytic adjoint
+    (lvae_dubo_bwd_f64); z is not differentiated."""
+
+    @staticmethod
+    def forward(ctx, params0, params1, noise, mu, logv, x, z, spec0, spec1, dims):
+        lib = _lib.lib()
+        dev = mu.device
+        f64 = lambda t: t.detach().to(torch.float64).contiguous()
+        p0, p1, nz, mu64, lv64, x64, z64 = f64(params0), f64(params1), f64(noise).reshape(-1), f64(mu), f64(logv), \
+            f64(x), f64(z)
+        ws = torch.empty(int(lib.lvae_dubo_workspace_size(dims)), dtype=torch.uint8, device=dev)
+        dubo = torch.empty(dims.L, dtype=torch.float64, device=dev)
+        info = torch.empty(dims.L, dtype=torch.int32, device=dev)
+        rc = lib.lvae_dubo_fwd_f64(spec0, spec1, dims, _lib.ptr(x64), _lib.ptr(z64), _lib.ptr(mu64), _lib.ptr(lv64),
+                                   _lib.ptr(p0), _lib.ptr(p1), _lib.ptr(nz), _lib.ptr(dubo), _lib.ptr(info),
+                                   _lib.ptr(ws), _lib.stream_ptr())
+        _lib.check(rc, "dubo_fwd")
+        _check_info(info, "deviance_upper_bound cholesky (10000+col: K0zz, 20000+col: B_st, 30000+col: W)")
+        ctx.save_for_backward(p0, p1, nz, mu64, lv64, x64, z64, ws)
+        ctx.spec0, ctx.spec1, ctx.dims = spec0, spec1, dims
+        ctx.dtypes = (params0.dtype, params1.dtype, noise.dtype, noise.shape, mu.dtype, logv.dtype)
+        return dubo
+
+    @staticmethod
+    def backward(ctx, gdubo):
+        lib = _lib.lib()
+        p0, p1, nz, mu64, lv64, x64, z64, ws = ctx.saved_tensors
+        g = gdubo.detach().to(torch.float64).reshape(-1).contiguous()
+        dmu, dlv = torch.empty_like(mu64), torch.empty_like(lv64)
+        dp0, dp1, dnz = torch.empty_like(p0), torch.empty_like(p1), torch.empty_like(nz)
+        rc = lib.lvae_dubo_bwd_f64(ctx.spec0, ctx.spec1, ctx.dims, _lib.ptr(x64), _lib.ptr(z64), _lib.ptr(mu64),
+                                   _lib.ptr(lv64), _lib.ptr(p0), _lib.ptr(p1), _lib.ptr(nz), _lib.ptr(g),
+                                   _lib.ptr(dmu), _lib.ptr(dlv), _lib.ptr(dp0), _lib.ptr(dp1), _lib.ptr(dnz),
+                                   _lib.ptr(ws), _lib.stream_ptr())
+        _lib.check(rc, "dubo_bwd")
+        t0, t1, tn, nshape, tmu, tlv = ctx.dtypes
+        return (dp0.to(t0), dp1.to(t1), dnz.to(tn).reshape(nshape), dmu.to(tmu), dlv.to(tlv), None, None, None,
+                None, None)
+
+
+def _dubo_noise(likelihoods, L):
+    """[L] noise of a batched likelihood (noise_covar.noise [L, 1] or [1]) or of a list of per-dim ones."""
+    if isinstance(likelihoods, (list, tuple, torch.nn.ModuleList)):
+        return torch.cat([lk.noise_covar.noise.reshape(-1)[:1] for lk in likelihoods]).reshape(L)
+    nz = likelihoods.noise_covar.noise.reshape(-1)
+    return nz.expand(L) if nz.numel() == 1 else nz.reshape(L)
+
+
+def deviance_upper_bound_batched(latent_dim, covar_module0, covar_module1, likelihoods, train_xt, m, log_v, z, P, T,
+                                 eps):
+    """The DUBO of every latent dim, [L] fp64, from one batched HIP forward (and one batched adjoint):
+    ``deviance_upper_bound`` for dim l on (m[:, l], log_v[:, l]).  covar_module0 / covar_module1: batched
+    modules or per-dim lists; likelihoods: a batched likelihood or a per-dim list; z: [L, M, Q], [M, Q]
+    (shared) or a per-dim list of [M, Q].  Gradients flow to m, log_v [N, L], the kernels' raw parameters
+    and the noise; z is not differentiated."""
+    from .elbo import _stack_modules
+    L = int(latent_dim)
+    spec0, params0 = _stack_modules(covar_module0)
+    spec1, params1 = _stack_modules(covar_module1)
+    if params0.shape[0] == 1 and L > 1:
+        params0 = params0.expand(L, -1)
+    if params1.shape[0] == 1 and L > 1:
+        params1 = params1.expand(L, -1)
+    if params0.shape[0] != L or params1.shape[0] != L:
+        raise ValueError(f"kernel batches {params0.shape[0]}, {params1.shape[0]} != latent dims {L}")
+    if isinstance(z, (list, tuple)):
+        z = torch.stack([zi.reshape(zi.shape[-2], zi.shape[-1]) for zi in z], 0)
+    zz = z if z.dim() == 3 else z.unsqueeze(0).expand(L, -1, -1)
+    if zz.shape[0] != L:
+        raise ValueError(f"z has {zz.shape[0]} dims, expected {L}")
+    if train_xt.shape[0] != P * T:
+        raise ValueError(f"train_xt has {train_xt.shape[0]} rows, expected P*T = {P * T}")
+    if tuple(m.shape) != (P * T, L) or tuple(log_v.shape) != (P * T, L):
+        raise ValueError(f"m / log_v must be [{P * T}, {L}]")
+    noise = _dubo_noise(likelihoods, L).to(m.device)
+    dims = _lib.DuboDims(L, int(zz.shape[-2]), int(P), int(T), int(train_xt.shape[-1]), float(eps))
+    return _DuboFn.apply(params0, params1, noise, m, log_v, train_xt, zz, spec0, spec1, dims)
+
+
 def validation_dubo(latent_dim, covar_module0, covar_module1, likelihood, train_xt, m, log_v, z, P, T, eps):
     """Sum over the latent dims of the DUBO with batched kernels (validation.py:8-68); m / log_v
-    [N, L], z [L, M, Q].  Returns a [1] tensor like the reference."""
-    from .kernels import kernel_spec_and_params
-    spec0, p0 = kernel_spec_and_params(covar_module0)
-    spec1, p1 = kernel_spec_and_params(covar_module1)
+    [N, L], z [L, M, Q].  Returns a [1] tensor like the reference.  One batched call
+    (deviance_upper_bound_batched) for all dims."""
     L = int(latent_dim)
-    nz = likelihood.noise_covar.noise.reshape(-1)
-    total = torch.zeros(1, dtype=torch.float64, device=m.device)
-    for i in range(L):
-        k0 = _Fixed(spec0, p0[i:i + 1])
-        k1 = _Fixed(spec1, p1[i:i + 1])
-        lik = _Noise(nz[i if nz.numel() > 1 else 0])
-        total = total + deviance_upper_bound(k0, k1, lik, train_xt, m[:, i], log_v[:, i], z[i], P, T, eps)
-    return total
+    return deviance_upper_bound_batched(L, covar_module0, covar_module1, likelihood, train_xt, m, log_v, z, P, T,
+                                        eps).sum().reshape(1)
 
-
-class _Lazy:
-    def __init__(self, t):
-        self.t = t
-
-    def evaluate(self):
-        return self.t
-
-
-class _Fixed:
-    """One latent dim's slice of a batched kernel (spec + [1, P] params)."""
-
-    def __init__(self, spec, params):
-        self.spec, self.params = spec, params
-
-    def __call__(self, x1, x2):
-        from .kernels import gram
-        return _Lazy(gram(self.spec, self.params, x1, x2).reshape(*torch.broadcast_shapes(x1.shape[:-2], x2.shape[:-2]),
-                                                                  x1.shape[-2], x2.shape[-2]))
-
-
-class _Noise:
-    def __init__(self, v):
-        import types
-        self.noise_covar = types.SimpleNamespace(noise=v.reshape(1))

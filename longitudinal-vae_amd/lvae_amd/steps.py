@@ -2,6 +2,7 @@
 
 ClosedStep   : standard_training with type_KL='closed' (training.py:484-592)
 HensmanStep  : hensman_training batch body incl. the natural-gradient update (training.py:91-135)
+DuboStep     : standard_training with type_KL='GPapprox_closed' (training.py:499-575), full batch
 GraphedStep  : either step replayed as HIP graphs (torch.cuda.CUDAGraph is a hipGraph on ROCm)
 
 Both steps return detached device scalars; callers read them when they choose (the reference's
@@ -258,6 +259,57 @@ class HensmanStep:
                 with torch.no_grad():
                     self.m.copy_(m2.reshape(self.m.shape).to(self.m.dtype))
                     self.H.copy_(H2.to(self.H.dtype))
+
+    def __call__(self, img, mask, X, eps=None):
+        out = self.forward_backward(img, mask, X, eps)
+        self.communicate()
+        self.apply()
+        return out
+
+
+class DuboStep:
+    """standard_training's type_KL='GPapprox_closed' branch (training.py:499-575): encode, sample, decode and
+    loss, the DUBO of every latent dim from (mu, log_var) in one batched call, recon + weight * sum_l dubo_l / L
+    ('mse') or nll + sum_l dubo_l ('nll'), backward; ``apply`` is the optimiser step and the scale constraint.
+
+    k0 / k1 / likelihood: batched modules or per-dim lists; z: [L, M, Q], [M, Q] or a per-dim list; X: the full
+    batch's covariates [P*T, Q], subjects in blocks of T rows.  One stream, eager; capture into a HIP graph is
+    untested."""
+
+    def __init__(self, vae, k0, k1, likelihood, optimiser, z, T, weight=0.15, loss_function="mse", eps=1e-6,
+                 constrain_scales=True, grad_hook=None):
+        self.vae, self.k0, self.k1, self.lik, self.opt = vae, k0, k1, likelihood, optimiser
+        self.z, self.T = z, T
+        self.weight, self.loss_function, self.eps = weight, loss_function, eps
+        self.constrain_scales, self.grad_hook = constrain_scales, grad_hook
+
+    def forward_backward(self, img, mask, X, eps=None):
+        from .gpapprox import deviance_upper_bound_batched
+        self.opt.zero_grad(set_to_none=True)
+        recon, mu, log_var = self.vae(img, eps)
+        mse, nll = self.vae.loss_function(recon, img, mask)
+        recon_loss, nll_loss = mse.sum(), nll.sum()
+        L = mu.shape[1]
+        dubo = deviance_upper_bound_batched(L, self.k0, self.k1, self.lik, X, mu, log_var, self.z,
+                                            X.shape[0] // self.T, self.T, self.eps)
+        if self.loss_function == "mse":
+            gp = dubo.sum() / L
+            net = recon_loss + self.weight * gp
+        else:
+            gp = dubo.sum()
+            net = nll_loss + gp
+        net.backward()
+        return net.detach(), recon_loss.detach(), nll_loss.detach(), gp.detach()
+
+    def communicate(self):
+        if self.grad_hook is not None:
+            self.grad_hook()
+
+    def apply(self):
+        self.opt.step()
+        if self.constrain_scales:
+            for lk in (self.lik if isinstance(self.lik, (list, tuple, torch.nn.ModuleList)) else [self.lik]):
+                lk.noise = 1.0
 
     def __call__(self, img, mask, X, eps=None):
         out = self.forward_backward(img, mask, X, eps)
