@@ -414,6 +414,45 @@ int lvae_dubo_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spe
                       double* dmu, double* dlogv, double* dparams0, double* dparams1, double* dnoise,
                       void* workspace, void* stream);
 
+/* Full-batch sampled GP ELBO (type_KL 'GPapprox', elbo_functions.py:36-84) of all L latent dims and S samples of
+ * the latent at once, and its adjoint.  P subjects of T consecutive rows each (N = P T rows), M inducing points,
+ * Q covariates, S samples (1..16: the columns of one MFMA tile; a caller with more splits them over calls).
+ * Everything but the right-hand sides is shared by a dim's samples: the four Grams, K0zz^-1, B_p^-1 and W^-1 are
+ * formed once per dim.                                                                                   */
+typedef struct lvae_gp_elbo_dims {
+  int32_t L, M, P, T, Q, S;
+  double eps;              /* jitter on K0zz */
+} lvae_gp_elbo_dims;
+
+/* Reads *d unchecked (d must not be NULL; the size is only meaningful for dims that the calls below accept).
+ * Always a multiple of 256.                                                                             */
+size_t lvae_gp_elbo_workspace_size(const lvae_gp_elbo_dims* d);
+
+/* Forward: elbo [S, L], elbo[s][l] = the reference's elbo() of dim l on the sample y[s][:, l].  x [P*T, Q],
+ * z [L, M, Q], y [S, P*T, L] (fp64, row-major), params0 [L, P0], params1 [L, P1], noise [L].  info [L] (may be
+ * NULL): 0, or the first failed factorisation of dim l in the order K0zz (10000 + col), B_p (20000 + col, the
+ * first such subject), W = K0zz + K0zx B^-1 K0xz (30000 + col), col the 1-based failing column; elbo[:, l] and
+ * that dim's gradients then mean nothing, the other dims are unaffected.  Kernel launches only, on the caller's
+ * stream; nothing is allocated; no atomics: the same inputs give the same bits on every call and every device
+ * (the split of the subjects over workgroups depends on P alone).  T <= 32 runs the fused subject pass, larger
+ * T batched small products.  Row s of a call with S samples agrees with the S = 1 call on that sample to
+ * rounding, not bit for bit (the sample's MFMA column differs).
+ * Return codes of both calls, checked in this order before any launch (nothing is written): -1 / -2: spec0 /
+ * spec1 NULL or outside every template bucket; -3: d NULL, L < 1, M or T outside 1..128, P < 1, Q < 1 or S
+ * outside 1..16; -4: workspace NULL or not 256-byte aligned.  0 = ok.                                    */
+int lvae_gp_elbo_fwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, const lvae_gp_elbo_dims* d,
+                         const double* x, const double* z, const double* y, const double* params0,
+                         const double* params1, const double* noise, double* elbo, int32_t* info,
+                         void* workspace, void* stream);
+/* Backward given the cotangents gelbo [S, L] (device): dy [S, P*T, L]; dparams0 [L, P0], dparams1 [L, P1],
+ * dnoise [L] (may be NULL), summed over the dim's samples, each weighted by its own gelbo[s][l].  Outputs are
+ * OVERWRITTEN (whatever they held).  Runs on the workspace the forward left (it may be called again on it, with
+ * the same bits out).  z is not differentiated.                                                          */
+int lvae_gp_elbo_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, const lvae_gp_elbo_dims* d,
+                         const double* x, const double* z, const double* y, const double* params0,
+                         const double* params1, const double* noise, const double* gelbo, double* dy,
+                         double* dparams0, double* dparams1, double* dnoise, void* workspace, void* stream);
+
 /* ConvVAE encoder (VAE.py:44-50): y = max_pool2d(relu(x), 2, 2) over planes = N*C planes of H x W
  * (H, W even) fp32, idx = argmax byte (0..3, row-major in the window, first strict maximum);
  * backward gx = the pooled gradient routed to the argmax where y > 0, 0 elsewhere.            */

@@ -49,6 +49,11 @@ class DuboDims(ctypes.Structure):
                 ("Q", ctypes.c_int32), ("eps", ctypes.c_double)]
 
 
+class GpElboDims(ctypes.Structure):
+    _fields_ = [("L", ctypes.c_int32), ("M", ctypes.c_int32), ("P", ctypes.c_int32), ("T", ctypes.c_int32),
+                ("Q", ctypes.c_int32), ("S", ctypes.c_int32), ("eps", ctypes.c_double)]
+
+
 def make_spec(components):
     """components: list of lists of (kind, dim) factors, in parameter order (see oracle header).
     Returns (KernelSpec, n_params)."""
@@ -79,6 +84,7 @@ _VP, _I32, _I64, _D, _SZ = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctyp
 _SPEC = ctypes.POINTER(KernelSpec)
 _DIMS = ctypes.POINTER(HensmanDims)
 _DDIMS = ctypes.POINTER(DuboDims)
+_GDIMS = ctypes.POINTER(GpElboDims)
 
 # name -> (restype, argtypes); every symbol include/lvae_hip.h declares
 SIGNATURES = {
@@ -130,6 +136,10 @@ SIGNATURES = {
     "lvae_dubo_fwd_f64": (_I32, [_SPEC, _SPEC, _DDIMS, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "lvae_dubo_bwd_f64": (_I32, [_SPEC, _SPEC, _DDIMS, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                  _VP, _VP, _VP]),
+    "lvae_gp_elbo_workspace_size": (_SZ, [_GDIMS]),
+    "lvae_gp_elbo_fwd_f64": (_I32, [_SPEC, _SPEC, _GDIMS, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "lvae_gp_elbo_bwd_f64": (_I32, [_SPEC, _SPEC, _GDIMS, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                    _VP, _VP]),
     "lvae_relu_maxpool2_fwd_f32": (_I32, [_VP, _I64, _I32, _I32, _VP, _VP, _VP]),
     "lvae_relu_maxpool2_bwd_f32": (_I32, [_VP, _VP, _VP, _I64, _I32, _I32, _VP, _VP]),
     "lvae_relu_maxpool2_bias_workspace_size": (_SZ, [_I32, _I32]),

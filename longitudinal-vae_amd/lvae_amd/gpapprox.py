@@ -9,8 +9,9 @@ x2).evaluate()``, the factorisations through ``spd_inverse`` (lvae_spd_inv_small
 workgroup per matrix, returning A^-1 and log|A|).  The remaining M x M / T x M products are plain
 library GEMMs (rocBLAS via torch.matmul); autograd composes the gradients (d A^-1 = -A^-1 dA A^-1,
 d log|A| = tr(A^-1 dA)).  The all-dims DUBO is instead one batched HIP forward and one analytic HIP adjoint
-(lvae_dubo_fwd_f64 / lvae_dubo_bwd_f64, csrc/dubo.hip: a fused pass over the subjects); the per-dim functions
-stay as they are, as its baseline and comparison.
+(lvae_dubo_fwd_f64 / lvae_dubo_bwd_f64, csrc/dubo.hip: a fused pass over the subjects), and so is the all-dims,
+all-samples ELBO ``elbo_batched`` (lvae_gp_elbo_fwd_f64 / lvae_gp_elbo_bwd_f64, csrc/gp_elbo.hip); the per-dim
+functions stay as they are, as their baseline and comparison.
 """
 import math
 
@@ -157,15 +158,10 @@ def _dubo_noise(likelihoods, L):
     return nz.expand(L) if nz.numel() == 1 else nz.reshape(L)
 
 
-def deviance_upper_bound_batched(latent_dim, covar_module0, covar_module1, likelihoods, train_xt, m, log_v, z, P, T,
-                                 eps):
-    """The DUBO of every latent dim, [L] fp64, from one batched HIP forward (and one batched adjoint):
-    ``deviance_upper_bound`` for dim l on (m[:, l], log_v[:, l]).  covar_module0 / covar_module1: batched
-    modules or per-dim lists; likelihoods: a batched likelihood or a per-dim list; z: [L, M, Q], [M, Q]
-    (shared) or a per-dim list of [M, Q].  Gradients flow to m, log_v [N, L], the kernels' raw parameters
-    and the noise; z is not differentiated."""
+def _batched_kernels(L, covar_module0, covar_module1, z, train_xt, P, T):
+    """(spec0, params0 [L, P0], spec1, params1 [L, P1], z [L, M, Q]) of the all-dims calls from batched modules or
+    per-dim lists and z as [L, M, Q], [M, Q] (shared) or a per-dim list; ValueError on mismatched shapes."""
     from .elbo import _stack_modules
-    L = int(latent_dim)
     spec0, params0 = _stack_modules(covar_module0)
     spec1, params1 = _stack_modules(covar_module1)
     if params0.shape[0] == 1 and L > 1:
@@ -176,11 +172,25 @@ def deviance_upper_bound_batched(latent_dim, covar_module0, covar_module1, likel
         raise ValueError(f"kernel batches {params0.shape[0]}, {params1.shape[0]} != latent dims {L}")
     if isinstance(z, (list, tuple)):
         z = torch.stack([zi.reshape(zi.shape[-2], zi.shape[-1]) for zi in z], 0)
+    if z.dim() not in (2, 3):
+        raise ValueError(f"z must be [L, M, Q], [M, Q] or a per-dim list, got {tuple(z.shape)}")
     zz = z if z.dim() == 3 else z.unsqueeze(0).expand(L, -1, -1)
     if zz.shape[0] != L:
         raise ValueError(f"z has {zz.shape[0]} dims, expected {L}")
     if train_xt.shape[0] != P * T:
         raise ValueError(f"train_xt has {train_xt.shape[0]} rows, expected P*T = {P * T}")
+    return spec0, params0, spec1, params1, zz
+
+
+def deviance_upper_bound_batched(latent_dim, covar_module0, covar_module1, likelihoods, train_xt, m, log_v, z, P, T,
+                                 eps):
+    """The DUBO of every latent dim, [L] fp64, from one batched HIP forward (and one batched adjoint):
+    ``deviance_upper_bound`` for dim l on (m[:, l], log_v[:, l]).  covar_module0 / covar_module1: batched
+    modules or per-dim lists; likelihoods: a batched likelihood or a per-dim list; z: [L, M, Q], [M, Q]
+    (shared) or a per-dim list of [M, Q].  Gradients flow to m, log_v [N, L], the kernels' raw parameters
+    and the noise; z is not differentiated."""
+    L = int(latent_dim)
+    spec0, params0, spec1, params1, zz = _batched_kernels(L, covar_module0, covar_module1, z, train_xt, P, T)
     if tuple(m.shape) != (P * T, L) or tuple(log_v.shape) != (P * T, L):
         raise ValueError(f"m / log_v must be [{P * T}, {L}]")
     noise = _dubo_noise(likelihoods, L).to(m.device)
@@ -196,3 +206,68 @@ def validation_dubo(latent_dim, covar_module0, covar_module1, likelihood, train_
     return deviance_upper_bound_batched(L, covar_module0, covar_module1, likelihood, train_xt, m, log_v, z, P, T,
                                         eps).sum().reshape(1)
 
+
+
+class _GpElboFn(torch.autograd.Function):
+    """elbo [S, L] of all latent dims and S <= 16 samples in one batched HIP pass (lvae_gp_elbo_fwd_f64) with its
+    analytic adjoint (lvae_gp_elbo_bwd_f64); z is not differentiated."""
+
+    @staticmethod
+    def forward(ctx, params0, params1, noise, y, x, z, spec0, spec1, dims):
+        lib = _lib.lib()
+        dev = y.device
+        f64 = lambda t: t.detach().to(torch.float64).contiguous()
+        p0, p1, nz, y64, x64, z64 = f64(params0), f64(params1), f64(noise).reshape(-1), f64(y), f64(x), f64(z)
+        ws = torch.empty(int(lib.lvae_gp_elbo_workspace_size(dims)), dtype=torch.uint8, device=dev)
+        out = torch.empty(dims.S, dims.L, dtype=torch.float64, device=dev)
+        info = torch.empty(dims.L, dtype=torch.int32, device=dev)
+        rc = lib.lvae_gp_elbo_fwd_f64(spec0, spec1, dims, _lib.ptr(x64), _lib.ptr(z64), _lib.ptr(y64), _lib.ptr(p0),
+                                      _lib.ptr(p1), _lib.ptr(nz), _lib.ptr(out), _lib.ptr(info), _lib.ptr(ws),
+                                      _lib.stream_ptr())
+        _lib.check(rc, "gp_elbo_fwd")
+        _check_info(info, "elbo_batched cholesky (10000+col: K0zz, 20000+col: B_st, 30000+col: W)")
+        ctx.save_for_backward(p0, p1, nz, y64, x64, z64, ws)
+        ctx.spec0, ctx.spec1, ctx.dims = spec0, spec1, dims
+        ctx.dtypes = (params0.dtype, params1.dtype, noise.dtype, noise.shape, y.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, gelbo):
+        lib = _lib.lib()
+        p0, p1, nz, y64, x64, z64, ws = ctx.saved_tensors
+        g = gelbo.detach().to(torch.float64).contiguous()
+        dy = torch.empty_like(y64)
+        dp0, dp1, dnz = torch.empty_like(p0), torch.empty_like(p1), torch.empty_like(nz)
+        rc = lib.lvae_gp_elbo_bwd_f64(ctx.spec0, ctx.spec1, ctx.dims, _lib.ptr(x64), _lib.ptr(z64), _lib.ptr(y64),
+                                      _lib.ptr(p0), _lib.ptr(p1), _lib.ptr(nz), _lib.ptr(g), _lib.ptr(dy),
+                                      _lib.ptr(dp0), _lib.ptr(dp1), _lib.ptr(dnz), _lib.ptr(ws), _lib.stream_ptr())
+        _lib.check(rc, "gp_elbo_bwd")
+        t0, t1, tn, nshape, ty = ctx.dtypes
+        return dp0.to(t0), dp1.to(t1), dnz.to(tn).reshape(nshape), dy.to(ty), None, None, None, None, None
+
+
+ELBO_MAX_SAMPLES = 16   # samples of one lvae_gp_elbo_* call (the columns of one MFMA tile)
+
+
+def elbo_batched(latent_dim, covar_module0, covar_module1, likelihoods, train_xt, train_yt, z, P, T, eps):
+    """``elbo`` of every latent dim and every sample at once, fp64: train_yt [N, L] -> [L], or [S, N, L] (S draws
+    of the latent) -> [S, L], entry (s, l) = ``elbo`` for dim l on train_yt[s, :, l].  One batched HIP forward and
+    one analytic adjoint per group of at most 16 samples (a dim's samples share its Grams and factorisations).
+    covar_module0 / covar_module1: batched modules or per-dim lists; likelihoods: a batched likelihood or a
+    per-dim list; z: [L, M, Q], [M, Q] (shared) or a per-dim list of [M, Q].  Gradients flow to train_yt, the
+    kernels' raw parameters and the noise; z is not differentiated."""
+    L = int(latent_dim)
+    spec0, params0, spec1, params1, zz = _batched_kernels(L, covar_module0, covar_module1, z, train_xt, P, T)
+    single = train_yt.dim() == 2
+    y = train_yt.unsqueeze(0) if single else train_yt
+    if y.dim() != 3 or y.shape[0] < 1 or tuple(y.shape[1:]) != (P * T, L):
+        raise ValueError(f"train_yt must be [{P * T}, {L}] or [S, {P * T}, {L}], got {tuple(train_yt.shape)}")
+    noise = _dubo_noise(likelihoods, L).to(y.device)
+    M, Q = int(zz.shape[-2]), int(train_xt.shape[-1])
+    out = []
+    for s0 in range(0, y.shape[0], ELBO_MAX_SAMPLES):
+        ys = y[s0:s0 + ELBO_MAX_SAMPLES]
+        dims = _lib.GpElboDims(L, M, int(P), int(T), Q, int(ys.shape[0]), float(eps))
+        out.append(_GpElboFn.apply(params0, params1, noise, ys, train_xt, zz, spec0, spec1, dims))
+    res = out[0] if len(out) == 1 else torch.cat(out, 0)
+    return res[0] if single else res

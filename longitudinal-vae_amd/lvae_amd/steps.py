@@ -3,6 +3,7 @@
 ClosedStep   : standard_training with type_KL='closed' (training.py:484-592)
 HensmanStep  : hensman_training batch body incl. the natural-gradient update (training.py:91-135)
 DuboStep     : standard_training with type_KL='GPapprox_closed' (training.py:499-575), full batch
+ElboStep     : standard_training with type_KL='GPapprox' (training.py:499-575), full batch, num_samples draws
 GraphedStep  : either step replayed as HIP graphs (torch.cuda.CUDAGraph is a hipGraph on ROCm)
 
 Both steps return detached device scalars; callers read them when they choose (the reference's
@@ -313,6 +314,65 @@ class DuboStep:
 
     def __call__(self, img, mask, X, eps=None):
         out = self.forward_backward(img, mask, X, eps)
+        self.communicate()
+        self.apply()
+        return out
+
+
+class ElboStep:
+    """standard_training's type_KL='GPapprox' branch (training.py:499-575): encode, sample, decode and loss, then
+    ``num_samples`` further draws Z_s of the latent and minus their ELBOs over all latent dims in one batched call
+    (gpapprox.elbo_batched: a dim's draws share its Grams and factorisations), gp = -sum_{s,l} elbo / num_samples;
+    recon + weight * gp / L ('mse') or nll + gp ('nll'), backward; ``apply`` is the optimiser step and the scale
+    constraint.
+
+    k0 / k1 / likelihood: batched modules or per-dim lists; z: [L, M, Q], [M, Q] or a per-dim list; X: the full
+    batch's covariates [P*T, Q], subjects in blocks of T rows; eps [N, L]: the decoder's draw, eps_gp
+    [num_samples, N, L]: the GP term's draws (each drawn if None).  One stream, eager; capture into a HIP graph is
+    untested."""
+
+    def __init__(self, vae, k0, k1, likelihood, optimiser, z, T, weight=0.15, loss_function="mse", eps=1e-6,
+                 constrain_scales=True, grad_hook=None, num_samples=1):
+        self.vae, self.k0, self.k1, self.lik, self.opt = vae, k0, k1, likelihood, optimiser
+        self.z, self.T = z, T
+        self.weight, self.loss_function, self.eps = weight, loss_function, eps
+        self.constrain_scales, self.grad_hook = constrain_scales, grad_hook
+        self.num_samples = int(num_samples)
+
+    def forward_backward(self, img, mask, X, eps=None, eps_gp=None):
+        from .gpapprox import elbo_batched
+        self.opt.zero_grad(set_to_none=True)
+        recon, mu, log_var = self.vae(img, eps)
+        mse, nll = self.vae.loss_function(recon, img, mask)
+        recon_loss, nll_loss = mse.sum(), nll.sum()
+        L, S = mu.shape[1], self.num_samples
+        if eps_gp is None:
+            eps_gp = torch.randn((S,) + tuple(mu.shape), dtype=mu.dtype, device=mu.device)
+        if tuple(eps_gp.shape) != (S,) + tuple(mu.shape):
+            raise ValueError(f"eps_gp must be [{S}, {mu.shape[0]}, {L}], got {tuple(eps_gp.shape)}")
+        Z = torch.stack([self.vae.sample_latent(mu, log_var, eps_gp[s]) for s in range(S)])
+        el = elbo_batched(L, self.k0, self.k1, self.lik, X, Z, self.z, X.shape[0] // self.T, self.T, self.eps)
+        if self.loss_function == "mse":
+            gp = -el.sum() / (S * L)
+            net = recon_loss + self.weight * gp
+        else:
+            gp = -el.sum() / S
+            net = nll_loss + gp
+        net.backward()
+        return net.detach(), recon_loss.detach(), nll_loss.detach(), gp.detach()
+
+    def communicate(self):
+        if self.grad_hook is not None:
+            self.grad_hook()
+
+    def apply(self):
+        self.opt.step()
+        if self.constrain_scales:
+            for lk in (self.lik if isinstance(self.lik, (list, tuple, torch.nn.ModuleList)) else [self.lik]):
+                lk.noise = 1.0
+
+    def __call__(self, img, mask, X, eps=None, eps_gp=None):
+        out = self.forward_backward(img, mask, X, eps, eps_gp)
         self.communicate()
         self.apply()
         return out
