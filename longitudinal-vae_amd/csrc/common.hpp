@@ -23,6 +23,18 @@ constexpr int kWave = 64;
 inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
+// Carves a workspace into 256-byte aligned arrays of doubles; a null base only measures (bytes = off at the end).
+struct WsCarve {
+  char* base;
+  size_t off;
+  explicit WsCarve(char* b) : base(b), off(0) {}
+  double* take(size_t n) {
+    double* q = base ? (double*)(base + off) : nullptr;
+    off += align256(n * sizeof(double));
+    return q;
+  }
+};
+
 // Zero `bytes` bytes at p (4-byte aligned) on st with a kernel.  The library never calls hipMemsetAsync: a memset
 // captured into a HIP graph by stream capture was found not to zero its target on the replays after the first
 // (ROCm 7.0 runtime; scripts/dp_replay_diag.py: the natural-gradient update's info array kept stale bytes in

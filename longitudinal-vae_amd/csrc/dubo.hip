@@ -9,7 +9,7 @@
 //   dubo = 1/2 [ sum diag(iB) v - sum iW.R + sum_p m_p^T iB_p m_p - p.w - N - log|Kz| + sum log|B_p| + log|W|
 //                - sum logv + sum iB.K0 - sum Q.iK ]
 // The data-sized products (iBK, Q, R, p and the per-subject sums) are ONE pass over the subjects
-// (dubo_subject_kernel): a workgroup walks kDuboS consecutive subjects with Q, R in MFMA accumulators and
+// (dubo_subject_kernel): a workgroup walks kBoundS consecutive subjects with Q, R in MFMA accumulators and
 // writes one partial; dubo_reduce_kernel adds the partials in group order (no atomics: bit-reproducible).
 // T > 32 (X_p and iBK_p no longer fit the LDS tile) takes batched gemm_small launches instead.
 //
@@ -20,7 +20,8 @@
 //   dB_p = g/2 (iB - iB D iB - iB K0 iB - a a^T - (U - Z) iBK^T - (U R - 2 F) U^T)_p
 // (dB_p is the adjoint of the dense form up to an antisymmetric part, which the symmetric Gram adjoint and the
 // trace of dnoise do not see: F U^T + U F^T -> 2 F U^T.)
-// (the group / tile maps, the W and residual kernels, the info merge and the workspace carving: gp_bound.hpp)
+// (the Grams and their adjoints, the argument check, W's inverse, the info merge and the blocks of the subject walk
+// that gp_elbo.hip's has too: gp_bound.hpp / gp_bound.hip; the workspace carving: common.hpp)
 #include "gp_bound.hpp"
 
 namespace lvae {
@@ -29,7 +30,12 @@ namespace {
 constexpr int kDuboScal = 8;   // scalar slots per dim: m.iB.m, diag(iB).v, iB.K0, sum logv, sum log|B_p|
 
 // doubles of one (dim, group) partial: Q and R lower tiles in accumulator order, p [128], the scalars
-inline int64_t dubo_part_stride(int M) { return (int64_t)2 * dubo_tiles(M) * 256 + 128 + kDuboScal; }
+inline int64_t dubo_part_stride(int M) { return (int64_t)2 * bound_tiles(M) * 256 + 128 + kDuboScal; }
+
+// (a null d: all zero, which bound_check answers with -3)
+inline BoundDims dubo_dims(const lvae_dubo_dims* d) {
+  return d ? BoundDims{d->L, d->M, d->P, d->T, d->Q} : BoundDims{};
+}
 
 struct DWs {
   double *X, *iBK, *U, *UR, *F, *Z, *tNM, *dX;                                    // [L,N,M]
@@ -42,32 +48,31 @@ struct DWs {
   size_t bytes;
   DWs(char* base, const lvae_dubo_dims& d) {
     WsCarve c(base);
-    auto take = [&](size_t n) { return c.take(n); };
     const size_t L = d.L, M = d.M, N = (size_t)d.P * d.T, TT = (size_t)d.P * d.T * d.T;
     double** nm[] = {&X, &iBK, &U, &UR, &F, &Z, &tNM, &dX};
-    for (auto q : nm) *q = take(L * N * M);
+    for (auto q : nm) *q = c.take(L * N * M);
     double** mm[] = {&Kz, &iK, &Q, &R, &W, &iW0, &E, &iW, &iWR, &iWRiW, &iKQ, &iKQiK, &dKz};
-    for (auto q : mm) *q = take(L * M * M);
+    for (auto q : mm) *q = c.take(L * M * M);
     double** tt[] = {&K0st, &Bst, &iB, &VB, &iBDiB, &K0iB, &iBK0iB, &GB, &GK0};
-    for (auto q : tt) *q = take(L * TT);
-    p = take(L * M);
-    w = take(L * M);
-    s = take(L * N);
-    y = take(L * N);
-    a = take(L * N);
-    ldK = take(L);
-    ldB = take(L * d.P);
-    ldW = take(L);
-    epsv = take(L);
-    scal = take(L * kDuboScal);
-    part = take(L * (size_t)dubo_groups(d.P) * (size_t)dubo_part_stride(d.M));
-    info = (int32_t*)take(L * (2 + (size_t)d.P));
-    gpart = c.take_gram_part(L, N, M, TT);
+    for (auto q : tt) *q = c.take(L * TT);
+    p = c.take(L * M);
+    w = c.take(L * M);
+    s = c.take(L * N);
+    y = c.take(L * N);
+    a = c.take(L * N);
+    ldK = c.take(L);
+    ldB = c.take(L * d.P);
+    ldW = c.take(L);
+    epsv = c.take(L);
+    scal = c.take(L * kDuboScal);
+    part = c.take(L * (size_t)bound_groups(d.P) * (size_t)dubo_part_stride(d.M));
+    info = (int32_t*)c.take(L * (2 + (size_t)d.P));
+    gpart = c.take(bound_gram_part_doubles(dubo_dims(&d)));
     bytes = c.off;
   }
 };
 
-// The fused subject pass: grid (groups, L), 512 threads.  Group g walks subjects [g kDuboS, (g + 1) kDuboS).
+// The fused subject pass: grid (groups, L), 512 threads.  Group g walks subjects [g kBoundS, (g + 1) kBoundS).
 // Per subject: iB_p [T,T], X_p [T,M], m_p, v_p into LDS (zero padded to whole MFMA steps); iBK_p = iB_p X_p on
 // v_mfma_f64_16x16x4 (C[(lane >> 4) + 4 r][lane & 15]) -> LDS and HBM; then Q += X_p^T iBK_p and
 // R += iBK_p^T D_p iBK_p on the lower 16 x 16 tiles, tile t = wave + 8 k in accumulators Qa[k] / Ra[k] for the
@@ -80,49 +85,30 @@ __global__ __launch_bounds__(512) void dubo_subject_kernel(int M, int P, int T, 
                                                            const double* __restrict__ mu,
                                                            const double* __restrict__ logv,
                                                            double* __restrict__ iBK, double* __restrict__ part) {
-  __shared__ double sB[kDuboT][kDuboT + 1];
-  __shared__ double sX[kDuboT][kDuboLD];
-  __shared__ double sY[kDuboT][kDuboLD];
-  __shared__ double sm[kDuboT], sv[kDuboT];
+  __shared__ double sB[kBoundT][kBoundT + 1];
+  __shared__ double sX[kBoundT][kBoundLD];
+  __shared__ double sY[kBoundT][kBoundLD];
+  __shared__ double sm[kBoundT], sv[kBoundT];
   __shared__ double red[8];
   const int g = blockIdx.x, l = blockIdx.y, G = gridDim.x;
   const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
   const int tM = (M + 15) >> 4, tT = (T + 15) >> 4, T4 = (T + 3) & ~3;
   const int64_t N = (int64_t)P * T, TT = (int64_t)T * T;
-  int ti[kDuboTPW], tj[kDuboTPW];
-  bool on[kDuboTPW];
-  bi_f64x4 Qa[kDuboTPW], Ra[kDuboTPW];
-#pragma unroll
-  for (int k = 0; k < kDuboTPW; ++k) {
-    const int t = wv + 8 * k;
-    on[k] = t < nt;
-    dubo_tile(on[k] ? t : 0, ti[k], tj[k]);
-    Qa[k] = bi_f64x4{0.0, 0.0, 0.0, 0.0};
-    Ra[k] = bi_f64x4{0.0, 0.0, 0.0, 0.0};
-  }
+  int ti[kBoundTPW], tj[kBoundTPW];
+  bool on[kBoundTPW];
+  bi_f64x4 Qa[kBoundTPW], Ra[kBoundTPW] = {};
+  bound_walk_setup(wv, nt, ti, tj, on, Qa);
   double pj = 0.0, s_mbm = 0.0, s_dv = 0.0, s_bk0 = 0.0, s_lv = 0.0, s_ldb = 0.0;
-  // the padding (rows T.., columns M..) is zeroed once; the walk only rewrites the valid parts
-  for (int e = tid; e < kDuboT * (kDuboT + 1); e += 512) (&sB[0][0])[e] = 0.0;
-  for (int e = tid; e < kDuboT * kDuboLD; e += 512) {
-    (&sX[0][0])[e] = 0.0;
-    (&sY[0][0])[e] = 0.0;
-  }
-  if (tid < kDuboT) {
+  bound_lds_zero(tid, sB, sX, sY);
+  if (tid < kBoundT) {
     sm[tid] = 0.0;
     sv[tid] = 0.0;
   }
-  const int p0 = g * kDuboS, p1 = p0 + kDuboS < P ? p0 + kDuboS : P;
+  const int p0 = g * kBoundS, p1 = p0 + kBoundS < P ? p0 + kBoundS : P;
   for (int p = p0; p < p1; ++p) {
     __syncthreads();  // the previous subject's readers are done (and the zero fill is visible)
-    const double* ib = iB + ((int64_t)l * P + p) * TT;
-    const double* k0 = K0st + ((int64_t)l * P + p) * TT;
-    for (int e = tid; e < T * T; e += 512) {
-      const double b = ib[e];
-      sB[e / T][e % T] = b;
-      s_bk0 += b * k0[e];
-    }
-    const double* xp = X + ((int64_t)l * N + (int64_t)p * T) * M;
-    for (int e = tid; e < T * M; e += 512) sX[e / M][e % M] = xp[e];
+    bound_load_subject(tid, T, M, iB + ((int64_t)l * P + p) * TT, K0st + ((int64_t)l * P + p) * TT,
+                       X + ((int64_t)l * N + (int64_t)p * T) * M, sB, sX, s_bk0);
     if (tid < T) {
       const int64_t q = ((int64_t)p * T + tid) * L + l;
       const double lv = logv[q];
@@ -140,18 +126,8 @@ __global__ __launch_bounds__(512) void dubo_subject_kernel(int M, int P, int T, 
     }
     // iBK_p = iB_p X_p: tT x tM tiles over the 8 waves
     double* yp = iBK + ((int64_t)l * N + (int64_t)p * T) * M;
-    for (int tt = wv; tt < tT * tM; tt += 8) {
-      const int r0 = (tt / tM) << 4, c0 = (tt % tM) << 4;
-      bi_f64x4 acc = {0.0, 0.0, 0.0, 0.0};
-      for (int kk = 0; kk < T4; kk += 4)
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(sB[r0 + li][kk + lk], sX[kk + lk][c0 + li], acc, 0, 0, 0);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int i = r0 + lk + 4 * r, j = c0 + li;
-        sY[i][j] = acc[r];
-        if (i < T && j < M) yp[(int64_t)i * M + j] = acc[r];
-      }
-    }
+    for (int tt = wv; tt < tT * tM; tt += 8)
+      bound_ibk_tile((tt / tM) << 4, (tt % tM) << 4, li, lk, T, M, T4, sB, sX, sY, yp);
     __syncthreads();
     if (tid < M) {
       double q = 0.0;
@@ -159,7 +135,7 @@ __global__ __launch_bounds__(512) void dubo_subject_kernel(int M, int P, int T, 
       pj += q;
     }
 #pragma unroll
-    for (int k = 0; k < kDuboTPW; ++k) {
+    for (int k = 0; k < kBoundTPW; ++k) {
       if (on[k]) {
         const int ci = (ti[k] << 4) + li, cj = (tj[k] << 4) + li;
         for (int kk = 0; kk < T4; kk += 4) {
@@ -171,17 +147,8 @@ __global__ __launch_bounds__(512) void dubo_subject_kernel(int M, int P, int T, 
     }
   }
   double* pp = part + ((int64_t)l * G + g) * pstride;
-#pragma unroll
-  for (int k = 0; k < kDuboTPW; ++k) {
-    if (on[k]) {
-      const int t = wv + 8 * k;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        pp[((int64_t)t * 4 + r) * 64 + lane] = Qa[k][r];
-        pp[((int64_t)(nt + t) * 4 + r) * 64 + lane] = Ra[k][r];
-      }
-    }
-  }
+  bound_store_tiles(pp, wv, lane, on, Qa);
+  bound_store_tiles(pp + (int64_t)nt * 256, wv, lane, on, Ra);  // R's tiles follow Q's, in the same order
   double* pv = pp + (int64_t)2 * nt * 256;
   if (tid < 128) pv[tid] = pj;
   const double vals[5] = {s_mbm, s_dv, s_bk0, s_lv, s_ldb};
@@ -201,17 +168,7 @@ __global__ __launch_bounds__(256) void dubo_reduce_kernel(int M, int G, int nt, 
   const int b = blockIdx.x, l = blockIdx.y, tid = threadIdx.x;
   const double* pl = part + (int64_t)l * G * pstride;
   if (b < 2 * nt) {
-    double sum = 0.0;
-    for (int g = 0; g < G; ++g) sum += pl[g * pstride + (int64_t)b * 256 + tid];
-    const int t = b < nt ? b : b - nt, r = tid >> 6, lane = tid & 63;
-    int ti, tj;
-    dubo_tile(t, ti, tj);
-    const int i = (ti << 4) + (lane >> 4) + 4 * r, j = (tj << 4) + (lane & 15);
-    if (i < M && j < M) {
-      double* o = (b < nt ? Q : R) + (int64_t)l * M * M;
-      o[(int64_t)i * M + j] = sum;
-      if (ti != tj) o[(int64_t)j * M + i] = sum;
-    }
+    bound_reduce_tile(M, G, pstride, pl, b, b < nt ? b : b - nt, tid, (b < nt ? Q : R) + (int64_t)l * M * M);
   } else if (tid < 128 + 5) {
     double sum = 0.0;
     for (int g = 0; g < G; ++g) sum += pl[g * pstride + (int64_t)2 * nt * 256 + tid];
@@ -378,13 +335,6 @@ __global__ void dubo_gb_kernel(int P, int T, int L, const double* __restrict__ g
   GK0[e] = h * iB[e];
 }
 
-int dubo_check(const lvae_kernel_spec* s0, const lvae_kernel_spec* s1, const lvae_dubo_dims* d) {
-  if (!s0 || !spec_bucket(s0)) return -1;
-  if (!s1 || !spec_bucket(s1)) return -2;
-  if (!d || d->L < 1 || d->M < 1 || d->M > 128 || d->P < 1 || d->T < 1 || d->T > 128 || d->Q < 1) return -3;
-  return 0;
-}
-
 }  // namespace
 }  // namespace lvae
 
@@ -398,26 +348,20 @@ int lvae_dubo_fwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spe
                       const double* x, const double* z, const double* mu, const double* logv, const double* params0,
                       const double* params1, const double* noise, double* dubo, int32_t* info, void* workspace,
                       void* stream) {
-  LVAE_TRY(dubo_check(spec0, spec1, dp));
+  const BoundDims bd = dubo_dims(dp);
+  LVAE_TRY(bound_check(spec0, spec1, bd));
   if (!workspace || ((uintptr_t)workspace & 255)) return -4;
   hipStream_t st = (hipStream_t)stream;
   const lvae_dubo_dims& d = *dp;
-  const int L = d.L, M = d.M, P = d.P, T = d.T, Q = d.Q, N = P * T;
+  const int L = d.L, M = d.M, P = d.P, T = d.T, N = P * T;
   const int64_t MM = (int64_t)M * M, TT = (int64_t)T * T, NM = (int64_t)N * M;
   DWs w((char*)workspace, d);
-  // Grams
-  dubo_fill_kernel<<<blocks(L), 256, 0, st>>>(w.epsv, L, d.eps);
-  const lvae_xview xv{x, 0, 0, Q}, zv{z, 0, (int64_t)M * Q, Q}, xs{x, (int64_t)T * Q, 0, Q};
-  const lvae_kernel_spec* specs[2] = {spec0, spec1};
-  const GramFwdJob jobs[4] = {{0, 1, N, M, 0, 0, 0, xv, zv, params0, nullptr, w.X, 0, NM, M},
-                              {0, 1, M, M, 0, 0, 0, zv, zv, params0, w.epsv, w.Kz, 0, MM, M},
-                              {0, P, T, T, 0, 0, 0, xs, xs, params0, nullptr, w.K0st, TT, P * TT, T},
-                              {1, P, T, T, 0, 0, 0, xs, xs, params1, noise, w.Bst, TT, P * TT, T}};
-  LVAE_TRY(gram_multi_f64(specs, jobs, 4, L, st));
+  LVAE_TRY(bound_grams_fwd(spec0, spec1, bd, x, z, params0, params1, noise, d.eps, w.epsv, w.X, w.Kz, w.K0st, w.Bst,
+                           st));
   LVAE_TRY(spd_inv_small_f64(M, L, w.Kz, MM, w.iK, MM, w.ldK, w.info, st));
   LVAE_TRY(spd_inv_small_f64(T, L * P, w.Bst, TT, w.iB, TT, w.ldB, w.info + L, st));
-  if (T <= kDuboT) {
-    const int G = dubo_groups(P), nt = dubo_tiles(M);
+  if (T <= kBoundT) {
+    const int G = bound_groups(P), nt = bound_tiles(M);
     const int64_t ps = dubo_part_stride(M);
     dubo_subject_kernel<<<dim3(G, L), 512, 0, st>>>(M, P, T, L, nt, ps, w.X, w.iB, w.K0st, w.ldB, mu, logv, w.iBK,
                                                    w.part);
@@ -434,14 +378,10 @@ int lvae_dubo_fwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spe
                             st));
     dubo_scal_kernel<<<L, 256, 0, st>>>(P, T, L, mu, logv, w.s, w.iB, w.K0st, w.ldB, w.scal);
   }
-  dubo_w_kernel<<<blocks(L * MM), 256, 0, st>>>(L, M, w.Kz, w.Q, w.W);
-  // iW = Y + Y (I - W Y), the residual in double-double (dubo_resid_kernel)
-  LVAE_TRY(spd_inv_small_f64(M, L, w.W, MM, w.iW0, MM, w.ldW, w.info + L + L * P, st));
-  dubo_resid_kernel<<<blocks(L * MM), 256, 0, st>>>(L, M, w.W, w.iW0, w.E, w.iW);
-  LVAE_TRY(gemm_small_f64(0, 0, M, M, M, 1.0, w.iW0, M, MM, 0, w.E, M, MM, 0, 1.0, w.iW, M, MM, 0, L, 1, st));
+  LVAE_TRY(bound_w_inverse(L, M, w.Kz, w.Q, w.W, w.iW0, w.E, w.iW, w.ldW, w.info + L + L * P, st));
   LVAE_TRY(gemm_small_f64(0, 0, M, 1, M, 1.0, w.iW, M, MM, 0, w.p, 1, M, 0, 0.0, w.w, 1, M, 0, L, 1, st));
   dubo_final_kernel<<<L, 256, 0, st>>>(M, (double)N, w.iW, w.R, w.Q, w.iK, w.p, w.w, w.scal, w.ldK, w.ldW, dubo);
-  if (info) dubo_info_kernel<<<blocks(L), 256, 0, st>>>(L, P, w.info, info);
+  if (info) bound_info(L, P, w.info, info, st);
   LVAE_CHECK_LAUNCH();
   return 0;
 }
@@ -451,11 +391,12 @@ int lvae_dubo_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spe
                       const double* params1, const double* noise, const double* gdubo, double* dmu, double* dlogv,
                       double* dparams0, double* dparams1, double* dnoise, void* workspace, void* stream) {
   (void)noise;
-  LVAE_TRY(dubo_check(spec0, spec1, dp));
+  const BoundDims bd = dubo_dims(dp);
+  LVAE_TRY(bound_check(spec0, spec1, bd));
   if (!workspace || ((uintptr_t)workspace & 255)) return -4;
   hipStream_t st = (hipStream_t)stream;
   const lvae_dubo_dims& d = *dp;
-  const int L = d.L, M = d.M, P = d.P, T = d.T, Q = d.Q, N = P * T;
+  const int L = d.L, M = d.M, P = d.P, T = d.T, N = P * T;
   const int64_t MM = (int64_t)M * M, TT = (int64_t)T * T, NM = (int64_t)N * M, LTT = (int64_t)L * P * TT;
   const int64_t TM = (int64_t)T * M;
   DWs w((char*)workspace, d);
@@ -492,16 +433,8 @@ int lvae_dubo_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spe
   LVAE_TRY(gemm_small_f64(0, 1, T, T, M, 1.0, w.UR, M, NM, TM, w.U, M, NM, TM, 1.0, w.GB, T, P * TT, TT, L, P, st));
   dubo_gb_kernel<<<blocks(LTT), 256, 0, st>>>(P, T, L, gdubo, w.iB, w.a, w.iBDiB, w.iBK0iB, w.GB, w.GK0);
   // hyper-parameter gradients through the four Grams
-  (void)zero_async(dparams0, sizeof(double) * L * spec0->n_params, st);
-  (void)zero_async(dparams1, sizeof(double) * L * spec1->n_params, st);
-  if (dnoise) (void)zero_async(dnoise, sizeof(double) * L, st);
-  const lvae_xview xv{x, 0, 0, Q}, zv{z, 0, (int64_t)M * Q, Q}, xs{x, (int64_t)T * Q, 0, Q};
-  const GramBwdJob jobs[4] = {{0, xv, zv, 1, N, M, 0, params0, w.dX, 0, NM, M, dparams0, nullptr, 0, 0},
-                              {0, zv, zv, 1, M, M, 0, params0, w.dKz, 0, MM, M, dparams0, nullptr, 0, 0},
-                              {0, xs, xs, P, T, T, 0, params0, w.GK0, TT, P * TT, T, dparams0, nullptr, 0, 0},
-                              {1, xs, xs, P, T, T, 0, params1, w.GB, TT, P * TT, T, dparams1, dnoise, 0, 0}};
-  const lvae_kernel_spec* specs[2] = {spec0, spec1};
-  LVAE_TRY(gram_bwd_multi_f64(specs, jobs, 4, L, w.gpart, st));
+  LVAE_TRY(bound_grams_bwd(spec0, spec1, bd, x, z, params0, params1, w.dX, w.dKz, w.GK0, w.GB, dparams0, dparams1,
+                           dnoise, w.gpart, st));
   LVAE_CHECK_LAUNCH();
   return 0;
 }

@@ -1,0 +1,134 @@
+// gp_bound.hip -- the host functions and kernels of gp_bound.hpp: what hensman.hip, dubo.hip and gp_elbo.hip share
+// outside their own kernels.
+#include "gp_bound.hpp"
+
+namespace lvae {
+namespace {
+
+__global__ void bound_fill_kernel(double* p, int n, double v) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) p[i] = v;
+}
+
+// W = 1/2 ((Kz + Q) + (Kz + Q)^T)
+__global__ void bound_w_kernel(int L, int M, const double* __restrict__ Kz, const double* __restrict__ Q,
+                               double* __restrict__ W) {
+  const int64_t MM = (int64_t)M * M;
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= L * MM) return;
+  const int64_t b = (e / MM) * MM;
+  const int i = (int)((e % MM) / M), j = (int)(e % M);
+  const int64_t f = b + (int64_t)j * M + i;
+  W[e] = 0.5 * ((Kz[e] + Q[e]) + (Kz[f] + Q[f]));
+}
+
+// E = I - W Y with every dot product accumulated in double-double (two-product by fma, two-sum), rounded to
+// fp64 at the end, and Y1 = Y: the residual of the first inverse of W, for the one Newton step Y1 += Y E.
+// W = K0zz + Q has cond ~1e8..1e9 (K0zz's jitter), so Y = spd_inv_small(W) carries a forward error of ~1e-9
+// |Y|; the bound's W terms (sum iW.R, p.iW p) see it directly (2.3e-9 of the bound on the reference's golden
+// vector, whose own bound is 1e-9), while a residual formed in plain fp64 is as inexact as Y itself.
+__global__ void bound_resid_kernel(int L, int M, const double* __restrict__ W, const double* __restrict__ Y,
+                                   double* __restrict__ E, double* __restrict__ Y1) {
+#pragma clang fp contract(off)  // the error-free transforms below need every product and sum rounded on its own
+  const int64_t MM = (int64_t)M * M;
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= L * MM) return;
+  const int64_t b = (e / MM) * MM;
+  const int i = (int)((e % MM) / M), j = (int)(e % M);
+  const double* wr = W + b + (int64_t)i * M;
+  const double* yc = Y + b + j;
+  double hi = (i == j) ? 1.0 : 0.0, lo = 0.0;
+  for (int k = 0; k < M; ++k) {
+    const double a = -wr[k], y = yc[(int64_t)k * M];
+    const double ph = a * y, pl = fma(a, y, -ph);  // a y = ph + pl exactly
+    const double s = hi + ph, bb = s - hi;
+    lo += ((hi - (s - bb)) + (ph - bb)) + pl;      // two-sum's error term + the product's
+    hi = s;
+  }
+  E[e] = hi + lo;
+  Y1[e] = Y[e];
+}
+
+__global__ void bound_info_kernel(int L, int P, const int32_t* __restrict__ w, int32_t* __restrict__ info) {
+  const int l = blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= L) return;
+  int v = 0;
+  if (w[l]) v = 10000 + w[l];
+  for (int p = 0; p < P && !v; ++p)
+    if (w[L + (int64_t)l * P + p]) v = 20000 + w[L + (int64_t)l * P + p];
+  if (!v && w[L + (int64_t)L * P + l]) v = 30000 + w[L + (int64_t)L * P + l];
+  info[l] = v;
+}
+
+// The four Grams X [N,M], Kz [M,M], K0_p and B_p [P][T,T] as adjoint jobs.  bound_gram_part_doubles passes null
+// pointers: gram_bwd_part_bytes reads the shapes alone.
+void bound_bwd_jobs(const BoundDims& d, const double* x, const double* z, const double* params0,
+                    const double* params1, const double* dX, const double* dKz, const double* dK0st,
+                    const double* dBst, double* dparams0, double* dparams1, double* dnoise, GramBwdJob (&jobs)[4]) {
+  const int M = d.M, P = d.P, T = d.T, Q = d.Q, N = P * T;
+  const int64_t MM = (int64_t)M * M, TT = (int64_t)T * T, NM = (int64_t)N * M;
+  const lvae_xview xv{x, 0, 0, Q}, zv{z, 0, (int64_t)M * Q, Q}, xs{x, (int64_t)T * Q, 0, Q};
+  jobs[0] = {0, xv, zv, 1, N, M, 0, params0, dX, 0, NM, M, dparams0, nullptr, 0, 0};
+  jobs[1] = {0, zv, zv, 1, M, M, 0, params0, dKz, 0, MM, M, dparams0, nullptr, 0, 0};
+  jobs[2] = {0, xs, xs, P, T, T, 0, params0, dK0st, TT, P * TT, T, dparams0, nullptr, 0, 0};
+  jobs[3] = {1, xs, xs, P, T, T, 0, params1, dBst, TT, P * TT, T, dparams1, dnoise, 0, 0};
+}
+
+}  // namespace
+
+int bound_check(const lvae_kernel_spec* s0, const lvae_kernel_spec* s1, const BoundDims& d) {
+  if (!s0 || !spec_bucket(s0)) return -1;
+  if (!s1 || !spec_bucket(s1)) return -2;
+  if (d.L < 1 || d.M < 1 || d.M > 128 || d.P < 1 || d.T < 1 || d.T > 128 || d.Q < 1) return -3;
+  return 0;
+}
+
+size_t bound_gram_part_doubles(const BoundDims& d) {
+  GramBwdJob jobs[4];
+  bound_bwd_jobs(d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                 jobs);
+  return gram_bwd_part_bytes(jobs, 4, d.L) / sizeof(double);
+}
+
+int bound_grams_fwd(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, const BoundDims& d, const double* x,
+                    const double* z, const double* params0, const double* params1, const double* noise, double eps,
+                    double* epsv, double* X, double* Kz, double* K0st, double* Bst, hipStream_t st) {
+  const int L = d.L, M = d.M, P = d.P, T = d.T, Q = d.Q, N = P * T;
+  const int64_t MM = (int64_t)M * M, TT = (int64_t)T * T, NM = (int64_t)N * M;
+  bound_fill_kernel<<<blocks(L), 256, 0, st>>>(epsv, L, eps);
+  const lvae_xview xv{x, 0, 0, Q}, zv{z, 0, (int64_t)M * Q, Q}, xs{x, (int64_t)T * Q, 0, Q};
+  const lvae_kernel_spec* specs[2] = {spec0, spec1};
+  const GramFwdJob jobs[4] = {{0, 1, N, M, 0, 0, 0, xv, zv, params0, nullptr, X, 0, NM, M},
+                              {0, 1, M, M, 0, 0, 0, zv, zv, params0, epsv, Kz, 0, MM, M},
+                              {0, P, T, T, 0, 0, 0, xs, xs, params0, nullptr, K0st, TT, P * TT, T},
+                              {1, P, T, T, 0, 0, 0, xs, xs, params1, noise, Bst, TT, P * TT, T}};
+  return gram_multi_f64(specs, jobs, 4, L, st);
+}
+
+int bound_grams_bwd(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, const BoundDims& d, const double* x,
+                    const double* z, const double* params0, const double* params1, const double* dX,
+                    const double* dKz, const double* dK0st, const double* dBst, double* dparams0, double* dparams1,
+                    double* dnoise, double* gpart, hipStream_t st) {
+  (void)zero_async(dparams0, sizeof(double) * d.L * spec0->n_params, st);
+  (void)zero_async(dparams1, sizeof(double) * d.L * spec1->n_params, st);
+  if (dnoise) (void)zero_async(dnoise, sizeof(double) * d.L, st);
+  GramBwdJob jobs[4];
+  bound_bwd_jobs(d, x, z, params0, params1, dX, dKz, dK0st, dBst, dparams0, dparams1, dnoise, jobs);
+  const lvae_kernel_spec* specs[2] = {spec0, spec1};
+  return gram_bwd_multi_f64(specs, jobs, 4, d.L, gpart, st);
+}
+
+void bound_info(int L, int P, const int32_t* w, int32_t* info, hipStream_t st) {
+  bound_info_kernel<<<blocks(L), 256, 0, st>>>(L, P, w, info);
+}
+
+int bound_w_inverse(int L, int M, const double* Kz, const double* Q, double* W, double* iW0, double* E, double* iW,
+                    double* ldW, int32_t* info, hipStream_t st) {
+  const int64_t MM = (int64_t)M * M;
+  bound_w_kernel<<<blocks(L * MM), 256, 0, st>>>(L, M, Kz, Q, W);
+  LVAE_TRY(spd_inv_small_f64(M, L, W, MM, iW0, MM, ldW, info, st));
+  bound_resid_kernel<<<blocks(L * MM), 256, 0, st>>>(L, M, W, iW0, E, iW);
+  return gemm_small_f64(0, 0, M, M, M, 1.0, iW0, M, MM, 0, E, M, MM, 0, 1.0, iW, M, MM, 0, L, 1, st);
+}
+
+}  // namespace lvae

@@ -1,116 +1,152 @@
-// gp_bound.hpp -- what the full-batch GP-approximation bounds share: the DUBO (dubo.hip) and the sampled ELBO
-// (gp_elbo.hip).  Both build X = k0(x, z), Kz, K0_p, B_p, walk the subjects in groups of kDuboS with Q in MFMA
-// accumulators over the lower 16 x 16 tiles, form W = sym(Kz + Q) and invert it with one Newton step on a
-// double-double residual; the tile maps, those two kernels, the info merge and the workspace carving are here.
+// gp_bound.hpp -- what the inducing-point bounds share: the Hensman KL bound (hensman.hip), the DUBO (dubo.hip)
+// and the sampled ELBO (gp_elbo.hip).  All three build X = k0(x, z), Kz, K0_p, B_p in one launch and contract the
+// four adjoints in two; the host side of that, the argument check, the info merge and W's inverse (W = sym(Kz + Q),
+// one Newton step on a double-double residual) are in gp_bound.hip.  The DUBO and the ELBO also walk the subjects
+// in groups of kBoundS with Q in MFMA accumulators over the lower 16 x 16 tiles: the tile maps and the blocks of
+// that walk the two subject kernels have in common are the device helpers below.
 #pragma once
 #include "common.hpp"
 #include "blkinv.hpp"
 #include "gram_bwd.hpp"
+#include "small.hpp"
 
 namespace lvae {
 
-int spd_inv_small_f64(int n, int batch, const double* A, int64_t stride, double* Ainv, int64_t stride_out,
-                      double* logdet, int32_t* info, hipStream_t st);
-int gemm_small_f64(int ta, int tb, int m, int n, int k, double alpha, const double* A, int lda, int64_t sa1,
-                   int64_t sa2, const double* B, int ldb, int64_t sb1, int64_t sb2, double beta, double* C, int ldc,
-                   int64_t sc1, int64_t sc2, int nb1, int nb2, hipStream_t st);
+constexpr int kBoundS = 16;     // subjects per workgroup of the fused pass (the group count is ceil(P / kBoundS))
+constexpr int kBoundT = 32;     // largest T of the fused pass
+constexpr int kBoundLD = 132;   // LDS row stride of the [T][M] tiles (128 + 4 doubles)
+constexpr int kBoundTPW = 5;    // lower 16 x 16 tiles of Q (and of R) per wave: 36 tiles at M = 128 over 8 waves
 
-namespace {
-
-constexpr int kDuboS = 16;     // subjects per workgroup of the fused pass (the group count is ceil(P / kDuboS))
-constexpr int kDuboT = 32;     // largest T of the fused pass
-constexpr int kDuboLD = 132;   // LDS row stride of the [T][M] tiles (128 + 4 doubles)
-constexpr int kDuboTPW = 5;    // lower 16 x 16 tiles of Q (and of R) per wave: 36 tiles at M = 128 over 8 waves
-
-inline int dubo_groups(int P) { return (P + kDuboS - 1) / kDuboS; }
-inline int dubo_tiles(int M) {
+inline int bound_groups(int P) { return (P + kBoundS - 1) / kBoundS; }
+inline int bound_tiles(int M) {
   const int tm = (M + 15) / 16;
   return tm * (tm + 1) / 2;
 }
 
 inline int blocks(int64_t n) { return cdiv(n, 256); }
 
-// Carves a workspace into 256-byte aligned arrays of doubles; a null base only measures (bytes = off at the end).
-struct WsCarve {
-  char* base;
-  size_t off;
-  explicit WsCarve(char* b) : base(b), off(0) {}
-  double* take(size_t n) {
-    double* q = base ? (double*)(base + off) : nullptr;
-    off += align256(n * sizeof(double));
-    return q;
-  }
-  // Gram-adjoint partials of the four Grams X, Kz, K0_p, B_p (gram.hip: 1024 elements per chunk, <= 145 slots)
-  double* take_gram_part(size_t L, size_t N, size_t M, size_t TT) {
-    const size_t chunks = (N * M + 1023) / 1024 + (M * M + 1023) / 1024 + 2 * ((TT + 1023) / 1024);
-    return take(L * chunks * 145);
-  }
+// The sizes every bound's dims begin with: L latent dims, M inducing points, P subjects of T rows (the Hensman
+// bound's P_b), Q covariates.  All zero stands for a null dims, which bound_check refuses like any L < 1.
+struct BoundDims {
+  int L, M, P, T, Q;
 };
 
-__global__ void dubo_fill_kernel(double* p, int n, double v) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] = v;
-}
+// -1 / -2: spec0 / spec1 null or outside every template bucket; -3: L < 1, M or T outside 1..128, P < 1 or Q < 1
+int bound_check(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, const BoundDims& d);
+
+// doubles of the Gram adjoint's partials (gram_bwd_part_bytes of the four jobs of bound_grams_bwd)
+size_t bound_gram_part_doubles(const BoundDims& d);
+
+// epsv[l] = eps, then X = k0(x, z) [L,N,M], Kz = k0(z, z) + eps I [L,M,M], K0st = k0(x_p, x_p) and
+// Bst = k1(x_p, x_p) + noise I [L,P,T,T] in one launch (gram_multi_f64)
+int bound_grams_fwd(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, const BoundDims& d, const double* x,
+                    const double* z, const double* params0, const double* params1, const double* noise, double eps,
+                    double* epsv, double* X, double* Kz, double* K0st, double* Bst, hipStream_t st);
+
+// dparams0, dparams1, dnoise (may be null) = 0, then the four Grams' adjoints dX, dKz, dK0st, dBst contracted into
+// them (gram_bwd_multi_f64 on gpart)
+int bound_grams_bwd(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, const BoundDims& d, const double* x,
+                    const double* z, const double* params0, const double* params1, const double* dX,
+                    const double* dKz, const double* dK0st, const double* dBst, double* dparams0, double* dparams1,
+                    double* dnoise, double* gpart, hipStream_t st);
+
+// info[l]: first failure among Kz[l] (10000 + col), B_{l,p} (20000 + col), W[l] or H[l] (30000 + col); w holds the
+// factorisations' own info words as [L] (Kz), [L, P] (B_p), [L] (W / H)
+void bound_info(int L, int P, const int32_t* w, int32_t* info, hipStream_t st);
+
+// W = sym(Kz + Q); iW0 = spd_inv_small(W) (+ ldW, info); iW = iW0 + iW0 (I - W iW0), the residual E in double-double
+int bound_w_inverse(int L, int M, const double* Kz, const double* Q, double* W, double* iW0, double* E, double* iW,
+                    double* ldW, int32_t* info, hipStream_t st);
+
+// ---- the fused subject walk (512 threads: 8 waves; lane = 16 lk + li) ----
 
 // lower tile t -> (row tile, column tile), row-major over the lower triangle
-__device__ inline void dubo_tile(int t, int& ti, int& tj) {
+__device__ inline void bound_tile(int t, int& ti, int& tj) {
   int i = 0;
   while ((i + 1) * (i + 2) / 2 <= t) ++i;
   ti = i;
   tj = t - i * (i + 1) / 2;
 }
 
-// W = 1/2 ((Kz + Q) + (Kz + Q)^T)
-__global__ void dubo_w_kernel(int L, int M, const double* __restrict__ Kz, const double* __restrict__ Q,
-                              double* __restrict__ W) {
-  const int64_t MM = (int64_t)M * M;
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= L * MM) return;
-  const int64_t b = (e / MM) * MM;
-  const int i = (int)((e % MM) / M), j = (int)(e % M);
-  const int64_t f = b + (int64_t)j * M + i;
-  W[e] = 0.5 * ((Kz[e] + Q[e]) + (Kz[f] + Q[f]));
-}
-
-// E = I - W Y with every dot product accumulated in double-double (two-product by fma, two-sum), rounded to
-// fp64 at the end, and Y1 = Y: the residual of the first inverse of W, for the one Newton step Y1 += Y E.
-// W = K0zz + Q has cond ~1e8..1e9 (K0zz's jitter), so Y = spd_inv_small(W) carries a forward error of ~1e-9
-// |Y|; the bound's W terms (sum iW.R, p.iW p) see it directly (2.3e-9 of the bound on the reference's golden
-// vector, whose own bound is 1e-9), while a residual formed in plain fp64 is as inexact as Y itself.
-__global__ void dubo_resid_kernel(int L, int M, const double* __restrict__ W, const double* __restrict__ Y,
-                                  double* __restrict__ E, double* __restrict__ Y1) {
-#pragma clang fp contract(off)  // the error-free transforms below need every product and sum rounded on its own
-  const int64_t MM = (int64_t)M * M;
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= L * MM) return;
-  const int64_t b = (e / MM) * MM;
-  const int i = (int)((e % MM) / M), j = (int)(e % M);
-  const double* wr = W + b + (int64_t)i * M;
-  const double* yc = Y + b + j;
-  double hi = (i == j) ? 1.0 : 0.0, lo = 0.0;
-  for (int k = 0; k < M; ++k) {
-    const double a = -wr[k], y = yc[(int64_t)k * M];
-    const double ph = a * y, pl = fma(a, y, -ph);  // a y = ph + pl exactly
-    const double s = hi + ph, bb = s - hi;
-    lo += ((hi - (s - bb)) + (ph - bb)) + pl;      // two-sum's error term + the product's
-    hi = s;
+// wave wv owns the lower tiles t = wv + 8 k < nt of Q for the whole walk, in the accumulators Qa[k]
+__device__ __forceinline__ void bound_walk_setup(int wv, int nt, int (&ti)[kBoundTPW], int (&tj)[kBoundTPW],
+                                                 bool (&on)[kBoundTPW], bi_f64x4 (&Qa)[kBoundTPW]) {
+#pragma unroll
+  for (int k = 0; k < kBoundTPW; ++k) {
+    const int t = wv + 8 * k;
+    on[k] = t < nt;
+    bound_tile(on[k] ? t : 0, ti[k], tj[k]);
+    Qa[k] = bi_f64x4{0.0, 0.0, 0.0, 0.0};
   }
-  E[e] = hi + lo;
-  Y1[e] = Y[e];
 }
 
-// info[l]: first failure among Kz[l] (10000 + col), B_{l,p} (20000 + col), W[l] (30000 + col); w holds the
-// factorisations' own info words as [L] (Kz), [L, P] (B_p), [L] (W)
-__global__ void dubo_info_kernel(int L, int P, const int32_t* __restrict__ w, int32_t* __restrict__ info) {
-  const int l = blockIdx.x * blockDim.x + threadIdx.x;
-  if (l >= L) return;
-  int v = 0;
-  if (w[l]) v = 10000 + w[l];
-  for (int p = 0; p < P && !v; ++p)
-    if (w[L + (int64_t)l * P + p]) v = 20000 + w[L + (int64_t)l * P + p];
-  if (!v && w[L + (int64_t)L * P + l]) v = 30000 + w[L + (int64_t)L * P + l];
-  info[l] = v;
+// the padding (rows T.., columns M..) is zeroed once; the walk only rewrites the valid parts
+__device__ __forceinline__ void bound_lds_zero(int tid, double (&sB)[kBoundT][kBoundT + 1],
+                                               double (&sX)[kBoundT][kBoundLD], double (&sY)[kBoundT][kBoundLD]) {
+  for (int e = tid; e < kBoundT * (kBoundT + 1); e += 512) (&sB[0][0])[e] = 0.0;
+  for (int e = tid; e < kBoundT * kBoundLD; e += 512) {
+    (&sX[0][0])[e] = 0.0;
+    (&sY[0][0])[e] = 0.0;
+  }
 }
 
-}  // namespace
+// iB_p [T,T] -> sB with s_bk0 += sum iB_p . K0_p (this thread's elements), X_p [T,M] -> sX
+__device__ __forceinline__ void bound_load_subject(int tid, int T, int M, const double* __restrict__ ib,
+                                                   const double* __restrict__ k0, const double* __restrict__ xp,
+                                                   double (&sB)[kBoundT][kBoundT + 1],
+                                                   double (&sX)[kBoundT][kBoundLD], double& s_bk0) {
+  for (int e = tid; e < T * T; e += 512) {
+    const double b = ib[e];
+    sB[e / T][e % T] = b;
+    s_bk0 += b * k0[e];
+  }
+  for (int e = tid; e < T * M; e += 512) sX[e / M][e % M] = xp[e];
+}
+
+// one 16 x 16 tile at (r0, c0) of iBK_p = iB_p X_p on v_mfma_f64_16x16x4 (C[(lane >> 4) + 4 r][lane & 15]) -> sY
+// and HBM (yp: iBK_p [T,M])
+__device__ __forceinline__ void bound_ibk_tile(int r0, int c0, int li, int lk, int T, int M, int T4,
+                                               const double (&sB)[kBoundT][kBoundT + 1],
+                                               const double (&sX)[kBoundT][kBoundLD],
+                                               double (&sY)[kBoundT][kBoundLD], double* __restrict__ yp) {
+  bi_f64x4 acc = {0.0, 0.0, 0.0, 0.0};
+  for (int kk = 0; kk < T4; kk += 4)
+    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(sB[r0 + li][kk + lk], sX[kk + lk][c0 + li], acc, 0, 0, 0);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int i = r0 + lk + 4 * r, j = c0 + li;
+    sY[i][j] = acc[r];
+    if (i < T && j < M) yp[(int64_t)i * M + j] = acc[r];
+  }
+}
+
+// this wave's tiles of Q (or of R) into the group's partial, tile t at pp[256 t ..) in accumulator order
+__device__ __forceinline__ void bound_store_tiles(double* __restrict__ pp, int wv, int lane,
+                                                  const bool (&on)[kBoundTPW], const bi_f64x4 (&Qa)[kBoundTPW]) {
+#pragma unroll
+  for (int k = 0; k < kBoundTPW; ++k) {
+    if (on[k]) {
+      const int t = wv + 8 * k;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) pp[((int64_t)t * 4 + r) * 64 + lane] = Qa[k][r];
+    }
+  }
+}
+
+// the reduce kernels' tile branch (256 threads): lower tile t of o [M,M] = the G groups' partials at pl[256 b ..),
+// added in group order and mirrored into the upper triangle (a diagonal tile holds both of its halves itself)
+__device__ __forceinline__ void bound_reduce_tile(int M, int G, int64_t pstride, const double* __restrict__ pl, int b,
+                                                  int t, int tid, double* __restrict__ o) {
+  double sum = 0.0;
+  for (int g = 0; g < G; ++g) sum += pl[g * pstride + (int64_t)b * 256 + tid];
+  const int r = tid >> 6, lane = tid & 63;
+  int ti, tj;
+  bound_tile(t, ti, tj);
+  const int i = (ti << 4) + (lane >> 4) + 4 * r, j = (tj << 4) + (lane & 15);
+  if (i < M && j < M) {
+    o[(int64_t)i * M + j] = sum;
+    if (ti != tj) o[(int64_t)j * M + i] = sum;
+  }
+}
+
 }  // namespace lvae

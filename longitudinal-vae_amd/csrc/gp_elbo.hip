@@ -1,6 +1,7 @@
 // gp_elbo.hip -- full-batch sampled GP ELBO (type_KL 'GPapprox', elbo_functions.py:36-84) of all L latent dims and
 // all S samples of the latent, and its analytic adjoint.  fp64 throughout; subjects are P blocks of T consecutive
-// rows, N = P T.  The notation is dubo.hip's; what the two share is gp_bound.hpp.
+// rows, N = P T.  The notation is dubo.hip's; what the two share (and share with hensman.hip) is gp_bound.hpp /
+// gp_bound.hip.
 //
 // Per latent dim (nothing here depends on the sample):
 //   X = k0(x, z) [N,M]   Kz = k0(z, z) + eps I   K0_p = k0(x_p, x_p)   B_p = k1(x_p, x_p) + noise I
@@ -10,7 +11,7 @@
 //   p_s = sum_p iBK_p^T y_{p,s}   w_s = iW p_s   q_s = sum_p y_{p,s}^T iB_p y_{p,s} - p_s.w_s
 //   elbo[s][l] = -N/2 log 2 pi - 1/2 (-log|Kz| + sum_p log|B_p| + log|W| + q_s) - 1/2 (sum iB.K0 - sum Q.iK)
 // The data-sized products (iBK, Q, Pm = [p_s], s_p = iB_p Y_p, the sums) are ONE pass over the subjects
-// (gp_elbo_subject_kernel): a workgroup walks kDuboS consecutive subjects with Q and Pm in MFMA accumulators and
+// (gp_elbo_subject_kernel): a workgroup walks kBoundS consecutive subjects with Q and Pm in MFMA accumulators and
 // writes one partial; gp_elbo_reduce_kernel adds the partials in group order (no atomics: bit-reproducible).
 // T > 32 takes batched gemm_small launches instead.
 //
@@ -30,7 +31,12 @@ constexpr int kGeScal = 24;   // scalar slots per dim: 0 sum iB.K0, 1 sum log|B_
 constexpr double kHalfLog2Pi = 0.91893853320467274178;
 
 // doubles of one (dim, group) partial: Q's lower tiles in accumulator order, Pm [128][16], the scalars
-inline int64_t ge_part_stride(int M) { return (int64_t)dubo_tiles(M) * 256 + 128 * kGeS + kGeScal; }
+inline int64_t ge_part_stride(int M) { return (int64_t)bound_tiles(M) * 256 + 128 * kGeS + kGeScal; }
+
+// (a null d: all zero, which bound_check answers with -3)
+inline BoundDims ge_dims(const lvae_gp_elbo_dims* d) {
+  return d ? BoundDims{d->L, d->M, d->P, d->T, d->Q} : BoundDims{};
+}
 
 struct GWs {
   double *X, *iBK, *U, *Z, *dX;                                   // [L,N,M]
@@ -60,14 +66,14 @@ struct GWs {
     epsv = c.take(L);
     scal = c.take(L * kGeScal);
     Gs = c.take(L);
-    part = c.take(L * (size_t)dubo_groups(d.P) * (size_t)ge_part_stride(d.M));
+    part = c.take(L * (size_t)bound_groups(d.P) * (size_t)ge_part_stride(d.M));
     info = (int32_t*)c.take(L * (2 + (size_t)d.P));
-    gpart = c.take_gram_part(L, N, M, TT);
+    gpart = c.take(bound_gram_part_doubles(ge_dims(&d)));
     bytes = c.off;
   }
 };
 
-// The fused subject pass: grid (groups, L), 512 threads.  Group g walks subjects [g kDuboS, (g + 1) kDuboS).
+// The fused subject pass: grid (groups, L), 512 threads.  Group g walks subjects [g kBoundS, (g + 1) kBoundS).
 // Per subject: iB_p [T,T], X_p [T,M] and the samples Y_p [T,16] (columns S.. zero) into LDS, zero padded to whole
 // MFMA steps; iBK_p = iB_p X_p and s_p = iB_p Y_p on v_mfma_f64_16x16x4 (C[(lane >> 4) + 4 r][lane & 15]), iBK_p
 // -> LDS and HBM, s_p -> HBM with y.s summed per lane (a lane's column IS its sample); then Q += X_p^T iBK_p on
@@ -81,47 +87,30 @@ __global__ __launch_bounds__(512) void gp_elbo_subject_kernel(int M, int P, int 
                                                               const double* __restrict__ y,
                                                               double* __restrict__ iBK, double* __restrict__ sbuf,
                                                               double* __restrict__ part) {
-  __shared__ double sB[kDuboT][kDuboT + 1];
-  __shared__ double sX[kDuboT][kDuboLD];
-  __shared__ double sY[kDuboT][kDuboLD];
-  __shared__ double sS[kDuboT][kGeS + 1];
+  __shared__ double sB[kBoundT][kBoundT + 1];
+  __shared__ double sX[kBoundT][kBoundLD];
+  __shared__ double sY[kBoundT][kBoundLD];
+  __shared__ double sS[kBoundT][kGeS + 1];
   __shared__ double sq[8][64];
   __shared__ double red[8];
   const int g = blockIdx.x, l = blockIdx.y, G = gridDim.x;
   const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
   const int tM = (M + 15) >> 4, tT = (T + 15) >> 4, T4 = (T + 3) & ~3;
   const int64_t N = (int64_t)P * T, TT = (int64_t)T * T;
-  int ti[kDuboTPW], tj[kDuboTPW];
-  bool on[kDuboTPW];
-  bi_f64x4 Qa[kDuboTPW];
+  int ti[kBoundTPW], tj[kBoundTPW];
+  bool on[kBoundTPW];
+  bi_f64x4 Qa[kBoundTPW];
   bi_f64x4 Pa = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int k = 0; k < kDuboTPW; ++k) {
-    const int t = wv + 8 * k;
-    on[k] = t < nt;
-    dubo_tile(on[k] ? t : 0, ti[k], tj[k]);
-    Qa[k] = bi_f64x4{0.0, 0.0, 0.0, 0.0};
-  }
+  bound_walk_setup(wv, nt, ti, tj, on, Qa);
   double s_ys = 0.0, s_bk0 = 0.0, s_ldb = 0.0;
-  // the padding (rows T.., columns M.. / S..) is zeroed once; the walk only rewrites the valid parts
-  for (int e = tid; e < kDuboT * (kDuboT + 1); e += 512) (&sB[0][0])[e] = 0.0;
-  for (int e = tid; e < kDuboT * kDuboLD; e += 512) {
-    (&sX[0][0])[e] = 0.0;
-    (&sY[0][0])[e] = 0.0;
-  }
-  for (int e = tid; e < kDuboT * (kGeS + 1); e += 512) (&sS[0][0])[e] = 0.0;
-  const int p0 = g * kDuboS, p1 = p0 + kDuboS < P ? p0 + kDuboS : P;
+  bound_lds_zero(tid, sB, sX, sY);
+  // (sS likewise: rows T.., sample columns S..)
+  for (int e = tid; e < kBoundT * (kGeS + 1); e += 512) (&sS[0][0])[e] = 0.0;
+  const int p0 = g * kBoundS, p1 = p0 + kBoundS < P ? p0 + kBoundS : P;
   for (int p = p0; p < p1; ++p) {
     __syncthreads();  // the previous subject's readers are done (and the zero fill is visible)
-    const double* ib = iB + ((int64_t)l * P + p) * TT;
-    const double* k0 = K0st + ((int64_t)l * P + p) * TT;
-    for (int e = tid; e < T * T; e += 512) {
-      const double b = ib[e];
-      sB[e / T][e % T] = b;
-      s_bk0 += b * k0[e];
-    }
-    const double* xp = X + ((int64_t)l * N + (int64_t)p * T) * M;
-    for (int e = tid; e < T * M; e += 512) sX[e / M][e % M] = xp[e];
+    bound_load_subject(tid, T, M, iB + ((int64_t)l * P + p) * TT, K0st + ((int64_t)l * P + p) * TT,
+                       X + ((int64_t)l * N + (int64_t)p * T) * M, sB, sX, s_bk0);
     for (int e = tid; e < T * kGeS; e += 512) {
       const int i = e >> 4, s = e & 15;
       if (s < S) sS[i][s] = y[((int64_t)s * N + (int64_t)p * T + i) * L + l];
@@ -132,19 +121,11 @@ __global__ __launch_bounds__(512) void gp_elbo_subject_kernel(int M, int P, int 
     double* yp = iBK + ((int64_t)l * N + (int64_t)p * T) * M;
     double* sp = sbuf + ((int64_t)l * N + (int64_t)p * T) * kGeS;
     for (int tt = wv; tt < tT * tM + tT; tt += 8) {
-      bi_f64x4 acc = {0.0, 0.0, 0.0, 0.0};
       if (tt < tT * tM) {
-        const int r0 = (tt / tM) << 4, c0 = (tt % tM) << 4;
-        for (int kk = 0; kk < T4; kk += 4)
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(sB[r0 + li][kk + lk], sX[kk + lk][c0 + li], acc, 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int i = r0 + lk + 4 * r, j = c0 + li;
-          sY[i][j] = acc[r];
-          if (i < T && j < M) yp[(int64_t)i * M + j] = acc[r];
-        }
+        bound_ibk_tile((tt / tM) << 4, (tt % tM) << 4, li, lk, T, M, T4, sB, sX, sY, yp);
       } else {
         const int r0 = (tt - tT * tM) << 4;
+        bi_f64x4 acc = {0.0, 0.0, 0.0, 0.0};
         for (int kk = 0; kk < T4; kk += 4)
           acc = __builtin_amdgcn_mfma_f64_16x16x4f64(sB[r0 + li][kk + lk], sS[kk + lk][li], acc, 0, 0, 0);
 #pragma unroll
@@ -164,7 +145,7 @@ __global__ __launch_bounds__(512) void gp_elbo_subject_kernel(int M, int P, int 
         Pa = __builtin_amdgcn_mfma_f64_16x16x4f64(sY[kk + lk][ci], sS[kk + lk][li], Pa, 0, 0, 0);
     }
 #pragma unroll
-    for (int k = 0; k < kDuboTPW; ++k) {
+    for (int k = 0; k < kBoundTPW; ++k) {
       if (on[k]) {
         const int ci = (ti[k] << 4) + li, cj = (tj[k] << 4) + li;
         for (int kk = 0; kk < T4; kk += 4)
@@ -173,14 +154,7 @@ __global__ __launch_bounds__(512) void gp_elbo_subject_kernel(int M, int P, int 
     }
   }
   double* pp = part + ((int64_t)l * G + g) * pstride;
-#pragma unroll
-  for (int k = 0; k < kDuboTPW; ++k) {
-    if (on[k]) {
-      const int t = wv + 8 * k;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) pp[((int64_t)t * 4 + r) * 64 + lane] = Qa[k][r];
-    }
-  }
+  bound_store_tiles(pp, wv, lane, on, Qa);
   double* pm = pp + (int64_t)nt * 256;
   if (wv < tM) {
 #pragma unroll
@@ -212,17 +186,7 @@ __global__ __launch_bounds__(256) void gp_elbo_reduce_kernel(int M, int G, int n
   const int b = blockIdx.x, l = blockIdx.y, tid = threadIdx.x;
   const double* pl = part + (int64_t)l * G * pstride;
   if (b < nt) {
-    double sum = 0.0;
-    for (int g = 0; g < G; ++g) sum += pl[g * pstride + (int64_t)b * 256 + tid];
-    const int r = tid >> 6, lane = tid & 63;
-    int ti, tj;
-    dubo_tile(b, ti, tj);
-    const int i = (ti << 4) + (lane >> 4) + 4 * r, j = (tj << 4) + (lane & 15);
-    if (i < M && j < M) {
-      double* o = Q + (int64_t)l * M * M;
-      o[(int64_t)i * M + j] = sum;
-      if (ti != tj) o[(int64_t)j * M + i] = sum;
-    }
+    bound_reduce_tile(M, G, pstride, pl, b, b, tid, Q + (int64_t)l * M * M);
   } else if (b < nt + 8) {
     const int e = (b - nt) * 256 + tid;
     if (e < M * kGeS) {
@@ -367,12 +331,8 @@ __global__ void gp_elbo_gb_kernel(int64_t PTT, int L, const double* __restrict__
 }
 
 int ge_check(const lvae_kernel_spec* s0, const lvae_kernel_spec* s1, const lvae_gp_elbo_dims* d) {
-  if (!s0 || !spec_bucket(s0)) return -1;
-  if (!s1 || !spec_bucket(s1)) return -2;
-  if (!d || d->L < 1 || d->M < 1 || d->M > 128 || d->P < 1 || d->T < 1 || d->T > 128 || d->Q < 1 || d->S < 1 ||
-      d->S > kGeS)
-    return -3;
-  return 0;
+  LVAE_TRY(bound_check(s0, s1, ge_dims(d)));
+  return (d->S < 1 || d->S > kGeS) ? -3 : 0;
 }
 
 }  // namespace
@@ -392,23 +352,16 @@ int lvae_gp_elbo_fwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* 
   if (!workspace || ((uintptr_t)workspace & 255)) return -4;
   hipStream_t st = (hipStream_t)stream;
   const lvae_gp_elbo_dims& d = *dp;
-  const int L = d.L, M = d.M, P = d.P, T = d.T, Q = d.Q, S = d.S, N = P * T;
+  const int L = d.L, M = d.M, P = d.P, T = d.T, S = d.S, N = P * T;
   const int64_t MM = (int64_t)M * M, TT = (int64_t)T * T, NM = (int64_t)N * M;
   const int64_t MS = (int64_t)M * kGeS, NS = (int64_t)N * kGeS;
   GWs w((char*)workspace, d);
-  // Grams
-  dubo_fill_kernel<<<blocks(L), 256, 0, st>>>(w.epsv, L, d.eps);
-  const lvae_xview xv{x, 0, 0, Q}, zv{z, 0, (int64_t)M * Q, Q}, xs{x, (int64_t)T * Q, 0, Q};
-  const lvae_kernel_spec* specs[2] = {spec0, spec1};
-  const GramFwdJob jobs[4] = {{0, 1, N, M, 0, 0, 0, xv, zv, params0, nullptr, w.X, 0, NM, M},
-                              {0, 1, M, M, 0, 0, 0, zv, zv, params0, w.epsv, w.Kz, 0, MM, M},
-                              {0, P, T, T, 0, 0, 0, xs, xs, params0, nullptr, w.K0st, TT, P * TT, T},
-                              {1, P, T, T, 0, 0, 0, xs, xs, params1, noise, w.Bst, TT, P * TT, T}};
-  LVAE_TRY(gram_multi_f64(specs, jobs, 4, L, st));
+  LVAE_TRY(bound_grams_fwd(spec0, spec1, ge_dims(dp), x, z, params0, params1, noise, d.eps, w.epsv, w.X, w.Kz,
+                           w.K0st, w.Bst, st));
   LVAE_TRY(spd_inv_small_f64(M, L, w.Kz, MM, w.iK, MM, w.ldK, w.info, st));
   LVAE_TRY(spd_inv_small_f64(T, L * P, w.Bst, TT, w.iB, TT, w.ldB, w.info + L, st));
-  if (T <= kDuboT) {
-    const int G = dubo_groups(P), nt = dubo_tiles(M);
+  if (T <= kBoundT) {
+    const int G = bound_groups(P), nt = bound_tiles(M);
     const int64_t ps = ge_part_stride(M);
     gp_elbo_subject_kernel<<<dim3(G, L), 512, 0, st>>>(M, P, T, L, S, nt, ps, w.X, w.iB, w.K0st, w.ldB, y, w.iBK,
                                                       w.s, w.part);
@@ -425,14 +378,11 @@ int lvae_gp_elbo_fwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* 
                             kGeS, NS, (int64_t)T * kGeS, L, P, st));
     gp_elbo_scal_kernel<<<L, 256, 0, st>>>(P, T, w.Yp, w.s, w.iB, w.K0st, w.ldB, w.scal);
   }
-  dubo_w_kernel<<<blocks(L * MM), 256, 0, st>>>(L, M, w.Kz, w.Q, w.W);
-  // iW = Y + Y (I - W Y), the residual in double-double (dubo_resid_kernel); Wm = iW Pm
-  LVAE_TRY(spd_inv_small_f64(M, L, w.W, MM, w.iW0, MM, w.ldW, w.info + L + L * P, st));
-  dubo_resid_kernel<<<blocks(L * MM), 256, 0, st>>>(L, M, w.W, w.iW0, w.E, w.iW);
-  LVAE_TRY(gemm_small_f64(0, 0, M, M, M, 1.0, w.iW0, M, MM, 0, w.E, M, MM, 0, 1.0, w.iW, M, MM, 0, L, 1, st));
+  // Wm = iW Pm
+  LVAE_TRY(bound_w_inverse(L, M, w.Kz, w.Q, w.W, w.iW0, w.E, w.iW, w.ldW, w.info + L + L * P, st));
   LVAE_TRY(gemm_small_f64(0, 0, M, kGeS, M, 1.0, w.iW, M, MM, 0, w.Pm, kGeS, MS, 0, 0.0, w.Wm, kGeS, MS, 0, L, 1, st));
   gp_elbo_final_kernel<<<L, 256, 0, st>>>(M, L, S, (double)N, w.Q, w.iK, w.Pm, w.Wm, w.scal, w.ldK, w.ldW, elbo);
-  if (info) dubo_info_kernel<<<blocks(L), 256, 0, st>>>(L, P, w.info, info);
+  if (info) bound_info(L, P, w.info, info, st);
   LVAE_CHECK_LAUNCH();
   return 0;
 }
@@ -447,7 +397,7 @@ int lvae_gp_elbo_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* 
   if (!workspace || ((uintptr_t)workspace & 255)) return -4;
   hipStream_t st = (hipStream_t)stream;
   const lvae_gp_elbo_dims& d = *dp;
-  const int L = d.L, M = d.M, P = d.P, T = d.T, Q = d.Q, S = d.S, N = P * T;
+  const int L = d.L, M = d.M, P = d.P, T = d.T, S = d.S, N = P * T;
   const int64_t MM = (int64_t)M * M, TT = (int64_t)T * T, NM = (int64_t)N * M, LTT = (int64_t)L * P * TT;
   const int64_t TM = (int64_t)T * M, MS = (int64_t)M * kGeS, NS = (int64_t)N * kGeS, TS = (int64_t)T * kGeS;
   GWs w((char*)workspace, d);
@@ -475,16 +425,8 @@ int lvae_gp_elbo_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* 
                           P, st));
   gp_elbo_gb_kernel<<<blocks(LTT), 256, 0, st>>>(P * TT, L, w.Gs, w.iB, w.iBK0iB, w.AAt, w.GB, w.GK0);
   // hyper-parameter gradients through the four Grams
-  (void)zero_async(dparams0, sizeof(double) * L * spec0->n_params, st);
-  (void)zero_async(dparams1, sizeof(double) * L * spec1->n_params, st);
-  if (dnoise) (void)zero_async(dnoise, sizeof(double) * L, st);
-  const lvae_xview xv{x, 0, 0, Q}, zv{z, 0, (int64_t)M * Q, Q}, xs{x, (int64_t)T * Q, 0, Q};
-  const GramBwdJob jobs[4] = {{0, xv, zv, 1, N, M, 0, params0, w.dX, 0, NM, M, dparams0, nullptr, 0, 0},
-                              {0, zv, zv, 1, M, M, 0, params0, w.dKz, 0, MM, M, dparams0, nullptr, 0, 0},
-                              {0, xs, xs, P, T, T, 0, params0, w.GK0, TT, P * TT, T, dparams0, nullptr, 0, 0},
-                              {1, xs, xs, P, T, T, 0, params1, w.GB, TT, P * TT, T, dparams1, dnoise, 0, 0}};
-  const lvae_kernel_spec* specs[2] = {spec0, spec1};
-  LVAE_TRY(gram_bwd_multi_f64(specs, jobs, 4, L, w.gpart, st));
+  LVAE_TRY(bound_grams_bwd(spec0, spec1, ge_dims(dp), x, z, params0, params1, w.dX, w.dKz, w.GK0, w.GB, dparams0,
+                           dparams1, dnoise, w.gpart, st));
   LVAE_CHECK_LAUNCH();
   return 0;
 }

@@ -1,6 +1,7 @@
 // gram_bwd.hpp -- host descriptors of the batched Grams (gram.hip): up to 4 Grams in one forward launch
-// (the Hensman forward), and up to 4 Grams contracted against their G in two launches (used by
-// lvae_gram_bwd_f64 and the Hensman backward).
+// (the inducing-point bounds' four: bound_grams_fwd, gp_bound.hip), and up to 4 Grams contracted against their G
+// in two launches (used by lvae_gram_bwd_f64 and the bounds' bound_grams_bwd, which also sizes its partials with
+// gram_bwd_part_bytes).
 #pragma once
 #include "common.hpp"
 
@@ -20,7 +21,7 @@ struct GramBwdJob {
 
 size_t gram_bwd_part_bytes(const GramBwdJob* jobs, int njobs, int L);
 
-// forward: up to 4 fp64 Grams in one launch (gram_multi_f64; the Hensman forward's four), each as
+// forward: up to 4 fp64 Grams in one launch (gram_multi_f64; the bounds' four), each as
 // lvae_gram_f64's arguments (gx, gy, blk0 filled by gram_multi_f64)
 struct GramFwdJob {
   int spec, nb, n1, n2, gx, gy, blk0;

@@ -18,25 +18,20 @@
 //   dK0_p = c iB_p
 //   dB_p = c (iB - s s^T - iB V iB - iB K0 iB)_p - iBK_p Xq iBK_p^T
 //   (Adam path) dm = 2c iK K0xz^T s + g t,  dH = c iK Q iK + h (iK - iH)
-#include "common.hpp"
-#include "gram_bwd.hpp"
+// (the four Grams and their adjoints, the argument check and the info merge are the DUBO's and the sampled ELBO's
+// too: gp_bound.hpp / gp_bound.hip)
+#include "gp_bound.hpp"
 #include "prof.hpp"
 
 namespace lvae {
-
-
-int spd_inv_small_f64(int n, int batch, const double* A, int64_t stride, double* Ainv, int64_t stride_out,
-                      double* logdet, int32_t* info, hipStream_t st);
-int spd_inv_small2_f64(int n, int nb0, const double* A0, int64_t stride0, double* Ainv0, int64_t stride_out0,
-                       double* logdet0, int32_t* info0, int nb1, const double* A1, int64_t stride1, double* Ainv1,
-                       int64_t stride_out1, double* logdet1, int32_t* info1, hipStream_t st);
-int gemm_small_f64(int ta, int tb, int m, int n, int k, double alpha, const double* A, int lda, int64_t sa1,
-                   int64_t sa2, const double* B, int ldb, int64_t sb1, int64_t sb2, double beta, double* C, int ldc,
-                   int64_t sc1, int64_t sc2, int nb1, int nb2, hipStream_t st);
-
 namespace {
 
 constexpr int kHnSlices = 8;  // workgroups per latent dim of hn_reduce_kernel
+
+// (a null d: all zero, which bound_check answers with -3)
+inline BoundDims hn_dims(const lvae_hensman_dims* d) {
+  return d ? BoundDims{d->L, d->M, d->P_b, d->T, d->Q} : BoundDims{};
+}
 
 struct HWs {
   // [L,B,M]
@@ -52,32 +47,25 @@ struct HWs {
   int32_t* info;
   size_t bytes;
   HWs(char* base, const lvae_hensman_dims& d) {
-    size_t off = 0;
-    auto take = [&](size_t n) {
-      double* p = base ? (double*)(base + off) : nullptr;
-      off += align256(n * sizeof(double));
-      return p;
-    };
+    WsCarve c(base);
     const size_t L = d.L, M = d.M, B = (size_t)d.P_b * d.T, TT = (size_t)d.P_b * d.T * d.T;
-    K0xz = take(L * B * M); iBK = take(L * B * M); dK0xz = take(L * B * M); tBM = take(L * B * M);
+    K0xz = c.take(L * B * M); iBK = c.take(L * B * M); dK0xz = c.take(L * B * M); tBM = c.take(L * B * M);
     double** mm[] = {&K0zz, &iK, &iH, &Q, &iKH, &Y, &Xq, &Z, &GiK, &T1, &dK0zz, &Bn, &iKQ, &tMM};
-    for (auto p : mm) *p = take(L * M * M);
+    for (auto p : mm) *p = c.take(L * M * M);
     double** tt[] = {&K0st, &Bst, &iB, &VB, &iBVB, &K0iB, &iBK0iB, &QB, &GB, &GK0};
-    for (auto p : tt) *p = take(L * TT);
+    for (auto p : tt) *p = c.take(L * TT);
     double** vm[] = {&t, &v1, &w, &a, &tM};
-    for (auto p : vm) *p = take(L * M);
+    for (auto p : vm) *p = c.take(L * M);
     double** vb[] = {&y, &r, &s, &u};
-    for (auto p : vb) *p = take(L * B);
-    ldK = take(L);
-    ldB = take(L * d.P_b);
-    ldH = take(L);
-    epsv = take(L);
-    part = take(L * 16 * kHnSlices);
-    info = (int32_t*)take(L * (2 + d.P_b));
-    // Gram-adjoint partials of the four Grams (gram.hip, kGBChunk = 1024 elements per chunk, <= 145 slots)
-    const size_t chunks = (B * M + 1023) / 1024 + (M * M + 1023) / 1024 + 2 * ((TT + 1023) / 1024);
-    gpart = take(L * chunks * 145);
-    bytes = off;
+    for (auto p : vb) *p = c.take(L * B);
+    ldK = c.take(L);
+    ldB = c.take(L * d.P_b);
+    ldH = c.take(L);
+    epsv = c.take(L);
+    part = c.take(L * 16 * kHnSlices);
+    info = (int32_t*)c.take(L * (2 + d.P_b));
+    gpart = c.take(bound_gram_part_doubles(hn_dims(&d)));
+    bytes = c.off;
   }
 };
 
@@ -101,11 +89,6 @@ __global__ void hn_seg_mask_kernel(int L, int P_b, int T, int M, const int32_t* 
       Bst[f] = (i == j) ? 1.0 : 0.0;
     }
   }
-}
-
-__global__ void fill_kernel(double* p, int n, double v) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] = v;
 }
 
 // r[l][i] = y[l][i] - mu[i][l]
@@ -302,31 +285,7 @@ __global__ void add_transpose_kernel(int L, int M, double a, const double* __res
   Y[e] += a * X[l * MM + (int64_t)j * M + i];
 }
 
-// info[l]: first failure among K0zz[l] (10000 + col), B_{l,p} (20000 + col), H[l] (30000 + col)
-__global__ void hn_info_kernel(int L, int P_b, const int32_t* __restrict__ w, int32_t* __restrict__ info) {
-  const int l = blockIdx.x * blockDim.x + threadIdx.x;
-  if (l >= L) return;
-  int v = 0;
-  if (w[l]) v = 10000 + w[l];
-  for (int p = 0; p < P_b && !v; ++p)
-    if (w[L + l * P_b + p]) v = 20000 + w[L + l * P_b + p];
-  if (!v && w[L + L * P_b + l]) v = 30000 + w[L + L * P_b + l];
-  info[l] = v;
-}
-
-inline int blocks(int64_t n) { return cdiv(n, 256); }
-
 }  // namespace
-
-
-
-static int hensman_check(const lvae_kernel_spec* s0, const lvae_kernel_spec* s1, const lvae_hensman_dims* d) {
-  if (!s0 || !spec_bucket(s0)) return -1;
-  if (!s1 || !spec_bucket(s1)) return -2;
-  if (!d || d->L < 1 || d->M < 1 || d->M > 128 || d->P_b < 1 || d->T < 1 || d->T > 128 || d->Q < 1) return -3;
-  return 0;
-}
-
 }  // namespace lvae
 
 using namespace lvae;
@@ -348,29 +307,21 @@ int lvae_hensman_fwd_part_f64(int part, const lvae_kernel_spec* spec0, const lva
                               const double* H, const double* mu, const double* logv, const double* params0,
                               const double* params1, const double* noise, double* kld, double* grad_m,
                               double* grad_H, int32_t* info, void* workspace, void* stream) {
-  LVAE_TRY(hensman_check(spec0, spec1, dp));
+  LVAE_TRY(bound_check(spec0, spec1, hn_dims(dp)));
   if (part < 0 || part > 2) return -18;
   if (!workspace || ((uintptr_t)workspace & 255)) return -17;
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(LVAE_PH_HENSMAN_FWD, st);
   const lvae_hensman_dims& d = *dp;
-  const int L = d.L, M = d.M, P_b = d.P_b, T = d.T, Q = d.Q, B = P_b * T;
+  const int L = d.L, M = d.M, P_b = d.P_b, T = d.T, B = P_b * T;
   const int64_t MM = (int64_t)M * M, TT = (int64_t)T * T, BM = (int64_t)B * M;
   HWs w((char*)workspace, d);
   const bool ng = d.natural_gradient && grad_m && grad_H;
   const double share = d.ng_prior_share;
   if (part != 2) {
     // Grams (elbo_functions.py:171-176)
-    fill_kernel<<<blocks(L), 256, 0, st>>>(w.epsv, L, d.eps);
-    const lvae_xview xv{x, 0, 0, Q}, zv{z, 0, (int64_t)M * Q, Q}, xs{x, (int64_t)T * Q, 0, Q};
-    // (the four in one launch: gram_multi_f64)
-    const lvae_kernel_spec* specs[2] = {spec0, spec1};
-    const GramFwdJob jobs[4] = {
-        {0, 1, B, M, 0, 0, 0, xv, zv, params0, nullptr, w.K0xz, 0, BM, M},
-        {0, 1, M, M, 0, 0, 0, zv, zv, params0, w.epsv, w.K0zz, 0, MM, M},
-        {0, P_b, T, T, 0, 0, 0, xs, xs, params0, nullptr, w.K0st, TT, P_b * TT, T},
-        {1, P_b, T, T, 0, 0, 0, xs, xs, params1, noise, w.Bst, TT, P_b * TT, T}};
-    LVAE_TRY(gram_multi_f64(specs, jobs, 4, L, st));
+    LVAE_TRY(bound_grams_fwd(spec0, spec1, hn_dims(dp), x, z, params0, params1, noise, d.eps, w.epsv, w.K0xz, w.K0zz,
+                             w.K0st, w.Bst, st));
     if (d.seg_len)
       hn_seg_mask_kernel<<<blocks((int64_t)L * B * M + (int64_t)L * P_b * TT), 256, 0, st>>>(
           L, P_b, T, M, d.seg_len, w.K0xz, w.K0st, w.Bst);
@@ -418,7 +369,7 @@ int lvae_hensman_fwd_part_f64(int part, const lvae_kernel_spec* spec0, const lva
                                                               0, 0);
     }
     // info: first failing matrix (K0zz, then B_p, then H) per latent dim
-    if (info) hn_info_kernel<<<blocks(L), 256, 0, st>>>(L, P_b, w.info, info);
+    if (info) bound_info(L, P_b, w.info, info, st);
   }
   LVAE_CHECK_LAUNCH();
   return 0;
@@ -439,12 +390,12 @@ int lvae_hensman_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* 
                          double* dnoise, double* dm, double* dH, void* workspace, void* stream) {
   (void)mu;
   (void)noise;
-  LVAE_TRY(hensman_check(spec0, spec1, dp));
+  LVAE_TRY(bound_check(spec0, spec1, hn_dims(dp)));
   if (!workspace || ((uintptr_t)workspace & 255)) return -21;
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(LVAE_PH_HENSMAN_BWD, st);
   const lvae_hensman_dims& d = *dp;
-  const int L = d.L, M = d.M, P_b = d.P_b, T = d.T, Q = d.Q, B = P_b * T;
+  const int L = d.L, M = d.M, P_b = d.P_b, T = d.T, B = P_b * T;
   const int64_t MM = (int64_t)M * M, TT = (int64_t)T * T, BM = (int64_t)B * M, LTT = (int64_t)L * P_b * TT;
   const double kc = d.P_tot / (2.0 * P_b), kh = 0.5;
   HWs w((char*)workspace, d);
@@ -478,19 +429,8 @@ int lvae_hensman_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* 
   gb_kernel<<<blocks(LTT), 256, 0, st>>>(P_b, T, L, kc, gkld, w.iB, w.s, w.iBVB, w.iBK0iB, w.QB, d.seg_len, w.GB,
                                           w.GK0);
   // hyper-parameter gradients through the four Grams
-  (void)zero_async(dparams0, sizeof(double) * L * spec0->n_params, st);
-  (void)zero_async(dparams1, sizeof(double) * L * spec1->n_params, st);
-  if (dnoise) (void)zero_async(dnoise, sizeof(double) * L, st);
-  const lvae_xview xv{x, 0, 0, Q}, zv{z, 0, (int64_t)M * Q, Q}, xs{x, (int64_t)T * Q, 0, Q};
-  {
-    const GramBwdJob jobs[4] = {
-        {0, xv, zv, 1, B, M, 0, params0, w.dK0xz, 0, BM, M, dparams0, nullptr, 0, 0},
-        {0, zv, zv, 1, M, M, 0, params0, w.dK0zz, 0, MM, M, dparams0, nullptr, 0, 0},
-        {0, xs, xs, P_b, T, T, 0, params0, w.GK0, TT, P_b * TT, T, dparams0, nullptr, 0, 0},
-        {1, xs, xs, P_b, T, T, 0, params1, w.GB, TT, P_b * TT, T, dparams1, dnoise, 0, 0}};
-    const lvae_kernel_spec* specs[2] = {spec0, spec1};
-    LVAE_TRY(gram_bwd_multi_f64(specs, jobs, 4, L, w.gpart, st));
-  }
+  LVAE_TRY(bound_grams_bwd(spec0, spec1, hn_dims(dp), x, z, params0, params1, w.dK0xz, w.dK0zz, w.GK0, w.GB, dparams0,
+                           dparams1, dnoise, w.gpart, st));
   // Adam path: gradients wrt m and H
   if (!d.natural_gradient && dm && dH) {
     LVAE_TRY(gemm_small_f64(0, 0, M, 1, M, 1.0, w.iK, M, MM, 0, w.v1, 1, M, 0, 0.0, w.tM, 1, M, 0, L, 1, st));

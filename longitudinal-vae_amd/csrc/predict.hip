@@ -13,20 +13,10 @@
 // padding blocks of B set to I, padding rows of mu zeroed by the caller).  The k1 term is the
 // reference's dense product over all prediction rows of the test subjects (include[p] = 1),
 // evaluated in chunks of test rows.
-#include "common.hpp"
+#include "small.hpp"
 #include "prof.hpp"
 
 namespace lvae {
-
-int spd_inv_small_f64(int n, int batch, const double* A, int64_t stride, double* Ainv, int64_t stride_out,
-                      double* logdet, int32_t* info, hipStream_t st);
-int spd_inv_small2_f64(int n, int nb0, const double* A0, int64_t stride0, double* Ainv0, int64_t stride_out0,
-                       double* logdet0, int32_t* info0, int nb1, const double* A1, int64_t stride1, double* Ainv1,
-                       int64_t stride_out1, double* logdet1, int32_t* info1, hipStream_t st);
-int gemm_small_f64(int ta, int tb, int m, int n, int k, double alpha, const double* A, int lda, int64_t sa1,
-                   int64_t sa2, const double* B, int ldb, int64_t sb1, int64_t sb2, double beta, double* C, int ldc,
-                   int64_t sc1, int64_t sc2, int nb1, int nb2, hipStream_t st);
-
 namespace {
 
 constexpr int64_t kPredChunkElems = 1 << 24;  // k1(X*, x) chunk: <= 128 MiB of fp64
@@ -38,42 +28,37 @@ struct PWs {
   int64_t chunk_rows;
   size_t bytes;
   PWs(char* base, int L, int M, int P, int T, int Nt) {
-    size_t off = 0;
-    auto take = [&](size_t n) {
-      double* p = base ? (double*)(base + off) : nullptr;
-      off += align256(n * sizeof(double));
-      return p;
-    };
+    WsCarve c(base);
     const size_t NP = (size_t)P * T, LMM = (size_t)L * M * M, LTT = (size_t)L * P * T * T;
-    K0xz = take(L * NP * M);
-    iBK = take(L * NP * M);
-    K0zz = take(LMM);
-    Hm = take(LMM);
-    iK = take(LMM);
-    iH = take(LMM);
-    Bst = take(LTT);
-    iB = take(LTT);
-    iBmu = take(L * NP);
-    t = take(L * NP);
-    muT = take(L * NP);
-    muTm = take(L * NP);
-    w = take((size_t)L * M);
-    v = take((size_t)L * M);
-    a = take((size_t)L * M);
-    b = take((size_t)L * M);
-    rr = take((size_t)L * M);
-    K0Xz = take((size_t)L * Nt * M);
-    out1 = take((size_t)L * Nt);
+    K0xz = c.take(L * NP * M);
+    iBK = c.take(L * NP * M);
+    K0zz = c.take(LMM);
+    Hm = c.take(LMM);
+    iK = c.take(LMM);
+    iH = c.take(LMM);
+    Bst = c.take(LTT);
+    iB = c.take(LTT);
+    iBmu = c.take(L * NP);
+    t = c.take(L * NP);
+    muT = c.take(L * NP);
+    muTm = c.take(L * NP);
+    w = c.take((size_t)L * M);
+    v = c.take((size_t)L * M);
+    a = c.take((size_t)L * M);
+    b = c.take((size_t)L * M);
+    rr = c.take((size_t)L * M);
+    K0Xz = c.take((size_t)L * Nt * M);
+    out1 = c.take((size_t)L * Nt);
     int64_t rows = kPredChunkElems / ((int64_t)L * (int64_t)NP);
     if (rows < 1) rows = 1;
     if (rows > Nt) rows = Nt;
     chunk_rows = rows;
-    K1 = take((size_t)L * rows * NP);
-    ldK = take(L);
-    ldH = take(L);
-    ldB = take((size_t)L * P);
-    info = (int32_t*)take((size_t)2 * L + (size_t)L * P);
-    bytes = off;
+    K1 = c.take((size_t)L * rows * NP);
+    ldK = c.take(L);
+    ldH = c.take(L);
+    ldB = c.take((size_t)L * P);
+    info = (int32_t*)c.take((size_t)2 * L + (size_t)L * P);
+    bytes = c.off;
   }
 };
 

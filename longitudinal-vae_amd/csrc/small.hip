@@ -7,7 +7,7 @@
 //                   training.py:130-134 (M = 120 -> 128: 8 waves x 8 tiles, 8 + 8 + 8 block steps).
 //   gemm_small    : C = alpha op(A) op(B) + beta C over a two-level batch; 32x32 output tile per
 //                   workgroup on v_mfma_f64_16x16x4f64, K staged through LDS in one pass (K <= 128).
-#include "common.hpp"
+#include "small.hpp"
 #include "blkinv.hpp"
 
 namespace lvae {

@@ -109,6 +109,33 @@ def deviance_upper_bound(covar_module0, covar_module1, likelihood, train_xt, m, 
     return 0.5 * ((tr_iB_D - tr2) + _quad(c, m, P, T) - P * T + c["logdet"] - log_v.sum() + c["tr"])
 
 
+def _f64(t):
+    return t.detach().to(torch.float64).contiguous()
+
+
+def _bound_fwd(name, what, fwd, ws_bytes, out_shape, spec0, spec1, dims, params0, params1, noise, x, z, data):
+    """One all-dims forward (lvae_dubo_fwd_f64 / lvae_gp_elbo_fwd_f64) on fp64 copies of the inputs: ``data`` are the
+    call's own tensors between z and params0.  Returns (out, the tensors the backward needs: p0, p1, nz, x, z, *data,
+    workspace)."""
+    p0, p1, nz, x64, z64 = _f64(params0), _f64(params1), _f64(noise).reshape(-1), _f64(x), _f64(z)
+    d64 = [_f64(t) for t in data]
+    dev = d64[0].device
+    ws = torch.empty(int(ws_bytes(dims)), dtype=torch.uint8, device=dev)
+    out = torch.empty(out_shape, dtype=torch.float64, device=dev)
+    info = torch.empty(dims.L, dtype=torch.int32, device=dev)
+    rc = fwd(spec0, spec1, dims, _lib.ptr(x64), _lib.ptr(z64), *[_lib.ptr(t) for t in d64], _lib.ptr(p0),
+             _lib.ptr(p1), _lib.ptr(nz), _lib.ptr(out), _lib.ptr(info), _lib.ptr(ws), _lib.stream_ptr())
+    _lib.check(rc, name + "_fwd")
+    _check_info(info, what + " cholesky (10000+col: K0zz, 20000+col: B_st, 30000+col: W)")
+    return out, (p0, p1, nz, x64, z64, *d64, ws)
+
+
+def _cast_back(ctx, dp0, dp1, dnz):
+    """(dparams0, dparams1, dnoise) in the dtypes (and the noise's shape) the forward was given"""
+    t0, t1, tn, nshape = ctx.dtypes[:4]
+    return dp0.to(t0), dp1.to(t1), dnz.to(tn).reshape(nshape)
+
+
 class _DuboFn(torch.autograd.Function):
     """dubo [L] of all latent dims in one batched HIP pass (lvae_dubo_fwd_f64) with its analytic adjoint
     (lvae_dubo_bwd_f64); z is not differentiated."""
@@ -116,19 +143,9 @@ class _DuboFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, params0, params1, noise, mu, logv, x, z, spec0, spec1, dims):
         lib = _lib.lib()
-        dev = mu.device
-        f64 = lambda t: t.detach().to(torch.float64).contiguous()
-        p0, p1, nz, mu64, lv64, x64, z64 = f64(params0), f64(params1), f64(noise).reshape(-1), f64(mu), f64(logv), \
-            f64(x), f64(z)
-        ws = torch.empty(int(lib.lvae_dubo_workspace_size(dims)), dtype=torch.uint8, device=dev)
-        dubo = torch.empty(dims.L, dtype=torch.float64, device=dev)
-        info = torch.empty(dims.L, dtype=torch.int32, device=dev)
-        rc = lib.lvae_dubo_fwd_f64(spec0, spec1, dims, _lib.ptr(x64), _lib.ptr(z64), _lib.ptr(mu64), _lib.ptr(lv64),
-                                   _lib.ptr(p0), _lib.ptr(p1), _lib.ptr(nz), _lib.ptr(dubo), _lib.ptr(info),
-                                   _lib.ptr(ws), _lib.stream_ptr())
-        _lib.check(rc, "dubo_fwd")
-        _check_info(info, "deviance_upper_bound cholesky (10000+col: K0zz, 20000+col: B_st, 30000+col: W)")
-        ctx.save_for_backward(p0, p1, nz, mu64, lv64, x64, z64, ws)
+        dubo, saved = _bound_fwd("dubo", "deviance_upper_bound", lib.lvae_dubo_fwd_f64, lib.lvae_dubo_workspace_size,
+                                 dims.L, spec0, spec1, dims, params0, params1, noise, x, z, (mu, logv))
+        ctx.save_for_backward(*saved)
         ctx.spec0, ctx.spec1, ctx.dims = spec0, spec1, dims
         ctx.dtypes = (params0.dtype, params1.dtype, noise.dtype, noise.shape, mu.dtype, logv.dtype)
         return dubo
@@ -136,8 +153,8 @@ class _DuboFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gdubo):
         lib = _lib.lib()
-        p0, p1, nz, mu64, lv64, x64, z64, ws = ctx.saved_tensors
-        g = gdubo.detach().to(torch.float64).reshape(-1).contiguous()
+        p0, p1, nz, x64, z64, mu64, lv64, ws = ctx.saved_tensors
+        g = _f64(gdubo).reshape(-1)
         dmu, dlv = torch.empty_like(mu64), torch.empty_like(lv64)
         dp0, dp1, dnz = torch.empty_like(p0), torch.empty_like(p1), torch.empty_like(nz)
         rc = lib.lvae_dubo_bwd_f64(ctx.spec0, ctx.spec1, ctx.dims, _lib.ptr(x64), _lib.ptr(z64), _lib.ptr(mu64),
@@ -145,9 +162,8 @@ class _DuboFn(torch.autograd.Function):
                                    _lib.ptr(dmu), _lib.ptr(dlv), _lib.ptr(dp0), _lib.ptr(dp1), _lib.ptr(dnz),
                                    _lib.ptr(ws), _lib.stream_ptr())
         _lib.check(rc, "dubo_bwd")
-        t0, t1, tn, nshape, tmu, tlv = ctx.dtypes
-        return (dp0.to(t0), dp1.to(t1), dnz.to(tn).reshape(nshape), dmu.to(tmu), dlv.to(tlv), None, None, None,
-                None, None)
+        tmu, tlv = ctx.dtypes[4:]
+        return (*_cast_back(ctx, dp0, dp1, dnz), dmu.to(tmu), dlv.to(tlv), None, None, None, None, None)
 
 
 def _dubo_noise(likelihoods, L):
@@ -215,18 +231,9 @@ class _GpElboFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, params0, params1, noise, y, x, z, spec0, spec1, dims):
         lib = _lib.lib()
-        dev = y.device
-        f64 = lambda t: t.detach().to(torch.float64).contiguous()
-        p0, p1, nz, y64, x64, z64 = f64(params0), f64(params1), f64(noise).reshape(-1), f64(y), f64(x), f64(z)
-        ws = torch.empty(int(lib.lvae_gp_elbo_workspace_size(dims)), dtype=torch.uint8, device=dev)
-        out = torch.empty(dims.S, dims.L, dtype=torch.float64, device=dev)
-        info = torch.empty(dims.L, dtype=torch.int32, device=dev)
-        rc = lib.lvae_gp_elbo_fwd_f64(spec0, spec1, dims, _lib.ptr(x64), _lib.ptr(z64), _lib.ptr(y64), _lib.ptr(p0),
-                                      _lib.ptr(p1), _lib.ptr(nz), _lib.ptr(out), _lib.ptr(info), _lib.ptr(ws),
-                                      _lib.stream_ptr())
-        _lib.check(rc, "gp_elbo_fwd")
-        _check_info(info, "elbo_batched cholesky (10000+col: K0zz, 20000+col: B_st, 30000+col: W)")
-        ctx.save_for_backward(p0, p1, nz, y64, x64, z64, ws)
+        out, saved = _bound_fwd("gp_elbo", "elbo_batched", lib.lvae_gp_elbo_fwd_f64, lib.lvae_gp_elbo_workspace_size,
+                                (dims.S, dims.L), spec0, spec1, dims, params0, params1, noise, x, z, (y,))
+        ctx.save_for_backward(*saved)
         ctx.spec0, ctx.spec1, ctx.dims = spec0, spec1, dims
         ctx.dtypes = (params0.dtype, params1.dtype, noise.dtype, noise.shape, y.dtype)
         return out
@@ -234,16 +241,15 @@ class _GpElboFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gelbo):
         lib = _lib.lib()
-        p0, p1, nz, y64, x64, z64, ws = ctx.saved_tensors
-        g = gelbo.detach().to(torch.float64).contiguous()
+        p0, p1, nz, x64, z64, y64, ws = ctx.saved_tensors
+        g = _f64(gelbo)
         dy = torch.empty_like(y64)
         dp0, dp1, dnz = torch.empty_like(p0), torch.empty_like(p1), torch.empty_like(nz)
         rc = lib.lvae_gp_elbo_bwd_f64(ctx.spec0, ctx.spec1, ctx.dims, _lib.ptr(x64), _lib.ptr(z64), _lib.ptr(y64),
                                       _lib.ptr(p0), _lib.ptr(p1), _lib.ptr(nz), _lib.ptr(g), _lib.ptr(dy),
                                       _lib.ptr(dp0), _lib.ptr(dp1), _lib.ptr(dnz), _lib.ptr(ws), _lib.stream_ptr())
         _lib.check(rc, "gp_elbo_bwd")
-        t0, t1, tn, nshape, ty = ctx.dtypes
-        return dp0.to(t0), dp1.to(t1), dnz.to(tn).reshape(nshape), dy.to(ty), None, None, None, None, None
+        return (*_cast_back(ctx, dp0, dp1, dnz), dy.to(ctx.dtypes[4]), None, None, None, None, None)
 
 
 ELBO_MAX_SAMPLES = 16   # samples of one lvae_gp_elbo_* call (the columns of one MFMA tile)

@@ -19,8 +19,8 @@ CFG = dict(cat_kernel=[2], bin_kernel=[], sqexp_kernel=[0],
                            {'cont_covariate': 1, 'cat_covariate': 4}],
            bin_int_kernel=[], covariate_missing_val=[])
 EPS = 1e-6
-SUBJECTS_PER_WORKGROUP = 16   # kDuboS of csrc/dubo.hip: the fused pass runs ceil(P / 16) workgroups per dim
-FAST_T = 32                   # kDuboT: larger T takes the batched-product route
+SUBJECTS_PER_WORKGROUP = 16   # kBoundS of csrc/gp_bound.hpp: the fused pass runs ceil(P / 16) workgroups per dim
+FAST_T = 32                   # kBoundT: larger T takes the batched-product route
 
 # id: (P, T, M, noise of dim 0); every case has L = 3
 CASES = {

@@ -35,17 +35,8 @@ def samples(cid, S):
     return y, g
 
 
-def _raw_grads(k0, k1, lik):
-    if isinstance(k0, list):
-        return (torch.stack([torch.cat([p.grad for _, p in k.named_parameters()]) for k in k0]),
-                torch.stack([torch.cat([p.grad for _, p in k.named_parameters()]) for k in k1]),
-                torch.cat([lk._log_noise.grad for lk in lik]))
-    return (torch.stack([p.grad for _, p in k0.named_parameters()], 1),
-            torch.stack([p.grad for _, p in k1.named_parameters()], 1), lik._log_noise.grad)
-
-
 def _collect(vals, y, k0, k1, lik):
-    d0, d1, dn = _raw_grads(k0, k1, lik)
+    d0, d1, dn = D._raw_grads(k0, k1, lik)
     out = dict(elbo=vals, dy=y.grad, draw0=d0, draw1=d1, dnoise=dn)
     return {k: v.detach().cpu().clone() for k, v in out.items()}
 
