@@ -19,6 +19,8 @@
  *   covar_module(x1, x2).evaluate()       -> lvae_gram_*            (GP_model.py:31-144,
  *                                             kernel_gen.py:9-310, call sites elbo_functions.py:22,56,171-174)
  *   autograd of that Gram wrt (scale, lengthscale) -> lvae_gram_bwd_*
+ *   autograd of that Gram wrt its second input (learnable inducing points, LVAE.py:204-208, 269;
+ *                                             training.py:349) -> lvae_gram_bwd_x2_f64, lvae_*_bwd_z_f64
  *   torch.cholesky(K1) on N x N           -> lvae_potrf_f64 / _f32 (elbo_functions.py:26)
  *   torch.cholesky_solve(B, LK1)          -> lvae_potrs_f64 / _f32, lvae_trsm_* (elbo_functions.py:27-28)
  *   torch.cholesky / cholesky_solve(I) / log-det on N x N -> lvae_spd_inv_chol_f32
@@ -101,6 +103,32 @@ int lvae_gram_bwd_f64(const lvae_kernel_spec* spec, lvae_xview x1, lvae_xview x2
                       int n2, const double* params, const double* G, int64_t gstride_b,
                       int64_t gstride_l, int64_t ldg, double* dparams, double* ddiag, void* workspace,
                       void* stream);
+
+/* Input adjoint of lvae_gram_f64 with respect to its second operand (what autograd gives the reference for a
+ * covar_module(x1, x2).evaluate() whose x2 requires grad: the inducing inputs, LVAE.py:204-208, 269 and
+ * training.py:349, which the reference leaves commented out):
+ *   dx2[b, l, j, q] = sum_{i < n1} G[b,l,i,j] * d k_l(x1[b,l,i], x2[b,l,j]) / d x2[b,l,j,q]    j < n2, q < Q
+ * G element (b,l,i,j) at G[b*gstride_b + l*gstride_l + i*gstride_i + j*gstride_j]: a caller passes G transposed
+ * through its strides, and gets the FIRST operand's adjoint by swapping x1 and x2 and passing G^T (every factor is
+ * symmetric in its two arguments).  Per factor on column d, with a = x1[.., d], b = x2[.., d] and v the value of
+ * the factor's component (scale and the other factors included): LVAE_CAT, LVAE_BIN: 0 (autograd through the
+ * reference's == comparisons); LVAE_RBF: v (a - b) / l^2; LVAE_PER: v (2 pi / (p l^2)) sin(2 pi (a - b) / p) (0 at
+ * a == b, as autograd through abs); LVAE_LIN: a times the component's other factors.  A column no differentiable
+ * factor reads gets exact zeros.  An element with G == 0 is skipped, as in lvae_gram_bwd_f64: it adds nothing even
+ * where the kernel value or its derivative is not finite (autograd would give 0 * inf = NaN there).
+ * dx2 [nb, L, n2, Q] (contiguous, fp64) is OVERWRITTEN; x1 / x2 may broadcast
+ * (stride 0).  fp64 throughout, both template buckets, factor dims below 32, arbitrary n1 / n2.  No atomics and a
+ * fixed summation order (the same inputs give the same bits): each block of 64 rows of G writes its partial
+ * [n2, min(Q, 32)] to the workspace, a second launch adds the blocks in row order.  workspace:
+ * lvae_gram_bwd_x2_workspace_size(nb, L, n1, n2, Q) bytes (a multiple of 256; 0 for arguments the call rejects).
+ * Returns 0, LVAE_ERR_LAUNCH, or before any launch, checked in this order, with lvae_gram_bwd_f64's codes for the
+ * faults the two share: -1 (spec NULL, outside every template bucket, or a factor dim >= 32) -4 (nb < 1, L < 1,
+ * n1 < 0, n2 < 0, or Q < 1 + the largest column the spec reads) -8 (params NULL) -9 (G NULL) -13 (dx2 NULL)
+ * -15 (workspace NULL).  n1 == 0 writes zeros to dx2 and returns 0; n2 == 0 writes nothing and returns 0.     */
+size_t lvae_gram_bwd_x2_workspace_size(int nb, int L, int n1, int n2, int Q);
+int lvae_gram_bwd_x2_f64(const lvae_kernel_spec* spec, lvae_xview x1, lvae_xview x2, int nb, int L, int n1, int n2,
+                         int Q, const double* params, const double* G, int64_t gstride_b, int64_t gstride_l,
+                         int64_t gstride_i, int64_t gstride_j, double* dx2, void* workspace, void* stream);
 
 /* Fused cross-Gram x vector in fp64, the [L, n1, n2] Gram never written:
  *   out[i, l] = sum_{j < n2} k_l(x1_i, x2_j) v[j, l] + (diag ? diag[l] v[i, l] : 0)      i < n1, l < L
@@ -406,8 +434,8 @@ int lvae_dubo_fwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spe
                       int32_t* info, void* workspace, void* stream);
 /* Backward given the cotangents gdubo [L] (device): dmu, dlogv [P*T, L]; dparams0 [L, P0], dparams1 [L, P1],
  * dnoise [L] (may be NULL); each dim's gradients are scaled by its own gdubo[l].  Outputs are OVERWRITTEN
- * (whatever they held).  Runs on the workspace the forward left (it may be called again on it).  z is not
- * differentiated.                                                                                      */
+ * (whatever they held).  Runs on the workspace the forward left (it may be called again on it).  The gradient
+ * with respect to z is a separate call, lvae_dubo_bwd_z_f64.                                           */
 int lvae_dubo_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, const lvae_dubo_dims* d,
                       const double* x, const double* z, const double* mu, const double* logv,
                       const double* params0, const double* params1, const double* noise, const double* gdubo,
@@ -447,11 +475,43 @@ int lvae_gp_elbo_fwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* 
 /* Backward given the cotangents gelbo [S, L] (device): dy [S, P*T, L]; dparams0 [L, P0], dparams1 [L, P1],
  * dnoise [L] (may be NULL), summed over the dim's samples, each weighted by its own gelbo[s][l].  Outputs are
  * OVERWRITTEN (whatever they held).  Runs on the workspace the forward left (it may be called again on it, with
- * the same bits out).  z is not differentiated.                                                          */
+ * the same bits out).  The gradient with respect to z is a separate call, lvae_gp_elbo_bwd_z_f64.        */
 int lvae_gp_elbo_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, const lvae_gp_elbo_dims* d,
                          const double* x, const double* z, const double* y, const double* params0,
                          const double* params1, const double* noise, const double* gelbo, double* dy,
                          double* dparams0, double* dparams1, double* dnoise, void* workspace, void* stream);
+
+/* Learnable inducing points: the gradient of the three inducing-point bounds with respect to z [L, M, Q] (the
+ * reference gets it from autograd once LVAE.py:204-208, 269 / training.py:349 are uncommented).  Each bound's
+ * backward leaves the cotangents of X = k0(x, z) [L, N, M] and of Kz = k0(z, z) + eps I [L, M, M] in its
+ * workspace; these calls contract them with the kernel's input derivative (lvae_gram_bwd_x2_f64's kernels, three
+ * jobs in one partial launch and one sum launch):
+ *   dz[l] = d/dx2 of k0(x, z) against dX[l] + d/dx2 of k0(z, z) against dKz[l] + d/dx1 of k0(z, z) against dKz[l]
+ * (the last as d/dx2 against dKz[l]^T; the jitter does not depend on z).  dz [L, M, Q] is OVERWRITTEN; columns of
+ * categorical / binary factors and unread columns get exact zeros.  No atomics: the same bits on every call.
+ * The DUBO's and the ELBO's calls first re-form dKz in zworkspace with its terms iK Q iK and iW R iW built from
+ * N x M factors ((X iK)^T (iBK iK), (iBK iW)^T B_p (F iW)): with inducing rows that coincide for k0, the backward's
+ * (iK Q) iK carries rounding times 1 / eps in directions the hyper-parameter adjoint is blind to and dz is not
+ * (gp_bound.hpp).  The Hensman call reads dK0zz as the backward left it.  None of this writes the bound's own
+ * workspace: the backward may run again on it, and so may these calls.
+ * PRECONDITION: the matching lvae_*_bwd_f64 has run on `workspace` since the last forward on it; the cotangent
+ * scaling (gdubo[l], gelbo[s][l], *gkld) is then already inside dX / dKz.  x, z, params0 and d as that call's.
+ * zworkspace: lvae_bound_dz_workspace_size(L, M, N, Q) bytes, N = P T rows (a multiple of 256; 0 for L, M, N or
+ * Q < 1), 256-byte aligned; it is separate so that the bounds' own workspace sizes stay what they were.
+ * With seg_len (Hensman) the padding rows contribute nothing: their rows of dK0xz are exact zeros.  A dim whose
+ * info[l] is non-zero has a meaningless dz[l], like its other gradients; the other dims are unaffected.
+ * Return codes, checked in this order before any launch (nothing is written): -1: spec0 NULL or outside every
+ * template bucket; -3: d NULL or the dims its bound rejects; -1: spec0 reads a column >= min(Q, 32); then
+ * workspace / zworkspace NULL or not 256-byte aligned: -4 / -5 (DUBO, ELBO), -21 / -22 (Hensman).  0 = ok.   */
+size_t lvae_bound_dz_workspace_size(int L, int M, int N, int Q);
+int lvae_dubo_bwd_z_f64(const lvae_kernel_spec* spec0, const lvae_dubo_dims* d, const double* x, const double* z,
+                        const double* params0, double* dz, void* workspace, void* zworkspace, void* stream);
+int lvae_gp_elbo_bwd_z_f64(const lvae_kernel_spec* spec0, const lvae_gp_elbo_dims* d, const double* x,
+                           const double* z, const double* params0, double* dz, void* workspace, void* zworkspace,
+                           void* stream);
+int lvae_hensman_bwd_z_f64(const lvae_kernel_spec* spec0, const lvae_hensman_dims* d, const double* x,
+                           const double* z, const double* params0, double* dz, void* workspace, void* zworkspace,
+                           void* stream);
 
 /* ConvVAE encoder (VAE.py:44-50): y = max_pool2d(relu(x), 2, 2) over planes = N*C planes of H x W
  * (H, W even) fp32, idx = argmax byte (0..3, row-major in the window, first strict maximum);

@@ -320,6 +320,7 @@ __global__ void dubo_rowscale_tt_kernel(int P, int T, int L, const double* __res
 }
 
 // GB = g_l / 2 (iB - iBDiB - iBK0iB - a a^T - GB);  GK0 = g_l / 2 iB
+// (lvae_dubo_bwd_z_f64 reads g_l / 2 back as GK0[l][0] / iB[l][0], bound_dkz_fix_kernel: keep GK0 = (g_l / 2) iB)
 __global__ void dubo_gb_kernel(int P, int T, int L, const double* __restrict__ g, const double* __restrict__ iB,
                                const double* __restrict__ a, const double* __restrict__ iBDiB,
                                const double* __restrict__ iBK0iB, double* __restrict__ GB,
@@ -437,6 +438,21 @@ int lvae_dubo_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spe
                            dnoise, w.gpart, st));
   LVAE_CHECK_LAUNCH();
   return 0;
+}
+
+// dz from the dX / dKz lvae_dubo_bwd_f64 left in the workspace (gdubo[l] is already inside them)
+int lvae_dubo_bwd_z_f64(const lvae_kernel_spec* spec0, const lvae_dubo_dims* dp, const double* x, const double* z,
+                        const double* params0, double* dz, void* workspace, void* zworkspace, void* stream) {
+  const BoundDims bd = dubo_dims(dp);
+  LVAE_TRY(bound_check_z(spec0, bd));
+  if (!workspace || ((uintptr_t)workspace & 255)) return -4;
+  if (!zworkspace || ((uintptr_t)zworkspace & 255)) return -5;
+  hipStream_t st = (hipStream_t)stream;
+  DWs w((char*)workspace, *dp);
+  BoundZWs zw((char*)zworkspace, bd.L, bd.M, bd.P * bd.T, bd.Q);
+  // (w.Z holds U - iBK iK and w.F, w.iWRiW, w.iKQiK, w.GK0 what the backward left)
+  LVAE_TRY(bound_dkz_stable(bd, w.X, w.iK, w.iW, w.U, w.Z, w.F, w.Bst, w.iKQiK, w.iWRiW, w.GK0, w.iB, w.dKz, zw, st));
+  return bound_grams_bwd_z(spec0, bd, x, z, params0, w.dX, zw.dKz, dz, zw.part, st);
 }
 
 }  // extern "C"

@@ -118,6 +118,87 @@ int bound_grams_bwd(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1
   return gram_bwd_multi_f64(specs, jobs, 4, d.L, gpart, st);
 }
 
+namespace {
+// X [N,M] against dX, Kz [M,M] against dKz and against dKz^T as input-adjoint jobs (null pointers: the shapes alone)
+void bound_z_jobs(int M, int N, int Q, const double* x, const double* z, const double* dX, const double* dKz,
+                  GramX2Job (&jobs)[3]) {
+  const int64_t MM = (int64_t)M * M, NM = (int64_t)N * M;
+  const lvae_xview xv{x, 0, 0, Q}, zv{z, 0, (int64_t)M * Q, Q};
+  jobs[0] = {xv, zv, 1, N, M, dX, 0, NM, M, 1, 0, 0, 0, 0};
+  jobs[1] = {zv, zv, 1, M, M, dKz, 0, MM, M, 1, 0, 0, 0, 0};
+  jobs[2] = {zv, zv, 1, M, M, dKz, 0, MM, 1, M, 0, 0, 0, 0};
+}
+}  // namespace
+
+namespace {
+// out = (first ? dKz : out) + h_l (S - T), h_l = GK0[l][0] / iB[l][0]: the factor the backward gave its iB term
+// (g_l / 2 in the DUBO, -G_l / 2 in the ELBO), which is also the factor of T inside dKz
+__global__ void bound_dkz_fix_kernel(int L, int64_t MM, int64_t PTT, int first, const double* __restrict__ dKz,
+                                     const double* __restrict__ S, const double* __restrict__ T,
+                                     const double* __restrict__ GK0, const double* __restrict__ iB,
+                                     double* __restrict__ out) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= L * MM) return;
+  const int64_t l = e / MM;
+  const double h = GK0[l * PTT] / iB[l * PTT];
+  out[e] = (first ? dKz[e] : out[e]) + h * (S[e] - T[e]);
+}
+}  // namespace
+
+BoundZWs::BoundZWs(char* base, int L, int M, int N, int Q) {
+  WsCarve c(base);
+  part = c.take(bound_dz_part_bytes(L, M, N, Q) / sizeof(double));
+  dKz = c.take((size_t)L * M * M);
+  S = c.take((size_t)L * M * M);
+  A = c.take((size_t)L * N * M);
+  G = c.take((size_t)L * N * M);
+  bytes = c.off;
+}
+
+int bound_dkz_stable(const BoundDims& d, const double* X, const double* iK, const double* iW, const double* U,
+                     const double* UmZ, const double* F, const double* Bst, const double* iKQiK,
+                     const double* iWRiW, const double* GK0, const double* iB, const double* dKz,
+                     const BoundZWs& zw, hipStream_t st) {
+  const int L = d.L, M = d.M, P = d.P, T = d.T, N = P * T;
+  const int64_t MM = (int64_t)M * M, TT = (int64_t)T * T, NM = (int64_t)N * M, TM = (int64_t)T * M;
+  // iK Q iK = (X iK)^T (iBK iK) = A^T (U - UmZ)
+  LVAE_TRY(gemm_small_f64(0, 0, N, M, M, 1.0, X, M, NM, 0, iK, M, MM, 0, 0.0, zw.A, M, NM, 0, L, 1, st));
+  LVAE_TRY(gemm_small_f64(1, 0, M, M, N, 1.0, zw.A, M, NM, 0, U, M, NM, 0, 0.0, zw.S, M, MM, 0, L, 1, st));
+  LVAE_TRY(gemm_small_f64(1, 0, M, M, N, -1.0, zw.A, M, NM, 0, UmZ, M, NM, 0, 1.0, zw.S, M, MM, 0, L, 1, st));
+  bound_dkz_fix_kernel<<<blocks(L * MM), 256, 0, st>>>(L, MM, P * TT, 1, dKz, zw.S, iKQiK, GK0, iB, zw.dKz);
+  if (iWRiW) {
+    // iW R iW = U^T D U = U^T B_p (F iW)   (F = iB D iBK)
+    LVAE_TRY(gemm_small_f64(0, 0, N, M, M, 1.0, F, M, NM, 0, iW, M, MM, 0, 0.0, zw.A, M, NM, 0, L, 1, st));
+    LVAE_TRY(gemm_small_f64(0, 0, T, M, T, 1.0, Bst, T, P * TT, TT, zw.A, M, NM, TM, 0.0, zw.G, M, NM, TM, L, P, st));
+    LVAE_TRY(gemm_small_f64(1, 0, M, M, N, 1.0, U, M, NM, 0, zw.G, M, NM, 0, 0.0, zw.S, M, MM, 0, L, 1, st));
+    bound_dkz_fix_kernel<<<blocks(L * MM), 256, 0, st>>>(L, MM, P * TT, 0, dKz, zw.S, iWRiW, GK0, iB, zw.dKz);
+  }
+  LVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+int bound_check_z(const lvae_kernel_spec* s0, const BoundDims& d) {
+  LVAE_TRY(bound_check(s0, s0, d));
+  for (int r = 0; r < s0->n_comp; ++r)
+    for (int f = 0; f < s0->n_fac[r]; ++f)
+      if (s0->dim[r][f] < 0 || s0->dim[r][f] >= (d.Q < 32 ? d.Q : 32)) return -1;  // (dz has Q columns, 32 staged)
+  return 0;
+}
+
+size_t bound_dz_part_bytes(int L, int M, int N, int Q) {
+  GramX2Job jobs[3];
+  bound_z_jobs(M, N, Q, nullptr, nullptr, nullptr, nullptr, jobs);
+  return gram_bwd_x2_part_bytes(jobs, 3, L, Q);
+}
+
+int bound_grams_bwd_z(const lvae_kernel_spec* spec0, const BoundDims& d, const double* x, const double* z,
+                      const double* params0, const double* dX, const double* dKz, double* dz, double* part,
+                      hipStream_t st) {
+  GramX2Job jobs[3];
+  bound_z_jobs(d.M, d.P * d.T, d.Q, x, z, dX, dKz, jobs);
+  return gram_bwd_x2_multi_f64(spec0, jobs, 3, d.L, d.Q, params0, dz, part, st);
+}
+
 void bound_info(int L, int P, const int32_t* w, int32_t* info, hipStream_t st) {
   bound_info_kernel<<<blocks(L), 256, 0, st>>>(L, P, w, info);
 }
@@ -132,3 +213,8 @@ int bound_w_inverse(int L, int M, const double* Kz, const double* Q, double* W, 
 }
 
 }  // namespace lvae
+
+extern "C" size_t lvae_bound_dz_workspace_size(int L, int M, int N, int Q) {
+  if (L < 1 || M < 1 || N < 1 || Q < 1) return 0;
+  return lvae::BoundZWs(nullptr, L, M, N, Q).bytes;
+}

@@ -50,6 +50,38 @@ int bound_grams_bwd(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1
                     const double* dKz, const double* dK0st, const double* dBst, double* dparams0, double* dparams1,
                     double* dnoise, double* gpart, hipStream_t st);
 
+// The z-adjoint the three bounds share.  bound_check_z: -1: spec0 null or outside every template bucket; -3: the
+// dims, as bound_check.  bound_dz_part_bytes: bytes of the partials of bound_grams_bwd_z's three jobs.
+int bound_check_z(const lvae_kernel_spec* spec0, const BoundDims& d);
+size_t bound_dz_part_bytes(int L, int M, int N, int Q);
+// dz[l] [M, Q] = d/dx2 of k0(x, z) against dX[l] + d/dx2 of k0(z, z) against dKz[l] + d/dx1 of k0(z, z) against
+// dKz[l] (= d/dx2 against dKz[l]^T: the kernel is symmetric), as three jobs of gram_bwd_x2_multi_f64 on part; the
+// eps I jitter does not depend on z.  dz is overwritten.
+int bound_grams_bwd_z(const lvae_kernel_spec* spec0, const BoundDims& d, const double* x, const double* z,
+                      const double* params0, const double* dX, const double* dKz, double* dz, double* part,
+                      hipStream_t st);
+
+// The z-adjoint's own workspace (lvae_bound_dz_workspace_size): the input adjoint's partials, and for the DUBO and
+// the ELBO a re-formed dKz with its scratch (S [L,M,M]; A, G [L,N,M]).
+struct BoundZWs {
+  double *part, *dKz, *S, *A, *G;
+  size_t bytes;
+  BoundZWs(char* base, int L, int M, int N, int Q);
+};
+// dKz as the DUBO's / the ELBO's backward left it, with its two terms of the form iK Q iK and iW R iW (null: the
+// ELBO has none) replaced by the same matrices formed from N x M factors, into zw.dKz:
+//   iK Q iK = (X iK)^T (iBK iK),   iW R iW = (iBK iW)^T B_p (F iW)      (UmZ: the backward's Z = U - iBK iK)
+// Inducing rows that coincide for k0 (rows of two subjects at one time point) leave Kz and W singular up to the
+// jitter, iK and iW ~ 1 / eps on the pair's difference direction n; Q n = R n = 0 exactly, so the terms are
+// moderate, but (iK Q) iK carries the rounding of iK Q times 1 / eps, as v n^T.  The hyper-parameter adjoint does
+// not see that (dKz / dtheta has equal columns on the pair), the z-adjoint does (d k(z_i, z_a) / d z_a stands
+// alone).  X iK and iBK iK lose nothing: the two columns of X are the same bits.  The replaced terms enter with
+// the factor the backward used, read back as GK0[l][0] / iB[l][0].
+int bound_dkz_stable(const BoundDims& d, const double* X, const double* iK, const double* iW, const double* U,
+                     const double* UmZ, const double* F, const double* Bst, const double* iKQiK,
+                     const double* iWRiW, const double* GK0, const double* iB, const double* dKz,
+                     const BoundZWs& zw, hipStream_t st);
+
 // info[l]: first failure among Kz[l] (10000 + col), B_{l,p} (20000 + col), W[l] or H[l] (30000 + col); w holds the
 // factorisations' own info words as [L] (Kz), [L, P] (B_p), [L] (W / H)
 void bound_info(int L, int P, const int32_t* w, int32_t* info, hipStream_t st);

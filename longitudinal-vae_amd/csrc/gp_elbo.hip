@@ -320,6 +320,7 @@ __global__ void gp_elbo_dkz_kernel(int L, int64_t MM, const double* __restrict__
 }
 
 // GB = -1/2 (G_l (iB - iBK0iB - GB) - AAt);  GK0 = -G_l / 2 iB   (GB holds (U - Z) iBK^T, AAt A Gam A^T on entry)
+// (lvae_gp_elbo_bwd_z_f64 reads -G_l / 2 back as GK0[l][0] / iB[l][0], bound_dkz_fix_kernel: keep GK0 = (-G_l / 2) iB)
 __global__ void gp_elbo_gb_kernel(int64_t PTT, int L, const double* __restrict__ Gs, const double* __restrict__ iB,
                                   const double* __restrict__ iBK0iB, const double* __restrict__ AAt,
                                   double* __restrict__ GB, double* __restrict__ GK0) {
@@ -429,6 +430,24 @@ int lvae_gp_elbo_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* 
                            dparams1, dnoise, w.gpart, st));
   LVAE_CHECK_LAUNCH();
   return 0;
+}
+
+// dz from the dX / dKz lvae_gp_elbo_bwd_f64 left in the workspace (gelbo[s][l] is already inside them)
+int lvae_gp_elbo_bwd_z_f64(const lvae_kernel_spec* spec0, const lvae_gp_elbo_dims* dp, const double* x,
+                           const double* z, const double* params0, double* dz, void* workspace, void* zworkspace,
+                           void* stream) {
+  LVAE_TRY(ge_check(spec0, spec0, dp));
+  LVAE_TRY(bound_check_z(spec0, ge_dims(dp)));
+  if (!workspace || ((uintptr_t)workspace & 255)) return -4;
+  if (!zworkspace || ((uintptr_t)zworkspace & 255)) return -5;
+  hipStream_t st = (hipStream_t)stream;
+  const BoundDims bd = ge_dims(dp);
+  GWs w((char*)workspace, *dp);
+  BoundZWs zw((char*)zworkspace, bd.L, bd.M, bd.P * bd.T, bd.Q);
+  // (w.Z holds U - iBK iK and w.iKQiK, w.GK0 what the backward left; the ELBO's dKz has no iW R iW term)
+  LVAE_TRY(bound_dkz_stable(bd, w.X, w.iK, nullptr, w.U, w.Z, nullptr, nullptr, w.iKQiK, nullptr, w.GK0, w.iB, w.dKz,
+                            zw, st));
+  return bound_grams_bwd_z(spec0, bd, x, z, params0, w.dX, zw.dKz, dz, zw.part, st);
 }
 
 }  // extern "C"

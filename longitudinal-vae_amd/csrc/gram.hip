@@ -318,6 +318,146 @@ __global__ __launch_bounds__(256) void gram_bwd_sum_kernel(GramBwdJobs J, const 
   }
 }
 
+// Input adjoint: dx2[b,l,j,q] = sum_i G[b,l,i,j] d k_l(x1_i, x2_j) / d x2_{j,q}, up to kGXMaxJobs Grams that share
+// one x2 shape summed into one dx2 (the bounds' z-adjoint: k0(x, z) against dX, k0(z, z) against dKz and dKz^T).
+// Stage 1: one workgroup per (kGXRows rows, kGT columns) block of one (b, l) slice; lane = column, so G is read
+// coalesced along j when gsj == 1, and the wave's row of x1 is an LDS broadcast.  Wave w takes rows w, w + 4, ..
+// of the block; a thread keeps one accumulator per (component, factor) in registers (compile-time indexed), and
+// the four waves then add theirs into the block's [column][covariate] LDS image one after the other, each thread
+// in (component, factor) order on its own row: a fixed order, no atomics.  The image goes to
+// part[job][b l][row chunk][j][q].  Stage 2: dx2[b,l,j,q] = the jobs' chunks added in (job, chunk) order; columns
+// no differentiable factor reads (and columns q >= kMaxQ) get exact zeros.
+constexpr int kGXMaxJobs = 3;
+constexpr int kGXRows = 64;
+
+struct GramX2Jobs {
+  DevSpec s;
+  GramX2Job j[kGXMaxJobs];
+  int njobs, qs, qp;  // qs: columns staged (1 + the largest the spec reads); qp = min(Q, kMaxQ): partial row length
+};
+
+// acc[r][f] += g s_r (d phi_rf / d b) prod_{f' != f} phi_rf'  (b = xj[dim]: the second operand's column)
+template <int MC, int MF>
+__device__ __attribute__((always_inline)) inline void kernel_dx2_acc(const DevSpec& s, const double* __restrict__ xi,
+                                                                     const double* __restrict__ xj,
+                                                                     const double* __restrict__ p, double g,
+                                                                     double (&acc)[MC][MF]) {
+#pragma unroll
+  for (int r = 0; r < MC; ++r) {
+    if (r < s.n_comp) {
+      double phi[MF], dphi[MF];
+#pragma unroll
+      for (int f = 0; f < MF; ++f) {
+        phi[f] = 1.0;
+        dphi[f] = 0.0;
+        if (f >= s.n_fac[r]) continue;
+        const int d = s.dim[r][f];
+        const double a = xi[d], b = xj[d];
+        const int k = s.kind[r][f];
+        if (k == LVAE_CAT) {
+          phi[f] = (a - b == 0.0) ? 1.0 : 0.0;
+        } else if (k == LVAE_BIN) {
+          phi[f] = (a + b == 2.0) ? 1.0 : 0.0;
+        } else if (k == LVAE_RBF) {
+          const double diff = a - b, ell = p[s.param_idx[r][f]];
+          phi[f] = exp(-(diff * diff) / (2.0 * ell * ell));
+          dphi[f] = phi[f] * diff / (ell * ell);
+        } else if (k == LVAE_PER) {
+          const double diff = a - b, ell = p[s.param_idx[r][f]], per = p[s.param_idx[r][f] + 1];
+          const double sn = sin(M_PI * fabs(diff) / per);
+          phi[f] = exp(-2.0 * sn * sn / (ell * ell));
+          dphi[f] = phi[f] * (2.0 * M_PI / (per * ell * ell)) * sin(2.0 * M_PI * diff / per);
+        } else {  // LVAE_LIN
+          phi[f] = a * b;
+          dphi[f] = a;
+        }
+      }
+      const double gs = g * p[s.scale_idx[r]];
+#pragma unroll
+      for (int f = 0; f < MF; ++f) {
+        double o = gs * dphi[f];
+#pragma unroll
+        for (int f2 = 0; f2 < MF; ++f2)
+          if (f2 != f) o *= phi[f2];
+        acc[r][f] += o;
+      }
+    }
+  }
+}
+
+template <int MC, int MF>
+__global__ __launch_bounds__(256) void gram_bwd_x2_part_kernel(GramX2Jobs J, int L, const double* __restrict__ params,
+                                                               double* __restrict__ part) {
+  constexpr int LD = kMaxQ + 1;  // (odd row stride: a wave's 64 rows fall on distinct banks)
+  __shared__ double sx1[kGXRows * kMaxQ];
+  __shared__ double sx2[kGT * LD];
+  __shared__ double sdx[kGT * LD];
+  __shared__ double sp[64];
+  int q = 0;
+  while (q + 1 < J.njobs && (int)blockIdx.x >= J.j[q + 1].blk0) ++q;  // (uniform)
+  const GramX2Job& jb = J.j[q];
+  const DevSpec& s = J.s;
+  const int rb = blockIdx.x - jb.blk0;
+  const int ct = rb % jb.nct, rc = (rb / jb.nct) % jb.nrc, bl = rb / (jb.nct * jb.nrc), b = bl / L, l = bl % L;
+  const int i0 = rc * kGXRows, j0 = ct * kGT, tid = threadIdx.x, qs = J.qs, qp = J.qp;
+  if (tid < s.n_params) sp[tid] = params[(int64_t)l * s.n_params + tid];
+  const double* p1 = jb.x1.ptr + b * jb.x1.stride_b + l * jb.x1.stride_l;
+  const double* p2 = jb.x2.ptr + b * jb.x2.stride_b + l * jb.x2.stride_l;
+  for (int e = tid; e < kGT * qs; e += 256) {
+    const int r = e / qs, c = e % qs;
+    sx1[r * kMaxQ + c] = (i0 + r < jb.n1) ? p1[(int64_t)(i0 + r) * jb.x1.ld + c] : 0.0;
+    sx2[r * LD + c] = (j0 + r < jb.n2) ? p2[(int64_t)(j0 + r) * jb.x2.ld + c] : 0.0;
+  }
+  for (int e = tid; e < kGT * LD; e += 256) sdx[e] = 0.0;
+  __syncthreads();
+  const int w = tid >> 6, jj = tid & 63, j = j0 + jj;
+  double acc[MC][MF];
+#pragma unroll
+  for (int r = 0; r < MC; ++r)
+#pragma unroll
+    for (int f = 0; f < MF; ++f) acc[r][f] = 0.0;
+  if (j < jb.n2) {
+    const double* g = jb.G + b * jb.gsb + l * jb.gsl + (int64_t)j * jb.gsj;
+    for (int ii = w; ii < kGXRows && i0 + ii < jb.n1; ii += 4) {
+      const double gv = g[(int64_t)(i0 + ii) * jb.gsi];
+      if (gv == 0.0) continue;  // (the Hensman bound's padding rows: dK0xz is exactly zero there)
+      kernel_dx2_acc<MC, MF>(s, &sx1[ii * kMaxQ], &sx2[jj * LD], sp, gv, acc);
+    }
+  }
+  for (int ww = 0; ww < 4; ++ww) {
+    if (w == ww && j < jb.n2) {
+#pragma unroll
+      for (int r = 0; r < MC; ++r)
+#pragma unroll
+        for (int f = 0; f < MF; ++f)
+          if (r < s.n_comp && f < s.n_fac[r] && s.kind[r][f] >= LVAE_RBF) sdx[jj * LD + s.dim[r][f]] += acc[r][f];
+    }
+    __syncthreads();
+  }
+  double* out = part + jb.part0 + ((int64_t)(bl * jb.nrc + rc) * jb.n2 + j0) * qp;
+  for (int e = tid; e < kGT * qp; e += 256) {
+    const int r = e / qp, c = e % qp;
+    if (j0 + r < jb.n2) out[e] = sdx[r * LD + c];
+  }
+}
+
+__global__ __launch_bounds__(256) void gram_bwd_x2_sum_kernel(GramX2Jobs J, int64_t total, int n2, int Q,
+                                                              const double* __restrict__ part,
+                                                              double* __restrict__ dx2) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= total) return;
+  const int q = (int)(e % Q), j = (int)((e / Q) % n2);
+  const int64_t bl = e / ((int64_t)Q * n2);
+  double v = 0.0;
+  if (q < J.qp) {
+    for (int k = 0; k < J.njobs; ++k) {
+      const GramX2Job& jb = J.j[k];
+      for (int rc = 0; rc < jb.nrc; ++rc) v += part[jb.part0 + ((bl * jb.nrc + rc) * jb.n2 + j) * J.qp + q];
+    }
+  }
+  dx2[e] = v;
+}
+
 // ------------------------------------------------------------------------------------------
 // Regime B Gram tiles, 4 x 4 micro-tiles.  A 256-thread workgroup owns a 64 x 64 tile; thread
 // (tr, tc) = (tid >> 4, tid & 15) owns rows 4 tr + a and columns 4 tc + c (a, c < 4): per factor
@@ -2017,6 +2157,53 @@ int gram_bwd_multi_f64(const lvae_kernel_spec* const* specs, const GramBwdJob* j
   return 0;
 }
 
+// Input adjoints of up to kGXMaxJobs Grams with one x2 shape [nb, L, n2, Q], summed into dx2 in two launches (see
+// gram_bwd_x2_part_kernel).  part: gram_bwd_x2_part_bytes(...) bytes.
+static_assert(kGXRows == kGT, "gram_bwd_x2_part_kernel stages both row blocks in one loop");
+
+size_t gram_bwd_x2_part_bytes(const GramX2Job* jobs, int njobs, int L, int Q) {
+  const size_t qp = Q < kMaxQ ? Q : kMaxQ;
+  size_t n = 0;
+  for (int q = 0; q < njobs; ++q)
+    n += (size_t)jobs[q].nb * L * cdiv(jobs[q].n1, kGXRows) * jobs[q].n2 * qp;
+  return align256((n > 0 ? n : 1) * sizeof(double));
+}
+
+int gram_bwd_x2_multi_f64(const lvae_kernel_spec* spec, const GramX2Job* jobs, int njobs, int L, int Q,
+                          const double* params, double* dx2, double* part, hipStream_t st) {
+  if (njobs < 1 || njobs > kGXMaxJobs || L < 1 || Q < 1) return -4;
+  const int bucket = spec ? spec_bucket(spec) : 0;
+  if (!bucket || spec_qs(spec) > kMaxQ || spec_qs(spec) > Q) return -1;
+  GramX2Jobs J;
+  J.s = to_dev(spec);
+  J.njobs = njobs;
+  J.qs = spec_qs(spec);
+  J.qp = Q < kMaxQ ? Q : kMaxQ;
+  const int nb = jobs[0].nb, n2 = jobs[0].n2;
+  int64_t blocks = 0, off = 0;
+  for (int q = 0; q < njobs; ++q) {
+    GramX2Job jb = jobs[q];
+    if (jb.nb != nb || jb.n2 != n2 || jb.nb < 1 || jb.n1 < 0 || jb.n2 < 0) return -4;
+    jb.nrc = cdiv(jb.n1, kGXRows), jb.nct = cdiv(jb.n2, kGT);
+    jb.blk0 = (int)blocks, jb.part0 = off;
+    blocks += (int64_t)jb.nrc * jb.nct * nb * L;
+    off += (int64_t)nb * L * jb.nrc * n2 * J.qp;
+    if (blocks > INT32_MAX) return -4;
+    J.j[q] = jb;
+  }
+  if (n2 == 0) return 0;
+  if (blocks > 0) {
+    if (bucket == 1)
+      gram_bwd_x2_part_kernel<8, 2><<<(unsigned)blocks, 256, 0, st>>>(J, L, params, part);
+    else
+      gram_bwd_x2_part_kernel<16, 4><<<(unsigned)blocks, 256, 0, st>>>(J, L, params, part);
+  }
+  const int64_t total = (int64_t)nb * L * n2 * Q;
+  gram_bwd_x2_sum_kernel<<<cdiv(total, 256), 256, 0, st>>>(J, total, n2, Q, part, dx2);
+  LVAE_CHECK_LAUNCH();
+  return 0;
+}
+
 }  // namespace lvae
 
 extern "C" {
@@ -2063,6 +2250,28 @@ int lvae_gram_bwd_f64(const lvae_kernel_spec* spec, lvae_xview x1, lvae_xview x2
   j.gsb = gsb, j.gsl = gsl, j.ldg = ldg, j.dparams = dparams, j.ddiag = ddiag;
   const lvae_kernel_spec* specs[2] = {spec, nullptr};
   return lvae::gram_bwd_multi_f64(specs, &j, 1, L, (double*)workspace, (hipStream_t)stream);
+}
+
+size_t lvae_gram_bwd_x2_workspace_size(int nb, int L, int n1, int n2, int Q) {
+  if (nb < 1 || L < 1 || n1 < 0 || n2 < 0 || Q < 1) return 0;
+  lvae::GramX2Job j{};
+  j.nb = nb, j.n1 = n1, j.n2 = n2;
+  return lvae::gram_bwd_x2_part_bytes(&j, 1, L, Q);
+}
+
+int lvae_gram_bwd_x2_f64(const lvae_kernel_spec* spec, lvae_xview x1, lvae_xview x2, int nb, int L, int n1, int n2,
+                         int Q, const double* params, const double* G, int64_t gsb, int64_t gsl, int64_t gsi,
+                         int64_t gsj, double* dx2, void* workspace, void* stream) {
+  if (!spec || !lvae::spec_bucket(spec) || lvae::spec_qs(spec) > lvae::kMaxQ) return -1;
+  if (nb < 1 || L < 1 || n1 < 0 || n2 < 0 || Q < lvae::spec_qs(spec) || Q < 1) return -4;
+  if (!params) return -8;
+  if (!G) return -9;
+  if (!dx2) return -13;
+  if (!workspace) return -15;
+  lvae::GramX2Job j{};
+  j.x1 = x1, j.x2 = x2, j.nb = nb, j.n1 = n1, j.n2 = n2, j.G = G;
+  j.gsb = gsb, j.gsl = gsl, j.gsi = gsi, j.gsj = gsj;
+  return lvae::gram_bwd_x2_multi_f64(spec, &j, 1, L, Q, params, dx2, (double*)workspace, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -35,4 +35,21 @@ int gram_multi_f64(const lvae_kernel_spec* const* specs, const GramFwdJob* jobs,
 int gram_bwd_multi_f64(const lvae_kernel_spec* const* specs, const GramBwdJob* jobs, int njobs, int L, double* part,
                        hipStream_t st);
 
+// input adjoint: up to 3 Grams of one spec with one x2 shape, d/dx2 of each against its G (element (b, l, i, j) at
+// G[b gsb + l gsl + i gsi + j gsj]) summed into one dx2 [nb, L, n2, Q] in two launches (lvae_gram_bwd_x2_f64 and the
+// bounds' bound_grams_bwd_z; nrc, nct, blk0, part0 filled by gram_bwd_x2_multi_f64)
+struct GramX2Job {
+  lvae_xview x1, x2;
+  int nb, n1, n2;
+  const double* G;
+  int64_t gsb, gsl, gsi, gsj;
+  int nrc, nct, blk0;
+  int64_t part0;
+};
+size_t gram_bwd_x2_part_bytes(const GramX2Job* jobs, int njobs, int L, int Q);
+// -1: spec null, outside every template bucket, or reading a column >= min(Q, 32); -4: a bad count or jobs whose
+// nb / n2 differ; n2 == 0 writes nothing; a job with n1 == 0 adds nothing (dx2 is still overwritten)
+int gram_bwd_x2_multi_f64(const lvae_kernel_spec* spec, const GramX2Job* jobs, int njobs, int L, int Q,
+                          const double* params, double* dx2, double* part, hipStream_t st);
+
 }  // namespace lvae

@@ -444,6 +444,23 @@ int lvae_hensman_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* 
   return 0;
 }
 
+// dz from the dK0xz / dK0zz lvae_hensman_bwd_f64 left in the workspace (*gkld is already inside them).  Varying T
+// needs no mask here: on a padding row q, K0xz's row is zero (hn_seg_mask_kernel), B_p is the identity there, so
+// iB_p's row q is e_q exactly (the Cholesky factor and inverse of blockdiag(B, I) keep the zeros) and iBK's row q
+// = K0xz's = 0; r_q = 0 (resid_kernel), so s_q = 0; hence dK0xz's row q = 2 iBK_q Xq + 2c s_q t^T = 0 exactly, and
+// the input adjoint skips G == 0 as the parameter adjoint does.
+int lvae_hensman_bwd_z_f64(const lvae_kernel_spec* spec0, const lvae_hensman_dims* dp, const double* x,
+                           const double* z, const double* params0, double* dz, void* workspace, void* zworkspace,
+                           void* stream) {
+  const BoundDims bd = hn_dims(dp);
+  LVAE_TRY(bound_check_z(spec0, bd));
+  if (!workspace || ((uintptr_t)workspace & 255)) return -21;
+  if (!zworkspace || ((uintptr_t)zworkspace & 255)) return -22;
+  HWs w((char*)workspace, *dp);
+  BoundZWs zw((char*)zworkspace, bd.L, bd.M, bd.P * bd.T, bd.Q);
+  return bound_grams_bwd_z(spec0, bd, x, z, params0, w.dK0xz, w.dK0zz, dz, zw.part, (hipStream_t)stream);
+}
+
 // ------------------------------------------------------------------------------------------
 // natural-gradient update (training.py:129-135)
 // ------------------------------------------------------------------------------------------

@@ -93,6 +93,13 @@ SIGNATURES = {
     "lvae_gram_bwd_workspace_size": (_SZ, [_I32, _I32, _I32, _I32]),
     "lvae_gram_bwd_f64": (_I32, [_SPEC, XView, XView, _I32, _I32, _I32, _I32, _VP, _VP, _I64, _I64, _I64, _VP,
                                  _VP, _VP, _VP]),
+    "lvae_gram_bwd_x2_workspace_size": (_SZ, [_I32, _I32, _I32, _I32, _I32]),
+    "lvae_gram_bwd_x2_f64": (_I32, [_SPEC, XView, XView, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _I64, _I64, _I64,
+                                    _I64, _VP, _VP, _VP]),
+    "lvae_bound_dz_workspace_size": (_SZ, [_I32, _I32, _I32, _I32]),
+    "lvae_dubo_bwd_z_f64": (_I32, [_SPEC, _DDIMS, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "lvae_gp_elbo_bwd_z_f64": (_I32, [_SPEC, _GDIMS, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "lvae_hensman_bwd_z_f64": (_I32, [_SPEC, _DIMS, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "lvae_kl_closed_padded_n": (_I32, [_I32]),
     "lvae_kl_closed_workspace_size": (_SZ, [_I32, _I32]),
     "lvae_kl_closed_factor_f32": (_I32, [_SPEC, _VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP]),

@@ -408,6 +408,7 @@ class _HensmanFn(torch.autograd.Function):
         ctx.save_for_backward(p0, p1, nz, mu64, lv64, m64, H64, x64, z64, ws)
         ctx.spec0, ctx.spec1, ctx.dims = spec0, spec1, dims
         ctx.dtypes = (params0.dtype, params1.dtype, noise.dtype, noise.shape, mu.dtype, logv.dtype, m.dtype, H.dtype)
+        ctx.z_dtype = z.dtype
         if want_ng:
             # H^-1 stays in the workspace: the natural-gradient update reuses it while H is unchanged
             off = int(lib.lvae_hensman_iH_offset(dims))
@@ -435,9 +436,14 @@ class _HensmanFn(torch.autograd.Function):
                                       _lib.stream_ptr())
         _lib.check(rc, "hensman_bwd")
         t0, t1, tn, nshape, tmu, tlv, tm, tH = ctx.dtypes
+        dz = None
+        if ctx.needs_input_grad[8]:  # learnable inducing points: lvae_hensman_bwd_z_f64 on the backward's cotangents
+            from .gpapprox import _bound_dz
+            dz = _bound_dz("hensman", lib.lvae_hensman_bwd_z_f64, ctx.spec0, d, x64, z64, p0, ws, d.P_b * d.T,
+                           ctx.z_dtype)
         return (dp0.to(t0), dp1.to(t1), dnz.to(tn).reshape(nshape), dmu.to(tmu), dlv.to(tlv),
                 None if dm is None else dm.to(tm), None if dH is None else dH.to(tH),
-                None, None, None, None, None, None, None)
+                None, dz, None, None, None, None, None)
 
 
 def minibatch_KLD_upper_bound(covar_module0, covar_module1, likelihood, latent_dim, m, H, train_xt, mu, log_v, z,

@@ -130,6 +130,19 @@ def _bound_fwd(name, what, fwd, ws_bytes, out_shape, spec0, spec1, dims, params0
     return out, (p0, p1, nz, x64, z64, *d64, ws)
 
 
+def _bound_dz(name, bwd_z, spec0, dims, x64, z64, p0, ws, N, z_dtype):
+    """dz [L, M, Q] of one bound (lvae_dubo_bwd_z_f64 / lvae_gp_elbo_bwd_z_f64 / lvae_hensman_bwd_z_f64) from the
+    cotangents its backward has just left in ``ws``, in z's dtype."""
+    lib = _lib.lib()
+    zws = torch.empty(int(lib.lvae_bound_dz_workspace_size(dims.L, dims.M, int(N), dims.Q)), dtype=torch.uint8,
+                      device=z64.device)
+    dz = torch.empty_like(z64)
+    rc = bwd_z(spec0, dims, _lib.ptr(x64), _lib.ptr(z64), _lib.ptr(p0), _lib.ptr(dz), _lib.ptr(ws), _lib.ptr(zws),
+               _lib.stream_ptr())
+    _lib.check(rc, name + "_bwd_z")
+    return dz.to(z_dtype)
+
+
 def _cast_back(ctx, dp0, dp1, dnz):
     """(dparams0, dparams1, dnoise) in the dtypes (and the noise's shape) the forward was given"""
     t0, t1, tn, nshape = ctx.dtypes[:4]
@@ -138,7 +151,7 @@ def _cast_back(ctx, dp0, dp1, dnz):
 
 class _DuboFn(torch.autograd.Function):
     """dubo [L] of all latent dims in one batched HIP pass (lvae_dubo_fwd_f64) with its analytic adjoint
-    (lvae_dubo_bwd_f64); z is not differentiated."""
+    (lvae_dubo_bwd_f64); a z that requires grad adds lvae_dubo_bwd_z_f64 (nothing runs for one that does not)."""
 
     @staticmethod
     def forward(ctx, params0, params1, noise, mu, logv, x, z, spec0, spec1, dims):
@@ -148,6 +161,7 @@ class _DuboFn(torch.autograd.Function):
         ctx.save_for_backward(*saved)
         ctx.spec0, ctx.spec1, ctx.dims = spec0, spec1, dims
         ctx.dtypes = (params0.dtype, params1.dtype, noise.dtype, noise.shape, mu.dtype, logv.dtype)
+        ctx.z_dtype = z.dtype
         return dubo
 
     @staticmethod
@@ -163,7 +177,11 @@ class _DuboFn(torch.autograd.Function):
                                    _lib.ptr(ws), _lib.stream_ptr())
         _lib.check(rc, "dubo_bwd")
         tmu, tlv = ctx.dtypes[4:]
-        return (*_cast_back(ctx, dp0, dp1, dnz), dmu.to(tmu), dlv.to(tlv), None, None, None, None, None)
+        dz = None
+        if ctx.needs_input_grad[6]:
+            dz = _bound_dz("dubo", lib.lvae_dubo_bwd_z_f64, ctx.spec0, ctx.dims, x64, z64, p0, ws,
+                           ctx.dims.P * ctx.dims.T, ctx.z_dtype)
+        return (*_cast_back(ctx, dp0, dp1, dnz), dmu.to(tmu), dlv.to(tlv), None, dz, None, None, None)
 
 
 def _dubo_noise(likelihoods, L):
@@ -203,8 +221,9 @@ def deviance_upper_bound_batched(latent_dim, covar_module0, covar_module1, likel
     """The DUBO of every latent dim, [L] fp64, from one batched HIP forward (and one batched adjoint):
     ``deviance_upper_bound`` for dim l on (m[:, l], log_v[:, l]).  covar_module0 / covar_module1: batched
     modules or per-dim lists; likelihoods: a batched likelihood or a per-dim list; z: [L, M, Q], [M, Q]
-    (shared) or a per-dim list of [M, Q].  Gradients flow to m, log_v [N, L], the kernels' raw parameters
-    and the noise; z is not differentiated."""
+    (shared) or a per-dim list of [M, Q].  Gradients flow to m, log_v [N, L], the kernels' raw parameters,
+    the noise, and to z in any of its forms when it requires grad (learnable inducing points; zero for the
+    columns of categorical / binary factors, as the reference's autograd)."""
     L = int(latent_dim)
     spec0, params0, spec1, params1, zz = _batched_kernels(L, covar_module0, covar_module1, z, train_xt, P, T)
     if tuple(m.shape) != (P * T, L) or tuple(log_v.shape) != (P * T, L):
@@ -226,7 +245,8 @@ def validation_dubo(latent_dim, covar_module0, covar_module1, likelihood, train_
 
 class _GpElboFn(torch.autograd.Function):
     """elbo [S, L] of all latent dims and S <= 16 samples in one batched HIP pass (lvae_gp_elbo_fwd_f64) with its
-    analytic adjoint (lvae_gp_elbo_bwd_f64); z is not differentiated."""
+    analytic adjoint (lvae_gp_elbo_bwd_f64); a z that requires grad adds lvae_gp_elbo_bwd_z_f64 (nothing runs for
+    one that does not)."""
 
     @staticmethod
     def forward(ctx, params0, params1, noise, y, x, z, spec0, spec1, dims):
@@ -236,6 +256,7 @@ class _GpElboFn(torch.autograd.Function):
         ctx.save_for_backward(*saved)
         ctx.spec0, ctx.spec1, ctx.dims = spec0, spec1, dims
         ctx.dtypes = (params0.dtype, params1.dtype, noise.dtype, noise.shape, y.dtype)
+        ctx.z_dtype = z.dtype
         return out
 
     @staticmethod
@@ -249,7 +270,11 @@ class _GpElboFn(torch.autograd.Function):
                                       _lib.ptr(p0), _lib.ptr(p1), _lib.ptr(nz), _lib.ptr(g), _lib.ptr(dy),
                                       _lib.ptr(dp0), _lib.ptr(dp1), _lib.ptr(dnz), _lib.ptr(ws), _lib.stream_ptr())
         _lib.check(rc, "gp_elbo_bwd")
-        return (*_cast_back(ctx, dp0, dp1, dnz), dy.to(ctx.dtypes[4]), None, None, None, None, None)
+        dz = None
+        if ctx.needs_input_grad[5]:
+            dz = _bound_dz("gp_elbo", lib.lvae_gp_elbo_bwd_z_f64, ctx.spec0, ctx.dims, x64, z64, p0, ws,
+                           ctx.dims.P * ctx.dims.T, ctx.z_dtype)
+        return (*_cast_back(ctx, dp0, dp1, dnz), dy.to(ctx.dtypes[4]), None, dz, None, None, None)
 
 
 ELBO_MAX_SAMPLES = 16   # samples of one lvae_gp_elbo_* call (the columns of one MFMA tile)
@@ -261,7 +286,8 @@ def elbo_batched(latent_dim, covar_module0, covar_module1, likelihoods, train_xt
     one analytic adjoint per group of at most 16 samples (a dim's samples share its Grams and factorisations).
     covar_module0 / covar_module1: batched modules or per-dim lists; likelihoods: a batched likelihood or a
     per-dim list; z: [L, M, Q], [M, Q] (shared) or a per-dim list of [M, Q].  Gradients flow to train_yt, the
-    kernels' raw parameters and the noise; z is not differentiated."""
+    kernels' raw parameters, the noise, and to z in any of its forms when it requires grad (each group of samples
+    adds its own share; autograd sums them)."""
     L = int(latent_dim)
     spec0, params0, spec1, params1, zz = _batched_kernels(L, covar_module0, covar_module1, z, train_xt, P, T)
     single = train_yt.dim() == 2

@@ -202,13 +202,21 @@ class HensmanStep:
     replays it); otherwise m and H are leaf tensors the optimiser owns (H enters as H H^T,
     training.py:108).
     Data parallel: pass ``world`` and a ``grad_hook`` (all-reduce of the Adam gradients) and
-    ``ng_reduce`` (SUM all-reduce of the natural-gradient directions, see lvae_hensman_dims)."""
+    ``ng_reduce`` (SUM all-reduce of the natural-gradient directions, see lvae_hensman_dims).
+    z is not differentiated here: the inducing inputs stay fixed in this step (it is the one GraphedStep captures,
+    and the captured graphs do not hold the z-adjoint); minibatch_KLD_upper_bound itself differentiates a z that
+    requires grad, and DuboStep / ElboStep train one."""
 
     def __init__(self, vae, k0, k1, likelihood, optimiser, m, H, z, P_tot, T, weight=0.15, loss_function="mse",
                  natural_gradient=True, natural_gradient_lr=0.01, eps=1e-6, world=1, grad_hook=None,
                  ng_reduce=None):
         self.vae, self.k0, self.k1, self.lik, self.opt = vae, k0, k1, likelihood, optimiser
-        self.m, self.H, self.z = m, H, z
+        if z.requires_grad:
+            import warnings
+            warnings.warn("HensmanStep keeps the inducing inputs fixed: z.requires_grad is ignored here (z.grad stays "
+                          "None); DuboStep / ElboStep or an eager loop over minibatch_KLD_upper_bound train z",
+                          stacklevel=2)
+        self.m, self.H, self.z = m, H, z.detach()
         self.P_tot, self.T = P_tot, T
         self.weight, self.loss_function = weight, loss_function
         self.ng, self.ng_lr, self.eps = natural_gradient, natural_gradient_lr, eps
@@ -274,8 +282,9 @@ class DuboStep:
     ('mse') or nll + sum_l dubo_l ('nll'), backward; ``apply`` is the optimiser step and the scale constraint.
 
     k0 / k1 / likelihood: batched modules or per-dim lists; z: [L, M, Q], [M, Q] or a per-dim list; X: the full
-    batch's covariates [P*T, Q], subjects in blocks of T rows.  One stream, eager; capture into a HIP graph is
-    untested."""
+    batch's covariates [P*T, Q], subjects in blocks of T rows.  A z that is an nn.Parameter (or a list of them)
+    registered with the optimiser is trained like every other parameter (learnable inducing points).  One stream,
+    eager; capture into a HIP graph is untested."""
 
     def __init__(self, vae, k0, k1, likelihood, optimiser, z, T, weight=0.15, loss_function="mse", eps=1e-6,
                  constrain_scales=True, grad_hook=None):
@@ -328,8 +337,9 @@ class ElboStep:
 
     k0 / k1 / likelihood: batched modules or per-dim lists; z: [L, M, Q], [M, Q] or a per-dim list; X: the full
     batch's covariates [P*T, Q], subjects in blocks of T rows; eps [N, L]: the decoder's draw, eps_gp
-    [num_samples, N, L]: the GP term's draws (each drawn if None).  One stream, eager; capture into a HIP graph is
-    untested."""
+    [num_samples, N, L]: the GP term's draws (each drawn if None).  A z that is an nn.Parameter (or a list of them)
+    registered with the optimiser is trained like every other parameter.  One stream, eager; capture into a HIP
+    graph is untested."""
 
     def __init__(self, vae, k0, k1, likelihood, optimiser, z, T, weight=0.15, loss_function="mse", eps=1e-6,
                  constrain_scales=True, grad_hook=None, num_samples=1):
@@ -393,7 +403,8 @@ def _comm_capturable():
 
 
 class GraphedStep:
-    """A ClosedStep / HensmanStep replayed as HIP graphs.
+    """A ClosedStep / HensmanStep replayed as HIP graphs.  z is not differentiated in a graphed Hensman step: the
+    step holds a detached z, so the captured graphs never contain the z-adjoint (lvae_hensman_bwd_z_f64).
 
     ``inputs`` are static device tensors (img, mask, X, eps) the caller refills in place between
     replays (e.g. ``index_select(..., out=)`` of the next batch).  With no communication the whole

@@ -6,10 +6,12 @@ the HIP Grams and inverses, autograd backward), against (b) lvae_amd.deviance_up
 process with the pivot checks deferred (set_sync_checks(False)); the relative difference of the two values is
 reported too.  DESIGN.md and profiles/dubo_timing.json hold a run.
 
-    python scripts/dubo_timing.py [batched] [out.json]
+    python scripts/dubo_timing.py [batched] [zgrad] [out.json]
 
 ``batched`` times (b) alone (the run to put under ``rocprofv3 --kernel-trace --stats``:
-profiles/dubo_kernel_stats.csv).
+profiles/dubo_kernel_stats.csv).  ``zgrad`` adds (c) = (b) with z.requires_grad (learnable inducing points: the
+backward also runs lvae_dubo_bwd_z_f64), alternating with the others; ``batched zgrad`` under rocprofv3 gave
+profiles/dubo_dz_kernel_stats.csv.
 """
 import json
 import os
@@ -48,7 +50,7 @@ def set_raw(module, raw_rows):
             p.copy_(torch.as_tensor(raw_rows[:, j], dtype=p.dtype))
 
 
-def measure(only_batched, seed=41):
+def measure(only_batched, zgrad=False, seed=41):
     N = P * T
     X = torch.tensor(health_mnist_covariates(P, T, seed=seed))
     gen = torch.Generator().manual_seed(seed)
@@ -78,9 +80,12 @@ def measure(only_batched, seed=41):
         for p in params:
             p.grad = None
 
-    def batched():
+    z_dz = z.clone().requires_grad_()
+    params.append(z_dz)
+
+    def batched(zt=z):
         zero()
-        d = la.deviance_upper_bound_batched(L, k0, k1, lik, X, mu, lv, z, P, T, EPS)
+        d = la.deviance_upper_bound_batched(L, k0, k1, lik, X, mu, lv, zt, P, T, EPS)
         tot = d.sum()
         tot.backward()
         return tot.detach()
@@ -93,6 +98,8 @@ def measure(only_batched, seed=41):
         tot.backward()
         return tot.detach()
     routes = {"batched": batched} if only_batched else {"per_dim": per_dim, "batched": batched}
+    if zgrad:  # learnable inducing points: the same call with z.requires_grad (adds lvae_dubo_bwd_z_f64)
+        routes["batched_dz"] = lambda: batched(z_dz)
     la.set_sync_checks(False)
     ms, outs = {r: [] for r in routes}, {}
     for rep in range(12):
@@ -111,7 +118,7 @@ def measure(only_batched, seed=41):
 
 if __name__ == "__main__":
     args = sys.argv[1:]
-    res = measure("batched" in args)
+    res = measure("batched" in args, "zgrad" in args)
     line = json.dumps(res)
     print(line, flush=True)
     for a in args:
