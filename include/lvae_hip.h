@@ -618,6 +618,55 @@ int lvae_predict_exact_f64(const lvae_kernel_spec* spec, const double* x, int64_
                            const double* tx, int64_t ldt, int nt, double* out, int64_t ld_out, int32_t* info,
                            void* workspace, void* stream);
 
+/* Exact-GP predictive variance (and, optionally, the mean) of the latent functions at test covariates, fp64.  With
+ * K_l = k_l(x, x) + noise_l I = L_l L_l^T:
+ *   out_var[t, l] = k_l(tx_t, tx_t) - |L_l^-1 k_l(x, tx_t)|^2  (+ noise_l when add_noise = 1)
+ * the raw difference (not clamped), element (t, l) at out_var[t*ld_var + l].  Arguments as lvae_predict_exact_f64;
+ * out_mean may be NULL (then mu may be too), and when given it receives lvae_predict_exact_f64's bits (the same
+ * launches).  Route: the Gram and lvae_potrf_f64 as there; then per chunk of c = min(chunk, nt) test rows the
+ * panel k(x, tx_chunk) [L, n, c] by lvae_gram_f64, lvae_trsm_f64 (trans = 0) in place, and one kernel that forms
+ * k(tx, tx) through the spec and subtracts each column's sum of squares in a fixed order (no atomics): the bits
+ * depend on neither the grid nor the chunk, and the [nt, n] cross-Gram is never whole in memory.  n^2 nt fp64 flops
+ * per dim in the solves.  nt == 0: the factor runs (info is written), nothing else is touched.  workspace:
+ * lvae_predict_exact_var_workspace_size(n, nt, L, chunk) bytes (lvae_predict_exact_f64's + 8 L n c; 0 for n < 1,
+ * nt < 0, L < 1 or, with nt > 0, chunk < 1), 256-B aligned.
+ * Returns 0, LVAE_ERR_LAUNCH, or before any launch, in this order: -1 .. -7 as lvae_predict_exact_f64; with
+ * out_mean: -8 (mu NULL) -9 (ld_mu < L); -12 (nt < 0); with nt > 0: -10 (tx NULL) -11 (ldt); with out_mean: -14
+ * (ld_out < L); -15 (info NULL) -16 (workspace NULL or misaligned); with nt > 0: -17 (out_var NULL) -18
+ * (ld_var < L); -19 (add_noise not 0 / 1); with nt > 0: -20 (chunk < 1).                                  */
+size_t lvae_predict_exact_var_workspace_size(int n, int nt, int L, int chunk);
+int lvae_predict_exact_var_f64(const lvae_kernel_spec* spec, const double* x, int64_t ldx, int n, int L,
+                               const double* params, const double* noise, const double* mu, int64_t ld_mu,
+                               const double* tx, int64_t ldt, int nt, double* out_mean, int64_t ld_out,
+                               double* out_var, int64_t ld_var, int add_noise, int chunk, int32_t* info,
+                               void* workspace, void* stream);
+
+/* Predictive variance (and, optionally, the mean) of the inducing-point predictor, in the structured model
+ * lvae_predict_f64's mean assumes: prior K~ = K0xz K0zz^-1 K0zx + blockdiag_p k1(x_p, x_p) (K0zz with eps I),
+ * Sigma = K~ + noise I, Sigma^-1 = iB - iB K0xz H^-1 K0zx iB.  Per latent dim and test row i of subject s:
+ *   q = K0zz^-1 K0zX*_i,  c = k1(x_s, x*_i) on subject s's valid rows (empty when s is not a prediction subject),
+ *   d = iB_s c,  e = K0zx_s d,  G = H - K0zz = K0zx iB K0xz,  w = G q + e,
+ *   out_var[i, l] = K0X*z_i . q + k1(x*_i, x*_i) - (q^T G q + 2 q^T e + c^T d) + w^T H^-1 w  (+ noise_l when add_noise = 1)
+ * = k~** - k~*^T Sigma^-1 k~*, the raw difference (not clamped).  k1 is taken to vanish between subjects (every
+ * component of spec1 carries the id covariate's cat factor).  Arguments as lvae_predict_f64, plus the test-row
+ * layout: test_x's rows grouped by subject, group g = rows [group_start[g], group_start[g + 1]) (device arrays,
+ * n_groups and n_groups + 1 entries) of prediction subject group_subject[g] (its index 0 .. P - 1 in the [P, T]
+ * layout, or -1: absent); rows in no group count as absent.  out (the mean, [Nt, L]) may be NULL (then mu may be
+ * too); when given it receives lvae_predict_f64's bits (the same launches).  out_var [Nt, L].  The per-row algebra
+ * runs with the test rows as the columns of fp64 matrix-core tiles; q and H^-1 w take one residual refinement step
+ * each; every reduction is in a fixed order.  O((M^2 + T^2 + M T) Nt) flops per dim.  info as lvae_predict_f64.
+ * workspace: lvae_predict_var_workspace_size(L, M, P, T, Nt) bytes (lvae_predict_f64's + 8 L ((2 T + 6 M) Nt + M^2)).
+ * Return codes (before any launch): -1 -3 -6 -8 -13 -20 as lvae_predict_f64; -9: out given and mu NULL; -10: x or
+ * z NULL; -11: params0, params1 or noise NULL; -12: Nt > 0 and test_x NULL; -14: n_groups < 0; -15: n_groups > 0 and
+ * group_subject or group_start NULL; -16: Nt > 0 and out_var NULL; -17: add_noise not 0 / 1.  0 = ok.   */
+size_t lvae_predict_var_workspace_size(int L, int M, int P, int T, int Nt);
+int lvae_predict_var_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, int L, int M, int Q, int P,
+                         int T, const int32_t* seg_len, const int32_t* include, const double* x, const double* mu,
+                         const double* z, int Nt, const double* test_x, int n_groups, const int32_t* group_subject,
+                         const int32_t* group_start, const double* params0, const double* params1,
+                         const double* noise, double eps, double* out, double* out_var, int add_noise, int32_t* info,
+                         void* workspace, void* stream);
+
 /* ---------------------------------------------------------------------------------------- */
 /* Phase timing (profiling aid; the only process-wide state of the library).  When enabled, */
 /* the composite entry points bracket their phases with hipEvents on the caller's stream;  */

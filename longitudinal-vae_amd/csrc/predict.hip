@@ -13,8 +13,12 @@
 // padding blocks of B set to I, padding rows of mu zeroed by the caller).  The k1 term is the
 // reference's dense product over all prediction rows of the test subjects (include[p] = 1),
 // evaluated in chunks of test rows.
+//
+// Both predictors also give the predictive variance of the latent functions, which the reference does not:
+// lvae_predict_exact_var_f64 and lvae_predict_var_f64 below, their kernels and formulas in predict_var.hpp.
 #include "small.hpp"
 #include "prof.hpp"
+#include "predict_var.hpp"
 
 namespace lvae {
 namespace {
@@ -173,6 +177,36 @@ __global__ void pe_add_kernel(int64_t m, double* __restrict__ a, const double* _
   if (e < m) a[e] += r[e];
 }
 
+// workspace of lvae_predict_var_f64 behind lvae_predict_f64's own (PWs): G [L, M, M], the test rows' subjects, and
+// per latent dim the [T, Nt] matrices C, D and the [M, Nt] matrices E, K0zX*, Q, W, V and the residual R
+struct VWs {
+  double *Gm, *C, *D, *E, *KzX, *Qm, *W, *V, *R;
+  int32_t* rs;
+  size_t bytes;
+  VWs(char* base, size_t off0, int L, int M, int T, int Nt) {
+    WsCarve c(base ? base + off0 : nullptr);
+    const size_t tn = (size_t)L * T * Nt, mn = (size_t)L * M * Nt;
+    Gm = c.take((size_t)L * M * M);
+    rs = (int32_t*)c.take(((size_t)Nt + 1) / 2);
+    C = c.take(tn);
+    D = c.take(tn);
+    E = c.take(mn);
+    KzX = c.take(mn);
+    Qm = c.take(mn);
+    W = c.take(mn);
+    V = c.take(mn);
+    R = c.take(mn);
+    bytes = off0 + c.off;
+  }
+};
+
+// workspace of lvae_predict_exact_var_f64 behind lvae_predict_exact_f64's own (EWs): the panel k(X, X*_chunk)
+// [L, n, c], solved in place
+inline size_t exact_var_panel_bytes(int n, int nt, int L, int chunk) {
+  const int c = chunk < nt ? chunk : nt;
+  return align256((size_t)L * n * (c > 0 ? c : 0) * sizeof(double));
+}
+
 }  // namespace
 
 int gram_matvec_f64(const lvae_kernel_spec* spec, const double* x1, int64_t ld1, int n1, const double* x2, int64_t ld2,
@@ -183,24 +217,15 @@ int gram_matvec_spec_ld(const lvae_kernel_spec* spec);
 
 using namespace lvae;
 
-extern "C" {
-
-size_t lvae_predict_workspace_size(int L, int M, int P, int T, int Nt) {
-  return PWs(nullptr, L, M, P, T, Nt > 0 ? Nt : 1).bytes;
-}
-
-int lvae_predict_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, int L, int M, int Q, int P, int T,
-                     const int32_t* seg_len, const int32_t* include, const double* x, const double* mu,
-                     const double* z, int Nt, const double* test_x, const double* params0, const double* params1,
-                     const double* noise, double eps, double* out, int32_t* info, void* workspace, void* stream) {
-  if (!spec0 || !spec1 || !spec_bucket(spec0) || !spec_bucket(spec1)) return -1;  // (before any launch)
-  if (L < 1 || M < 1 || M > 128) return -3;
-  if (P < 1 || T < 1 || T > 128 || Q < 1) return -6;
-  if (!seg_len || !include) return -8;
-  if (Nt < 0) return -13;
-  if (!workspace || ((uintptr_t)workspace & 255)) return -20;
+// The launches of lvae_predict_f64 on the carved workspace w (arguments checked by the caller).  mean = false
+// stops after the factorisations (the variance alone needs no mu~); Gm, when given, receives
+// G = K0zx iB K0xz [L, M, M] before K0zz is added to it (H - K0zz would lose G's low bits).
+static int predict_core(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, int L, int M, int Q, int P, int T,
+                        const int32_t* seg_len, const int32_t* include, const double* x, const double* mu,
+                        const double* z, int Nt, const double* test_x, const double* params0, const double* params1,
+                        const double* noise, double eps, double* out, bool mean, double* Gm, int32_t* info, PWs& w,
+                        void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  PWs w((char*)workspace, L, M, P, T, Nt > 0 ? Nt : 1);
   const int NP = P * T;
   const int64_t MM = (int64_t)M * M, TT = (int64_t)T * T, NPM = (int64_t)NP * M;
   // Grams (utils.py:139-160): K0xz [L,NP,M], K0zz + eps I, K0X*z [L,Nt,M], B_p = k1(x_p, x_p) + noise I
@@ -212,14 +237,21 @@ int lvae_predict_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec
   pr_mask_kernel<<<nblk((int64_t)L * NPM + (int64_t)L * P * TT), 256, 0, st>>>(L, P, T, M, seg_len, w.K0xz, w.Bst);
   // iB (per subject), iB mu, iB K0xz
   LVAE_TRY(spd_inv_small_f64(T, L * P, w.Bst, TT, w.iB, TT, w.ldB, w.info + 2 * L, st));
-  LVAE_TRY(gemm_small_f64(0, 0, T, 1, T, 1.0, w.iB, T, (int64_t)P * TT, TT, mu, L, 1, (int64_t)T * L, 0.0, w.iBmu, 1,
-                          NP, T, L, P, st));
+  if (mean)
+    LVAE_TRY(gemm_small_f64(0, 0, T, 1, T, 1.0, w.iB, T, (int64_t)P * TT, TT, mu, L, 1, (int64_t)T * L, 0.0, w.iBmu,
+                            1, NP, T, L, P, st));
   LVAE_TRY(gemm_small_f64(0, 0, T, M, T, 1.0, w.iB, T, (int64_t)P * TT, TT, w.K0xz, M, NPM, (int64_t)T * M, 0.0, w.iBK,
                           M, NPM, (int64_t)T * M, L, P, st));
   // H = K0zz + eps I + K0xz^T iB K0xz  (utils.py:147,171);  K0zz += eps I
   LVAE_TRY(gemm_small_f64(1, 0, M, M, NP, 1.0, w.K0xz, M, NPM, 0, w.iBK, M, NPM, 0, 0.0, w.Hm, M, MM, 0, L, 1, st));
+  if (Gm) LVAE_TRY(copy_words_async(Gm, w.Hm, (size_t)L * MM * sizeof(double), st));
   pr_eye_add_kernel<<<nblk((int64_t)L * MM), 256, 0, st>>>(L, M, eps, w.K0zz, w.Hm);
   LVAE_TRY(spd_inv_small2_f64(M, L, w.K0zz, MM, w.iK, MM, w.ldK, w.info, L, w.Hm, MM, w.iH, MM, w.ldH, w.info + L, st));
+  if (!mean) {
+    if (info) pr_info_kernel<<<nblk(L), 256, 0, st>>>(L, P, w.info, info);
+    LVAE_CHECK_LAUNCH();
+    return 0;
+  }
   // mu~ = iB mu - iB K0xz H^-1 K0xz^T iB mu
   LVAE_TRY(gemm_small_f64(1, 0, M, 1, NP, 1.0, w.K0xz, M, NPM, 0, w.iBmu, 1, NP, 0, 0.0, w.w, 1, M, 0, L, 1, st));
   LVAE_TRY(gemm_small_f64(0, 0, M, 1, M, 1.0, w.iH, M, MM, 0, w.w, 1, M, 0, 0.0, w.v, 1, M, 0, L, 1, st));
@@ -255,6 +287,57 @@ int lvae_predict_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec
   return 0;
 }
 
+// The launches of lvae_predict_exact_f64 on the carved workspace w (arguments checked by the caller): the factor
+// of K into w.K and, when out is given, the mean.
+static int exact_core(const lvae_kernel_spec* spec, const double* x, int64_t ldx, int n, int L, const double* params,
+                      const double* noise, const double* mu, int64_t ld_mu, const double* tx, int64_t ldt, int nt,
+                      double* out, int64_t ld_out, int32_t* info, EWs& w, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t nn = (int64_t)n * n;
+  // K = k(x, x) + noise I, factored in place (info[l] > 0: dim l is not positive definite; its outputs are
+  // then meaningless, every other dim's are unaffected)
+  const lvae_xview xv{x, 0, 0, ldx};
+  LVAE_TRY(lvae_gram_f64(spec, xv, xv, 1, L, n, n, params, noise, w.K, 0, nn, n, stream));
+  LVAE_TRY(lvae_potrf_f64(n, L, w.K, n, nn, w.K, n, nn, w.logdet, info, stream));
+  if (nt == 0 || !out) {
+    LVAE_CHECK_LAUNCH();
+    return 0;
+  }
+  // a0 = K^-1 mu, then one refinement step a = a0 + K^-1 (mu - K a0) with K a0 from the covariates again (K itself
+  // is overwritten by its factor): the solve alone is cond(K) ulps from the reference's explicit-inverse product
+  pe_gather_kernel<<<nblk((int64_t)L * n), 256, 0, st>>>(L, n, mu, ld_mu, w.a);
+  LVAE_TRY(lvae_potrs_f64(n, 1, L, w.K, n, nn, w.a, 1, n, w.trsm, stream));
+  LVAE_TRY(gram_matvec_f64(spec, x, ldx, n, x, ldx, n, L, params, noise, w.a, n, 1, w.r, n, 1, w.mv, st));
+  pe_resid_kernel<<<nblk((int64_t)L * n), 256, 0, st>>>(L, n, mu, ld_mu, w.r);
+  LVAE_TRY(lvae_potrs_f64(n, 1, L, w.K, n, nn, w.r, 1, n, w.trsm, stream));
+  pe_add_kernel<<<nblk((int64_t)L * n), 256, 0, st>>>((int64_t)L * n, w.a, w.r);
+  // Zpred = k(X*, x) a
+  LVAE_TRY(gram_matvec_f64(spec, tx, ldt, nt, x, ldx, n, L, params, nullptr, w.a, n, 1, out, ld_out, 0, w.mv, st));
+  LVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" {
+
+size_t lvae_predict_workspace_size(int L, int M, int P, int T, int Nt) {
+  return PWs(nullptr, L, M, P, T, Nt > 0 ? Nt : 1).bytes;
+}
+
+int lvae_predict_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, int L, int M, int Q, int P, int T,
+                     const int32_t* seg_len, const int32_t* include, const double* x, const double* mu,
+                     const double* z, int Nt, const double* test_x, const double* params0, const double* params1,
+                     const double* noise, double eps, double* out, int32_t* info, void* workspace, void* stream) {
+  if (!spec0 || !spec1 || !spec_bucket(spec0) || !spec_bucket(spec1)) return -1;  // (before any launch)
+  if (L < 1 || M < 1 || M > 128) return -3;
+  if (P < 1 || T < 1 || T > 128 || Q < 1) return -6;
+  if (!seg_len || !include) return -8;
+  if (Nt < 0) return -13;
+  if (!workspace || ((uintptr_t)workspace & 255)) return -20;
+  PWs w((char*)workspace, L, M, P, T, Nt > 0 ? Nt : 1);
+  return predict_core(spec0, spec1, L, M, Q, P, T, seg_len, include, x, mu, z, Nt, test_x, params0, params1, noise,
+                      eps, out, true, nullptr, info, w, stream);
+}
+
 size_t lvae_predict_exact_workspace_size(int n, int nt, int L) {
   if (n < 1 || nt < 0 || L < 1) return 0;
   return EWs(nullptr, n, nt, L).bytes;
@@ -281,28 +364,142 @@ int lvae_predict_exact_f64(const lvae_kernel_spec* spec, const double* x, int64_
   if (nt > 0 && ld_out < L) return -14;
   if (!info) return -15;
   if (!workspace || ((uintptr_t)workspace & 255)) return -16;
+  EWs w((char*)workspace, n, nt, L);
+  return exact_core(spec, x, ldx, n, L, params, noise, mu, ld_mu, tx, ldt, nt, out, ld_out, info, w, stream);
+}
+
+size_t lvae_predict_exact_var_workspace_size(int n, int nt, int L, int chunk) {
+  if (n < 1 || nt < 0 || L < 1 || (nt > 0 && chunk < 1)) return 0;
+  return EWs(nullptr, n, nt, L).bytes + exact_var_panel_bytes(n, nt, L, chunk);
+}
+
+int lvae_predict_exact_var_f64(const lvae_kernel_spec* spec, const double* x, int64_t ldx, int n, int L,
+                               const double* params, const double* noise, const double* mu, int64_t ld_mu,
+                               const double* tx, int64_t ldt, int nt, double* out_mean, int64_t ld_out,
+                               double* out_var, int64_t ld_var, int add_noise, int chunk, int32_t* info,
+                               void* workspace, void* stream) {
+  const int ld_min = spec ? gram_matvec_spec_ld(spec) : 0;
+  if (ld_min < 1 || ld_min > 32) return -1;  // (before any launch)
+  if (!x) return -2;
+  if (ldx < ld_min) return -3;
+  if (n < 1) return -4;
+  if (L < 1) return -5;
+  if (!params) return -6;
+  if (!noise) return -7;
+  if (out_mean && !mu) return -8;
+  if (out_mean && ld_mu < L) return -9;
+  if (nt < 0) return -12;
+  if (nt > 0 && !tx) return -10;
+  if (nt > 0 && ldt < ld_min) return -11;
+  if (out_mean && ld_out < L) return -14;
+  if (!info) return -15;
+  if (!workspace || ((uintptr_t)workspace & 255)) return -16;
+  if (nt > 0 && !out_var) return -17;
+  if (nt > 0 && ld_var < L) return -18;
+  if (add_noise != 0 && add_noise != 1) return -19;
+  if (nt > 0 && chunk < 1) return -20;
   hipStream_t st = (hipStream_t)stream;
   EWs w((char*)workspace, n, nt, L);
-  const int64_t nn = (int64_t)n * n;
-  // K = k(x, x) + noise I, factored in place (info[l] > 0: dim l is not positive definite; its outputs are
-  // then meaningless, every other dim's are unaffected)
+  double* panel = (double*)((char*)workspace + w.bytes);
+  // the factor of K (and the mean, by lvae_predict_exact_f64's own launches)
+  LVAE_TRY(exact_core(spec, x, ldx, n, L, params, noise, mu, ld_mu, tx, ldt, nt, out_mean, ld_out, info, w, stream));
+  if (nt == 0) return 0;
+  // var = k(x*, x*) - |L^-1 k(X, x*)|^2, c test rows at a time: the panel k(X, X*_chunk) [L, n, c], one
+  // triangular solve in place, then the columns' sums of squares.  A column's solve and sum do not depend on its
+  // neighbours, so the bits do not depend on the chunk.
+  const int c = chunk < nt ? chunk : nt;
+  const int bucket = spec_bucket(spec);
+  const DevSpec ds = to_dev(spec);
   const lvae_xview xv{x, 0, 0, ldx};
-  LVAE_TRY(lvae_gram_f64(spec, xv, xv, 1, L, n, n, params, noise, w.K, 0, nn, n, stream));
-  LVAE_TRY(lvae_potrf_f64(n, L, w.K, n, nn, w.K, n, nn, w.logdet, info, stream));
-  if (nt == 0) {
-    LVAE_CHECK_LAUNCH();
-    return 0;
+  for (int c0 = 0; c0 < nt; c0 += c) {
+    const int nr = nt - c0 < c ? nt - c0 : c;
+    const double* tc = tx + (int64_t)c0 * ldt;
+    const lvae_xview tv{tc, 0, 0, ldt};
+    LVAE_TRY(lvae_gram_f64(spec, xv, tv, 1, L, n, nr, params, nullptr, panel, 0, (int64_t)n * c, c, stream));
+    LVAE_TRY(lvae_trsm_f64(0, n, nr, L, w.K, n, (int64_t)n * n, panel, c, (int64_t)n * c, w.trsm, stream));
+    const dim3 grid(cdiv(nr, 64), L);
+    double* vo = out_var + (int64_t)c0 * ld_var;
+    if (bucket == 1)
+      pe_var_kernel<8, 2><<<grid, 256, 0, st>>>(ds, n, nr, panel, c, tc, ldt, params, noise, add_noise, vo, ld_var);
+    else
+      pe_var_kernel<16, 4><<<grid, 256, 0, st>>>(ds, n, nr, panel, c, tc, ldt, params, noise, add_noise, vo, ld_var);
   }
-  // a0 = K^-1 mu, then one refinement step a = a0 + K^-1 (mu - K a0) with K a0 from the covariates again (K itself
-  // is overwritten by its factor): the solve alone is cond(K) ulps from the reference's explicit-inverse product
-  pe_gather_kernel<<<nblk((int64_t)L * n), 256, 0, st>>>(L, n, mu, ld_mu, w.a);
-  LVAE_TRY(lvae_potrs_f64(n, 1, L, w.K, n, nn, w.a, 1, n, w.trsm, stream));
-  LVAE_TRY(gram_matvec_f64(spec, x, ldx, n, x, ldx, n, L, params, noise, w.a, n, 1, w.r, n, 1, w.mv, st));
-  pe_resid_kernel<<<nblk((int64_t)L * n), 256, 0, st>>>(L, n, mu, ld_mu, w.r);
-  LVAE_TRY(lvae_potrs_f64(n, 1, L, w.K, n, nn, w.r, 1, n, w.trsm, stream));
-  pe_add_kernel<<<nblk((int64_t)L * n), 256, 0, st>>>((int64_t)L * n, w.a, w.r);
-  // Zpred = k(X*, x) a
-  LVAE_TRY(gram_matvec_f64(spec, tx, ldt, nt, x, ldx, n, L, params, nullptr, w.a, n, 1, out, ld_out, 0, w.mv, st));
+  LVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+size_t lvae_predict_var_workspace_size(int L, int M, int P, int T, int Nt) {
+  const int nt1 = Nt > 0 ? Nt : 1;
+  return VWs(nullptr, PWs(nullptr, L, M, P, T, nt1).bytes, L, M, T, nt1).bytes;
+}
+
+int lvae_predict_var_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, int L, int M, int Q, int P,
+                         int T, const int32_t* seg_len, const int32_t* include, const double* x, const double* mu,
+                         const double* z, int Nt, const double* test_x, int n_groups, const int32_t* group_subject,
+                         const int32_t* group_start, const double* params0, const double* params1,
+                         const double* noise, double eps, double* out, double* out_var, int add_noise, int32_t* info,
+                         void* workspace, void* stream) {
+  if (!spec0 || !spec1 || !spec_bucket(spec0) || !spec_bucket(spec1)) return -1;  // (before any launch)
+  if (L < 1 || M < 1 || M > 128) return -3;
+  if (P < 1 || T < 1 || T > 128 || Q < 1) return -6;
+  if (!seg_len || !include) return -8;
+  if (out && !mu) return -9;
+  if (!x || !z) return -10;
+  if (!params0 || !params1 || !noise) return -11;
+  if (Nt < 0) return -13;
+  if (Nt > 0 && !test_x) return -12;
+  if (n_groups < 0) return -14;
+  if (n_groups > 0 && (!group_subject || !group_start)) return -15;
+  if (Nt > 0 && !out_var) return -16;
+  if (add_noise != 0 && add_noise != 1) return -17;
+  if (!workspace || ((uintptr_t)workspace & 255)) return -20;
+  hipStream_t st = (hipStream_t)stream;
+  const int nt1 = Nt > 0 ? Nt : 1;
+  PWs w((char*)workspace, L, M, P, T, nt1);
+  VWs v((char*)workspace, w.bytes, L, M, T, nt1);
+  // the Grams, iB, K0zz^-1, H^-1 (and the mean) by lvae_predict_f64's own launches; G kept aside
+  LVAE_TRY(predict_core(spec0, spec1, L, M, Q, P, T, seg_len, include, x, mu, z, Nt, test_x, params0, params1, noise,
+                        eps, out, out != nullptr, v.Gm, info, w, stream));
+  if (Nt == 0) return 0;
+  const int64_t MM = (int64_t)M * M, MN = (int64_t)M * Nt;
+  const size_t mn_bytes = (size_t)L * MN * sizeof(double);
+  const int b1 = spec_bucket(spec1);
+  const DevSpec d1 = to_dev(spec1);
+  // c_i, d_i = iB_s c_i, e_i = K0zx_s d_i per subject group (rows of no group, or of an absent subject: 0)
+  pv_rowsubj_kernel<<<nblk(Nt), 256, 0, st>>>(Nt, P, n_groups, group_subject, group_start, v.rs);
+  if (b1 == 1)
+    pv_c_kernel<8, 2><<<nblk((int64_t)L * T * Nt), 256, 0, st>>>(d1, L, T, Nt, Q, seg_len, v.rs, x, test_x, params1, v.C);
+  else
+    pv_c_kernel<16, 4><<<nblk((int64_t)L * T * Nt), 256, 0, st>>>(d1, L, T, Nt, Q, seg_len, v.rs, x, test_x, params1, v.C);
+  LVAE_TRY(zero_async(v.D, (size_t)L * T * Nt * sizeof(double), st));
+  LVAE_TRY(zero_async(v.E, mn_bytes, st));
+  if (n_groups > 0)
+    pv_group_kernel<<<dim3(Nt / kPvC + n_groups, L), 256, 0, st>>>(M, P, T, Nt, n_groups, group_subject, group_start,
+                                                                  v.C, w.iB, w.K0xz, v.D, v.E);
+  // Q = K0zz^-1 K0zX* with one refinement step Q += K0zz^-1 (K0zX* - K0zz Q), as the mean refines its two products
+  // with explicit inverses: the bare product is cond(K0zz) ulps off, and q enters the variance three times in
+  // terms that cancel.  With this step and the one for V below, an fp64 emulation of the route against the dense
+  // oracle gives 5e-15 of the largest prior variance at M = 128, eps = 1e-3 (cond K0zz 5e5) where the bare
+  // products give 1.5e-10; the tests' bound is 2e-12.  K0zX* [L, M, Nt] is its own Gram (test rows as columns).
+  const lvae_xview zv{z, 0, (int64_t)M * Q, Q}, tv{test_x, 0, 0, Q};
+  LVAE_TRY(lvae_gram_f64(spec0, zv, tv, 1, L, M, Nt, params0, nullptr, v.KzX, 0, MN, Nt, stream));
+  LVAE_TRY(gemm_small_f64(0, 0, M, Nt, M, 1.0, w.iK, M, MM, 0, v.KzX, Nt, MN, 0, 0.0, v.Qm, Nt, MN, 0, L, 1, st));
+  LVAE_TRY(copy_words_async(v.R, v.KzX, mn_bytes, st));
+  LVAE_TRY(gemm_small_f64(0, 0, M, Nt, M, -1.0, w.K0zz, M, MM, 0, v.Qm, Nt, MN, 0, 1.0, v.R, Nt, MN, 0, L, 1, st));
+  LVAE_TRY(gemm_small_f64(0, 0, M, Nt, M, 1.0, w.iK, M, MM, 0, v.R, Nt, MN, 0, 1.0, v.Qm, Nt, MN, 0, L, 1, st));
+  // W = G Q + E;  V = H^-1 W with the same refinement step, V += H^-1 (W - H V) (cond(H) ulps otherwise)
+  LVAE_TRY(copy_words_async(v.W, v.E, mn_bytes, st));
+  LVAE_TRY(gemm_small_f64(0, 0, M, Nt, M, 1.0, v.Gm, M, MM, 0, v.Qm, Nt, MN, 0, 1.0, v.W, Nt, MN, 0, L, 1, st));
+  LVAE_TRY(gemm_small_f64(0, 0, M, Nt, M, 1.0, w.iH, M, MM, 0, v.W, Nt, MN, 0, 0.0, v.V, Nt, MN, 0, L, 1, st));
+  LVAE_TRY(copy_words_async(v.R, v.W, mn_bytes, st));
+  LVAE_TRY(gemm_small_f64(0, 0, M, Nt, M, -1.0, w.Hm, M, MM, 0, v.V, Nt, MN, 0, 1.0, v.R, Nt, MN, 0, L, 1, st));
+  LVAE_TRY(gemm_small_f64(0, 0, M, Nt, M, 1.0, w.iH, M, MM, 0, v.R, Nt, MN, 0, 1.0, v.V, Nt, MN, 0, L, 1, st));
+  if (b1 == 1)
+    pv_var_kernel<8, 2><<<nblk((int64_t)L * Nt), 256, 0, st>>>(d1, L, M, T, Nt, Q, v.KzX, v.Qm, v.W, v.E, v.V, v.C, v.D,
+                                                               test_x, params1, noise, add_noise, out_var);
+  else
+    pv_var_kernel<16, 4><<<nblk((int64_t)L * Nt), 256, 0, st>>>(d1, L, M, T, Nt, Q, v.KzX, v.Qm, v.W, v.E, v.V, v.C, v.D,
+                                                                test_x, params1, noise, add_noise, out_var);
   LVAE_CHECK_LAUNCH();
   return 0;
 }

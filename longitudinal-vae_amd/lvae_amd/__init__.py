@@ -21,7 +21,7 @@ from .likelihoods import GaussianLikelihood  # noqa: F401
 from .elbo import (HensmanPrior, KL_closed, KL_closed_batched, check_pending, kl_closed_prefactor,  # noqa: F401
                    minibatch_KLD_upper_bound, minibatch_KLD_upper_bound_iter, natural_gradient_update,
                    set_sync_checks)
-from .predict import batch_predict_varying_T, predict_exact  # noqa: F401
+from .predict import batch_predict_varying_T, predict_exact, sample_predictions  # noqa: F401
 from .evaluation import MSE_test, MSE_test_GPapprox  # noqa: F401
 from .gpapprox import (deviance_upper_bound, deviance_upper_bound_batched, elbo, elbo_batched,  # noqa: F401
                        spd_inverse, validation_dubo)

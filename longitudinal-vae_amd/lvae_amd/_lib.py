@@ -184,6 +184,12 @@ SIGNATURES = {
     "lvae_predict_exact_workspace_size": (_SZ, [_I32, _I32, _I32]),
     "lvae_predict_exact_f64": (_I32, [_SPEC, _VP, _I64, _I32, _I32, _VP, _VP, _VP, _I64, _VP, _I64, _I32, _VP, _I64,
                                       _VP, _VP, _VP]),
+    "lvae_predict_exact_var_workspace_size": (_SZ, [_I32, _I32, _I32, _I32]),
+    "lvae_predict_exact_var_f64": (_I32, [_SPEC, _VP, _I64, _I32, _I32, _VP, _VP, _VP, _I64, _VP, _I64, _I32, _VP,
+                                          _I64, _VP, _I64, _I32, _I32, _VP, _VP, _VP]),
+    "lvae_predict_var_workspace_size": (_SZ, [_I32, _I32, _I32, _I32, _I32]),
+    "lvae_predict_var_f64": (_I32, [_SPEC, _SPEC, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _I32, _VP,
+                                    _I32, _VP, _VP, _VP, _VP, _VP, _D, _VP, _VP, _I32, _VP, _VP, _VP]),
     "lvae_prof_enable": (_I32, [_I32]),
     "lvae_prof_collect": (_I32, [_VP, _VP, _I32]),
     "lvae_version": (ctypes.c_char_p, []),
