@@ -515,7 +515,9 @@ int lvae_hensman_bwd_z_f64(const lvae_kernel_spec* spec0, const lvae_hensman_dim
 
 /* ConvVAE encoder (VAE.py:44-50): y = max_pool2d(relu(x), 2, 2) over planes = N*C planes of H x W
  * (H, W even) fp32, idx = argmax byte (0..3, row-major in the window, first strict maximum);
- * backward gx = the pooled gradient routed to the argmax where y > 0, 0 elsewhere.            */
+ * backward gx = the pooled gradient routed to the argmax unless y <= 0, 0 elsewhere.
+ * NaN is kept as torch keeps it, here and in every encoder entry point below: a window that holds
+ * a NaN gives y = NaN with idx = its last NaN in scan order, and a NaN y passes its gradient.  */
 int lvae_relu_maxpool2_fwd_f32(const float* x, int64_t planes, int H, int W, float* y, uint8_t* idx,
                                void* stream);
 int lvae_relu_maxpool2_bwd_f32(const float* gy, const float* y, const uint8_t* idx, int64_t planes, int H,
@@ -552,7 +554,7 @@ int lvae_conv3x3_pool_wgrad_f32(const float* gy, const float* y, const uint8_t* 
                                 int Cin, int H, int W, float* dw, float* db, void* workspace, void* stream);
 /* The input gradient of the same layer (the second encoder conv, VAE.py:48-50; torch's conv2d backward-data
  * in the reference's autograd): gx [N, Cin, H, W] = the conv's backward-data of the routed gradient (gy at
- * each window's argmax where y > 0), formed per image in LDS, never in HBM.  w [C, Cin, 3, 3].  Cin == 16
+ * each window's argmax unless y <= 0), formed per image in LDS, never in HBM.  w [C, Cin, 3, 3].  Cin == 16
  * (-3 otherwise), H W <= 1024 and lvae_conv3x3_pool_dgrad_lds(C, H, W) <= 64 KB (-4 otherwise).      */
 size_t lvae_conv3x3_pool_dgrad_lds(int C, int H, int W);
 int lvae_conv3x3_pool_dgrad_f32(const float* gy, const float* y, const uint8_t* idx, const float* w, int N, int C,

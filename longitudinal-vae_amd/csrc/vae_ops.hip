@@ -2,8 +2,15 @@
 // 2x2 / stride-2 max pool.  relu and a max commute, so the pair is one pass over the conv output:
 // y = max(0, max of the window), with the argmax position kept as one byte (0..3, scan order,
 // first strict maximum -- the element torch's max_pool2d routes the gradient to).  Backward writes
-// every input element once: g_y to the argmax element when y > 0 (relu'(y) = 0 otherwise), 0 to
+// every input element once: g_y to the argmax element unless y <= 0 (relu'(y) = 0 there), 0 to
 // the rest.  Replaces torch's relu + max_pool2d (+ int64 indices) + their two backward kernels.
+//
+// NaN is kept, as torch keeps it, so a diverging encoder shows in the loss: the window scan takes an
+// element when it is larger or NaN (v > m || v != v: a NaN wins and is never displaced by a number, so
+// the argmax is the window's last NaN in scan order, torch's max_pool2d index), the relu is
+// m <= 0 ? 0 : m (NaN stays; every other value, -0 included, as max(0, m) before), and every backward
+// mask is y <= 0 ? 0 : g (torch's threshold_backward and act_bwd in glue.hip: a NaN y passes its
+// gradient).  Finite inputs give the same bits as the plain v > m / m > 0 forms.
 //
 // The _bias forms also take the conv's per-channel bias (the conv itself then runs without one):
 // the window is max of fl(x + b) (first strict maximum, so ties and rounding match torch's
@@ -34,10 +41,10 @@ __global__ __launch_bounds__(256) void relu_maxpool2_fwd_kernel(const float* __r
   const vo_f32x2 b = *reinterpret_cast<const vo_f32x2*>(p + W);
   float m = a[0];
   uint8_t k = 0;
-  if (a[1] > m) m = a[1], k = 1;
-  if (b[0] > m) m = b[0], k = 2;
-  if (b[1] > m) m = b[1], k = 3;
-  y[e] = m > 0.f ? m : 0.f;
+  if (a[1] > m || a[1] != a[1]) m = a[1], k = 1;
+  if (b[0] > m || b[0] != b[0]) m = b[0], k = 2;
+  if (b[1] > m || b[1] != b[1]) m = b[1], k = 3;
+  y[e] = m <= 0.f ? 0.f : m;
   idx[e] = k;
 }
 
@@ -51,7 +58,7 @@ __global__ __launch_bounds__(256) void relu_maxpool2_bwd_kernel(const float* __r
   const int64_t plane = e / ((int64_t)Ho * Wo);
   const int r = (int)(e % ((int64_t)Ho * Wo)), i = r / Wo, j = r % Wo;
   const int W = 2 * Wo;
-  const float g = y[e] > 0.f ? gy[e] : 0.f;
+  const float g = y[e] <= 0.f ? 0.f : gy[e];
   const int k = idx[e];
   float* p = gx + plane * 4 * Ho * Wo + (int64_t)(2 * i) * W + 2 * j;
   vo_f32x2 a, b;
@@ -78,12 +85,13 @@ __global__ __launch_bounds__(256) void relu_maxpool2_bias_fwd_kernel(const float
   const float* p = x + plane * 4 * Ho * Wo + (int64_t)(2 * i) * W + 2 * j;
   const vo_f32x2 a = *reinterpret_cast<const vo_f32x2*>(p);
   const vo_f32x2 b = *reinterpret_cast<const vo_f32x2*>(p + W);
+  const float v1 = a[1] + bc, v2 = b[0] + bc, v3 = b[1] + bc;
   float m = a[0] + bc;
   uint8_t k = 0;
-  if (a[1] + bc > m) m = a[1] + bc, k = 1;
-  if (b[0] + bc > m) m = b[0] + bc, k = 2;
-  if (b[1] + bc > m) m = b[1] + bc, k = 3;
-  y[e] = m > 0.f ? m : 0.f;
+  if (v1 > m || v1 != v1) m = v1, k = 1;
+  if (v2 > m || v2 != v2) m = v2, k = 2;
+  if (v3 > m || v3 != v3) m = v3, k = 3;
+  y[e] = m <= 0.f ? 0.f : m;
   idx[e] = k;
 }
 
@@ -102,7 +110,7 @@ __global__ __launch_bounds__(256) void relu_maxpool2_bias_bwd_kernel(const float
   for (int t = threadIdx.x; t < total; t += 256) {
     const int n = n0 + t / P, r = t % P, i = r / Wo, j = r % Wo;
     const int64_t plane = (int64_t)n * C + c, e = plane * P + r;
-    const float g = y[e] > 0.f ? gy[e] : 0.f;
+    const float g = y[e] <= 0.f ? 0.f : gy[e];
     s += g;
     const int k = idx[e];
     float* q = gx + plane * 4 * P + (int64_t)(2 * i) * W + 2 * j;
@@ -315,11 +323,11 @@ __global__ __launch_bounds__(256) void conv1_relu_maxpool2_fwd_kernel(const floa
     }
     float m = v[0];
     uint8_t k = 0;
-    if (v[1] > m) m = v[1], k = 1;
-    if (v[2] > m) m = v[2], k = 2;
-    if (v[3] > m) m = v[3], k = 3;
+    if (v[1] > m || v[1] != v[1]) m = v[1], k = 1;
+    if (v[2] > m || v[2] != v[2]) m = v[2], k = 2;
+    if (v[3] > m || v[3] != v[3]) m = v[3], k = 3;
     const int64_t o = ((int64_t)n * C + c) * P + r;
-    y[o] = m > 0.f ? m : 0.f;
+    y[o] = m <= 0.f ? 0.f : m;
     idx[o] = k;
   }
 }
@@ -374,7 +382,7 @@ __global__ __launch_bounds__(256) void conv3x3_pool_wgrad_kernel(const float* __
     for (int e = t; e < C * P; e += 256) {  // unconditional loads: no load waits on another
       const float yv = y[b0 + e], gv = gy[b0 + e];
       const int k = idx[b0 + e], r = e % P, i = r / Wo, j = r % Wo;
-      gl[e] = yv > 0.f ? gv : 0.f;
+      gl[e] = yv <= 0.f ? 0.f : gv;
       ol[e] = (2 * i + (k >> 1)) * Wp + 2 * j + (k & 1);  // padded coords of tap (0, 0)
     }
     __syncthreads();
@@ -483,7 +491,7 @@ __global__ __launch_bounds__(1024) void conv3x3_pool_dgrad_kernel(const float* _
       const int64_t s = b0 + (int64_t)c0 * P + e;
       const float yv = y[s], gv = gy[s];
       const int k = idx[s];
-      const float g = yv > 0.f ? gv : 0.f;
+      const float g = yv <= 0.f ? 0.f : gv;
       float* q = sm + c * HWp + (2 * i + 1) * Wp + 2 * j + 1;
       q[0] = k == 0 ? g : 0.f;
       q[1] = k == 1 ? g : 0.f;
@@ -543,7 +551,7 @@ __global__ __launch_bounds__(512) void conv3x3_pool_dgrad2_kernel(const float* _
     const int c = e / P, r = e % P, i = r / Wo, j = r % Wo;
     const float yv = y[b0 + e], gv = gy[b0 + e];
     const int k = idx[b0 + e];
-    const float g = yv > 0.f ? gv : 0.f;
+    const float g = yv <= 0.f ? 0.f : gv;
     float* q = sm + c * HWp + (2 * i + 1) * Wp + 2 * j + 1;
     q[0] = k == 0 ? g : 0.f;
     q[1] = k == 1 ? g : 0.f;
@@ -647,13 +655,14 @@ __global__ __launch_bounds__(256) void conv3x3_relu_pool_fwd_kernel(const float*
       for (int co = 0; co < 16; ++co) {
         const int c = grp * 16 + co;
         const float bc = bias[c];
+        const float v1 = acc[co][0][1] + bc, v2 = acc[co][1][0] + bc, v3 = acc[co][1][1] + bc;
         float m = acc[co][0][0] + bc;
         uint8_t k = 0;
-        if (acc[co][0][1] + bc > m) m = acc[co][0][1] + bc, k = 1;
-        if (acc[co][1][0] + bc > m) m = acc[co][1][0] + bc, k = 2;
-        if (acc[co][1][1] + bc > m) m = acc[co][1][1] + bc, k = 3;
+        if (v1 > m || v1 != v1) m = v1, k = 1;
+        if (v2 > m || v2 != v2) m = v2, k = 2;
+        if (v3 > m || v3 != v3) m = v3, k = 3;
         const int64_t o = ((int64_t)(n0 + img) * C + c) * P + r;
-        y[o] = m > 0.f ? m : 0.f;
+        y[o] = m <= 0.f ? 0.f : m;
         idx[o] = k;
       }
     }
@@ -1038,7 +1047,7 @@ __global__ __launch_bounds__(256) void conv3x3_pool_wgrad_mfma_kernel(const floa
       const int e = t + 256 * k;
       if (e < C * P) {
         const float yv = y[ob + e], gv = gy[ob + e];
-        pg[k] = yv > 0.f ? gv : 0.f;
+        pg[k] = yv <= 0.f ? 0.f : gv;
         pk[k] = idx[ob + e];
       }
     }
@@ -1150,7 +1159,7 @@ __global__ __launch_bounds__(256) void conv3x3_pool_dgrad_mfma_kernel(const floa
       const int e = t + 256 * k;
       if (e < C * P) {
         const float yv = y[ob + e], gv = gy[ob + e];
-        pg[k] = yv > 0.f ? gv : 0.f;
+        pg[k] = yv <= 0.f ? 0.f : gv;
         pk[k] = idx[ob + e];
       }
     }

@@ -35,7 +35,8 @@ def _side_stream(dev):
 class _ReluMaxPool2(torch.autograd.Function):
     """max_pool2d(relu(x), 2, 2) in one HIP pass (lvae_relu_maxpool2_fwd/bwd_f32, vae_ops.hip):
     one byte of argmax per output instead of torch's int64 indices, one write per input in the
-    backward.  Same values and gradient routing as relu + max_pool2d (first strict maximum)."""
+    backward.  Same values and gradient routing as relu + max_pool2d (first strict maximum; a NaN
+    in the window is kept and takes the gradient, as in torch)."""
 
     @staticmethod
     def forward(ctx, x):

@@ -294,7 +294,9 @@ def test_kl_closed_vs_oracle_full_size(hip):
 
 
 def test_relu_maxpool2_matches_torch(hip):
-    """Fused encoder relu + 2x2 max pool vs torch (values bit-exact, gradient routing identical)."""
+    """Fused encoder relu + 2x2 max pool vs torch on finite inputs (values bit-exact, gradient routing identical).
+    NaN rule (pinned in test_gpu_vae_ops_abi.py): a NaN in the window gives a NaN output, the argmax is the
+    window's last NaN in scan order and its gradient passes, as in torch's max_pool2d(relu(x))."""
     from lvae_amd.vae import relu_maxpool2
     import torch.nn.functional as F
     gen = torch.Generator(device=DEV).manual_seed(0)
