@@ -670,7 +670,20 @@ int lvae_predict_var_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* 
                          void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------- */
-/* Phase timing (profiling aid; the only process-wide state of the library).  When enabled, */
+/* The early stream (per device; optional).  The blocked Cholesky inverse (lvae_spd_inv_chol_f32,   */
+/* lvae_kl_closed_factor_f32) can start the part of its triangular inverse that needs only the      */
+/* first block columns while the factorisation's last passes, bound by their chain of pivot blocks, */
+/* leave the GPU nearly idle -- on a second stream, which the CALLER lends: a process may have as   */
+/* few as 4 hardware queues, and a stream more than that serialises with another one, so the        */
+/* library creates none of its own for this.  Lend a stream that is idle while the factor runs and   */
+/* outlives every later call on the current device (its work is ordered by events: forked from the  */
+/* call's stream and joined before the call returns; a call under stream capture does not use it);  */
+/* NULL withdraws it.  Results are bitwise the same with and without.  0 or LVAE_ERR_LAUNCH.        */
+/* ---------------------------------------------------------------------------------------- */
+int lvae_set_early_stream(void* stream);
+
+/* ---------------------------------------------------------------------------------------- */
+/* Phase timing (profiling aid; with the early stream the only process-wide state of the library).  When enabled, */
 /* the composite entry points bracket their phases with hipEvents on the caller's stream;  */
 /* lvae_prof_collect synchronises on them, ADDS each phase's elapsed ms into ms[phase],    */
 /* the number of bracketed intervals into count[phase], and forgets them.                  */

@@ -33,10 +33,12 @@
 // crosses blocks changes the operand scales: the accumulators are rescaled by the (power-of-two) ratio
 // at each block boundary (exact).
 //
-// Buffers (ci_inverse): A [L, np, np] fp32 (lower tiles read; dead after potrf, then reused as the Y
-// planes), YT [L, np, np] x 2 halves (Y^T planes; caller-provided), Kinv [L, np, np] fp32 out (reused as
-// the X^T planes during trtri), scratch (CiScratch): C planes 2 x [L, np, 256] by pass parity, the
-// pivot's X block, D [L, nt, 256, 256], the L planes [L, np, np] and the per-tile scales.
+// Buffers (ci_inverse): A [L, np, np] fp32 (lower tiles read and overwritten by potrf; unused after it),
+// YT [L, np, np] x 2 halves (Y^T planes; caller-provided), Kinv [L, np, np] fp32 out (during trtri one
+// hi + lo plane pair that holds BOTH the X^T planes -- tiles (j, i), j < i: strictly upper -- and the
+// row-major Y planes -- tiles (i, j), i >= j: lower and diagonal; the same tile offsets, so the two sets
+// are disjoint; lauum reads neither and overwrites it), scratch (CiScratch): C planes 2 x [L, np, 256] by
+// pass parity, the pivot's X block, D [L, nt, 256, 256], the L planes [L, np, np] and the per-tile scales.
 #include "prof.hpp"
 #include "pv_lds.hpp"
 #include "side_stream.hpp"
@@ -1165,14 +1167,15 @@ __global__ __launch_bounds__(256, 2) void ci_update128_kernel(float* __restrict_
                                               ((32 * a + (e & 3) + 8 * (e >> 2)) * np_ + 32 * b) * 4, CAUX);
 }
 
-// D (the pivots' Y_kk planes) -> the diagonal tiles of the row-major Y planes (after potrf: the Y
-// planes alias A) and, transposed through LDS, of the Y^T planes.  grid (16 nt, L): one 256-thread
-// workgroup per 64 x 64 piece (a, b) of a diagonal tile, Y (a, b) = D (a, b) and Y^T (b, a) = D (a, b)^T.
+// D (the pivots' Y_kk planes) -> the diagonal tiles of the row-major Y planes (the lower tiles of the
+// Kinv plane pair) and, transposed through LDS, of the Y^T planes, for the blocks k0 .. k0 + count - 1.
+// grid (16 count, L): one 256-thread workgroup per 64 x 64 piece (a, b) of a diagonal tile,
+// Y (a, b) = D (a, b) and Y^T (b, a) = D (a, b)^T.
 __global__ __launch_bounds__(256) void ci_diag_copy_kernel(CiScratch S, int np_, _Float16* __restrict__ Yh,
                                                            _Float16* __restrict__ Yl, _Float16* __restrict__ YTh,
-                                                           _Float16* __restrict__ YTl) {
+                                                           _Float16* __restrict__ YTl, int k0) {
   __shared__ _Float16 tp[2][64][66];
-  const int k = blockIdx.x >> 4, pa = (blockIdx.x >> 2) & 3, pb = blockIdx.x & 3, l = blockIdx.y, t = threadIdx.x;
+  const int k = k0 + (blockIdx.x >> 4), pa = (blockIdx.x >> 2) & 3, pb = blockIdx.x & 3, l = blockIdx.y, t = threadIdx.x;
   const int64_t od = ((int64_t)l * S.nt + k) * kSwBB + (int64_t)(64 * pa) * kSwB + 64 * pb;
   const int64_t ot = (int64_t)l * np_ * np_ + (int64_t)k * kSwB * np_ + k * kSwB;
   const int64_t oy = ot + (int64_t)(64 * pa) * np_ + 64 * pb, oyt = ot + (int64_t)(64 * pb) * np_ + 64 * pa;
@@ -1260,6 +1263,7 @@ struct CiGemmArgs {
   const int* hbon = nullptr;  // kCiLauumKL: *hbon != 0 -> the binned hyper-gradient (kl_hyper.hip) runs: the full
                               // symmetric K^-1 (the mirror) instead of the S GEMM's B planes
   const int* dimflag = nullptr;  // kCiLauum: only the dims l with dimflag[l] != 0 (the others' workgroups exit)
+  int bid0 = 0;  // ci_gemm_kernel: this launch's first workgroup of the list (nwg counts the whole list)
 };
 
 // one halving butterfly step over lane bit D (D <= 16): the lane keeps the half of its N partial sums
@@ -1734,7 +1738,8 @@ __device__ inline void ci_gemm_body(const CiGemmArgs& g, const CiScratch& S, con
 template <int MODE>
 __global__ __launch_bounds__(512) void ci_gemm_kernel(CiGemmArgs g, CiScratch S) {
   CI_GEMM_LDS
-  ci_gemm_body<MODE>(g, S, blockIdx.x, lds, sprod, &red, kl_mu, kl_sv, kl_part);
+  // (bid0: a launch list cut into several launches, trtri's early part in ci_factor_f32)
+  ci_gemm_body<MODE>(g, S, blockIdx.x + g.bid0, lds, sprod, &red, kl_mu, kl_sv, kl_part);
 }
 
 // two modes in ONE launch (the pipelined schedule's passes: fewer, fuller launches on the caller's stream):
@@ -1767,10 +1772,36 @@ __global__ __launch_bounds__(512) void ci_pair_kernel(CiGemmArgs g1, CiGemmArgs 
 // their previous readers (panel(k-1), pivot(k)) precede U1(k) on the caller's stream.  The L planes of
 // column k are written once (panel(k)) and read by U1(k), U2(k), and trtri; D by the pivots, the panels
 // and the diagonal copies.
-// Then, on the caller's stream: the diagonal copy, trtri (2 launches per level); lauum is ci_lauum_f32.  (Launching each
-// recursive-doubling instance as soon as potrf had produced its blocks -- 2 small launches per
-// instance on the caller's stream between the passes -- measured 15.1 vs 14.2 ms per closed step at
-// L = 16: the small launches slowed the passes more than the overlap saved.)
+// Then trtri: the diagonal copy and 2 launches per level; lauum is ci_lauum_f32.  In schedule (b), with
+// LVAE_CI_TRTRI_EARLY=0, under a stream capture and when the caller has lent no early stream
+// (lvae_set_early_stream) all of it follows potrf on the caller's stream.  Else, in schedule (a) (recursive
+// doubling, nt >= 2), it is SPLIT at s = the largest power of two below nt, the A-group size of the top level:
+// from pass s on potrf is bound by the pivot chain (64 workgroups per link at L = 16) and the GPU is nearly
+// idle, while the top-left group's part of trtri needs only columns < s:
+//   early (the lent stream, forked from the caller's after panel(s-1); every launch list cut into launches of at
+//          most CUs - the pivot launch's workgroups: a resident workgroup is not evicted by a stream priority, so
+//          the cap is what keeps the pivots' CUs free):
+//          diagonal copy k < s;  X, Y of levels h < s over instances [0, s / 2h);  X of level s
+//   main:  after the last pivot: diagonal copy k >= s;  X, Y of levels h < s over the other instances;
+//          wait for the early stream;  Y of level s
+// The early part reads D and ysc(k, k) for k < s (pivot(k), before panel(s-1)), the L planes and lsc of columns
+// < s (panels 0 .. s-1) and its own outputs; it writes Y^T tiles inside the top-left group, Y and X^T tiles of
+// the Kinv plane pair (rows or columns < s) and the xsc / ysc entries of those tiles.  Potrf's tail writes A
+// tiles >= s, the C planes, and the L planes, lsc, D and ysc(k, k) of columns >= s; it reads none of the early
+// part's outputs.  The main part's levels h < s touch only tiles of the bottom-right group.  Every tile is
+// produced by one workgroup from the same operands in the same K order either way: the results are bitwise
+// those of the unsplit order.  The join precedes the return (also under capture).
+// (An earlier form -- each recursive-doubling instance launched as soon as potrf had produced its blocks, 2
+// small launches per instance on the caller's stream between ALL passes, the update-bound early ones included
+// -- measured 15.1 vs 14.2 ms per closed step at L = 16: the small launches slowed the passes more than the
+// overlap saved.  This form, one fork at the pass where the chain becomes the bound, on a lent stream, capped:
+// 8.16-8.22 vs 8.55-8.62 ms per closed step at L = 16 against the unsplit order, four interleaved default bench
+// runs each on one box; LVAE_CI_TRTRI_EARLY=0 on this library 8.52-8.58.  In the traced step the
+// pivots of passes >= 8 start 134-207 us apart (mean 172) instead of 117-143 (mean 125) beside the early work, and
+// trtri's part after potrf takes 0.83 instead of 1.42 ms (profiles/trtri_early_timeline.txt).  Leaving
+// 128 CUs free instead of the pivot launch's 64 (LVAE_CI_EARLY_FREE) measured the same, 8.19-8.21; none free 8.27-8.28.
+// The same schedule on a stream of the library's own, of the lowest priority, was 11.1-11.6 ms: creating a fifth
+// stream alone cost 2.6 ms, whether used or not -- hence the lent stream.  profiles/trtri_early_ab.txt.)
 size_t ci_scratch_bytes(int np_, int L) { return CiScratch(nullptr, np_, L).bytes; }
 int ci_factor_f32(int np_, int L, float* A, void* scratch, _Float16* YT, float* Kinv, double* logdet,
                   int32_t* info, hipStream_t st, float* lout = nullptr);
@@ -1788,16 +1819,51 @@ int ci_factor_f32(int np_, int L, float* A, void* scratch, _Float16* YT, float* 
   const int64_t full = (int64_t)L * np_ * np_;
   _Float16* YTh = YT;
   _Float16* YTl = YT + full;
-  _Float16* Yh = reinterpret_cast<_Float16*>(A);  // A is dead after potrf: the Y planes
-  _Float16* Yl = Yh + full;
-  _Float16* XTh = reinterpret_cast<_Float16*>(Kinv);  // Kinv is written last (lauum): the X^T planes until then
+  // Kinv is written last (lauum): until then one plane pair for the X^T planes (kCiX writes tiles (j, i), j < i:
+  // strictly upper) and the row-major Y planes (tiles (i, j), i >= j: lower and diagonal) -- the same tile
+  // offsets (c16_off, or row-major), so disjoint tiles.  Nothing of trtri lives in A: the early part below may
+  // write Y tiles while potrf's trailing updates still run on A.  (The pipelined schedule keeps fp32 X in Kinv
+  // and produces no Y planes.)
+  _Float16* XTh = reinterpret_cast<_Float16*>(Kinv);
   _Float16* XTl = XTh + full;
+  _Float16* Yh = XTh;
+  _Float16* Yl = XTl;
   auto ok = [](hipError_t e) { return e == hipSuccess; };
   bool pipe = false;
+  // trtri's early part (schedule (a), recursive doubling, nt >= 2; see the schedules above): the top level's
+  // A-group size s_top, the early launches' stream and grid cap
+  static const bool early_env = !getenv("LVAE_CI_TRTRI_EARLY") || atoi(getenv("LVAE_CI_TRTRI_EARLY")) != 0;
+  // the compute units the early launches leave free (A/B runs; read once per process): by default the pending
+  // pivot launch's workgroup count, and never less than a quarter of the device for the early work
+  static const int free_env = getenv("LVAE_CI_EARLY_FREE") ? atoi(getenv("LVAE_CI_EARLY_FREE")) : -1;
+  bool early = false;
+  int s_top = 1, ecap = 0;
+  while (2 * s_top < nt) s_top *= 2;
+  SideStream* sd = nullptr;
+  // level h of the recursive doubling over the instances [i0, i0 + ni): its X and / or Y launch on q, whole
+  // (cap == 0) or cut into launches of at most cap workgroups (the list is longest K first: a launch's tiles are
+  // of nearly one length, so cutting it leaves short tails)
+  auto trtri_level = [&](int h, int i0, int ni, bool do_x, bool do_y, hipStream_t q, int cap) {
+    const int per = ni * h * h, nwg = per * L;
+    if (nwg <= 0) return;
+    if (do_x) {
+      CiGemmArgs gx{S.Lh, S.Ll, YTh, YTl, nullptr, nullptr, XTh, XTl, nullptr, np_, nt, h, per, nwg, i0};
+      for (int b0 = 0; b0 < nwg; b0 += cap > 0 ? cap : nwg) {
+        gx.bid0 = b0;
+        ci_gemm_kernel<kCiX><<<min(nwg - b0, cap > 0 ? cap : nwg), 512, 0, q>>>(gx, S);
+      }
+    }
+    if (do_y) {
+      CiGemmArgs gy{Yh, Yl, XTh, XTl, Yh, Yl, YTh, YTl, nullptr, np_, nt, h, per, nwg, i0};
+      for (int b0 = 0; b0 < nwg; b0 += cap > 0 ? cap : nwg) {
+        gy.bid0 = b0;
+        ci_gemm_kernel<kCiY><<<min(nwg - b0, cap > 0 ? cap : nwg), 512, 0, q>>>(gy, S);
+      }
+    }
+  };
   {
     ProfScope ps(LVAE_PH_POTRF, st);
     std::lock_guard<std::recursive_mutex> lock(side_mutex());
-    SideStream* sd = nullptr;
     LVAE_TRY(side_stream(sd));
     (void)zero_async(logdet, sizeof(double) * L, st);
     (void)zero_async(info, sizeof(int32_t) * L, st);
@@ -1826,6 +1892,15 @@ int ci_factor_f32(int np_, int L, float* A, void* scratch, _Float16* YT, float* 
     // its own launch (9.21 vs 9.14 ms per step), or + a 70 us split pass with the column folded in (9.58-9.63 vs 9.22)
     const bool uring = getenv("LVAE_CI_URING") && atoi(getenv("LVAE_CI_URING")) != 0;
     pipe = pmode > 0;
+    // (the lent stream stays out of a capture of the caller's: a captured call keeps the unsplit order)
+    hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
+    if (!ok(hipStreamIsCapturing(st, &cap_st))) return LVAE_ERR_LAUNCH;
+    early = early_env && fuse && !pipe && !lout && nt >= 2 && sd->early && sd->early != st &&
+            cap_st == hipStreamCaptureStatusNone;
+    {
+      const int pvwg = split ? kCiPvG * ((L + 7) / 8 * 8) : L;
+      ecap = max(sd->cus - (free_env >= 0 ? free_env : pvwg), max(sd->cus / 4, 1));
+    }
     if (fuse) {
       ci_pivot_kernel<1><<<L, 1024, 0, sd->s>>>(A, np_, 0, S, logdet, info, 0, L, g_pivot_prof);
       if (!ok(hipEventRecord(sd->piv[0], sd->s))) return LVAE_ERR_LAUNCH;
@@ -1864,6 +1939,19 @@ int ci_factor_f32(int np_, int L, float* A, void* scratch, _Float16* YT, float* 
         }
         if (m + 1 < nt) {
           ci_panel_kernel<<<dim3(nt - m - 1, L), 512, 0, st>>>(S, np_, m);
+          if (early && m == s_top - 1) {
+            // the fork: columns < s_top of L and D are complete.  On the early stream: the top-left group's
+            // diagonal tiles and levels, then the top level's X step
+            if (!ok(hipEventRecord(sd->efork, st)) || !ok(hipStreamWaitEvent(sd->early, sd->efork, 0)))
+              return LVAE_ERR_LAUNCH;
+            {
+              ProfScope pe(LVAE_PH_POTRI, sd->early);
+              ci_diag_copy_kernel<<<dim3(16 * s_top, L), 256, 0, sd->early>>>(S, np_, Yh, Yl, YTh, YTl, 0);
+              for (int h = 1; h < s_top; h *= 2) trtri_level(h, 0, s_top / (2 * h), true, true, sd->early, ecap);
+              trtri_level(s_top, 0, 1, true, false, sd->early, ecap);
+            }
+            if (!ok(hipEventRecord(sd->edone, sd->early))) return LVAE_ERR_LAUNCH;
+          }
           // column m+1 without the pivot block + the trailing tiles
           const int n1 = nt - m - 2, n2 = (nt - m - 2) * (nt - m - 1) / 2;
           if (n2 > 0 && la && n2 > 1) {
@@ -1935,13 +2023,19 @@ int ci_factor_f32(int np_, int L, float* A, void* scratch, _Float16* YT, float* 
   if (!pipe) {
     // trtri (recursive doubling, 2 launches per level): with lauum (ci_lauum_f32) the rest of potri
     ProfScope ps(LVAE_PH_POTRI, st);
-    ci_diag_copy_kernel<<<dim3(16 * nt, L), 256, 0, st>>>(S, np_, Yh, Yl, YTh, YTl);
-    for (int h = 1; h < nt; h *= 2) {
-      const int ninst = (nt + 2 * h - 1) / (2 * h), per = ninst * h * h, nwg = per * L;
-      CiGemmArgs gx{S.Lh, S.Ll, YTh, YTl, nullptr, nullptr, XTh, XTl, nullptr, np_, nt, h, per, nwg, 0};
-      ci_gemm_kernel<kCiX><<<nwg, 512, 0, st>>>(gx, S);
-      CiGemmArgs gy{Yh, Yl, XTh, XTl, Yh, Yl, YTh, YTl, nullptr, np_, nt, h, per, nwg, 0};
-      ci_gemm_kernel<kCiY><<<nwg, 512, 0, st>>>(gy, S);
+    if (early) {
+      // the rest: the bottom-right group's diagonal tiles and levels, then (the join) the top level's Y step
+      std::lock_guard<std::recursive_mutex> lock(side_mutex());
+      ci_diag_copy_kernel<<<dim3(16 * (nt - s_top), L), 256, 0, st>>>(S, np_, Yh, Yl, YTh, YTl, s_top);
+      for (int h = 1; h < s_top; h *= 2) {
+        const int i0 = s_top / (2 * h);
+        trtri_level(h, i0, (nt + 2 * h - 1) / (2 * h) - i0, true, true, st, 0);
+      }
+      if (!ok(hipStreamWaitEvent(st, sd->edone, 0))) return LVAE_ERR_LAUNCH;
+      trtri_level(s_top, 0, 1, false, true, st, 0);
+    } else {
+      ci_diag_copy_kernel<<<dim3(16 * nt, L), 256, 0, st>>>(S, np_, Yh, Yl, YTh, YTl, 0);
+      for (int h = 1; h < nt; h *= 2) trtri_level(h, 0, (nt + 2 * h - 1) / (2 * h), true, true, st, 0);
     }
   }
   LVAE_CHECK_LAUNCH();

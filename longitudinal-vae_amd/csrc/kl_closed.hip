@@ -520,7 +520,8 @@ static void kl_ymv(const KLWorkspace& ws, const float* ysc, int np_, int L, bool
   const int64_t full = (int64_t)L * np_ * np_;
   double* p2 = ws.ypart + (int64_t)L * nt * np_;
   if (!upper) {
-    const _Float16* yh = reinterpret_cast<const _Float16*>(ws.A);  // the Y planes (A is dead after potrf)
+    // the Y planes: the lower tiles of the Kinv plane pair until lauum writes K^-1 there (ci_factor_f32)
+    const _Float16* yh = reinterpret_cast<const _Float16*>(ws.Kinv);
     kl_ymv_kernel<false, false><<<dim3(ntri, L), 256, 0, st>>>(yh, yh + full, ysc, np_, x, ws.ypart, nullptr);
     kl_ymv_reduce<false><<<dim3(nt, L), 256, 0, st>>>(ws.ypart, base, np_, out);
   } else {

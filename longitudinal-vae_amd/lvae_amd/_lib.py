@@ -191,6 +191,7 @@ SIGNATURES = {
     "lvae_predict_var_f64": (_I32, [_SPEC, _SPEC, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _I32, _VP,
                                     _I32, _VP, _VP, _VP, _VP, _VP, _D, _VP, _VP, _I32, _VP, _VP, _VP]),
     "lvae_prof_enable": (_I32, [_I32]),
+    "lvae_set_early_stream": (_I32, [_VP]),
     "lvae_prof_collect": (_I32, [_VP, _VP, _I32]),
     "lvae_version": (ctypes.c_char_p, []),
 }

@@ -140,6 +140,8 @@ class LatentShardedClosedStep:
         s = getattr(self, "_vae_stream", None)
         if s is None or s.device != device:
             s = self._vae_stream = torch.cuda.Stream(device=device, priority=self.vae_stream_priority)
+            from .vae import lend_early_stream
+            lend_early_stream(device)
         return s
 
     def _finish(self, recon_loss, nll_loss, gp_loc, L):

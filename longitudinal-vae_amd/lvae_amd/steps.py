@@ -59,6 +59,8 @@ class ClosedStep:
         if s is None or s.device != device:
             s = torch.cuda.Stream(device=device, priority=self.vae_stream_priority)
             setattr(self, name, s)
+            from .vae import lend_early_stream
+            lend_early_stream(device)
         return s
 
     def forward_backward(self, img, mask, X, eps=None):

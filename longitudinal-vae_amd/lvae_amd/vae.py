@@ -32,6 +32,19 @@ def _side_stream(dev):
     return s
 
 
+def lend_early_stream(dev):
+    """Lend the weight gradient's side stream -- idle while the exact KL's factor runs, and kept for the process
+    lifetime -- to the HIP library as its early stream (lvae_set_early_stream: the blocked inverse starts part of its
+    triangular inverse there beside the factorisation's pivot-bound last passes).  No new stream: a step already uses
+    the 4 hardware queues a process has here."""
+    import ctypes
+
+    from . import _lib
+    dev = torch.device(dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().lvae_set_early_stream(ctypes.c_void_p(_side_stream(dev).cuda_stream)), "set_early_stream")
+
+
 class _ReluMaxPool2(torch.autograd.Function):
     """max_pool2d(relu(x), 2, 2) in one HIP pass (lvae_relu_maxpool2_fwd/bwd_f32, vae_ops.hip):
     one byte of argmax per output instead of torch's int64 indices, one write per input in the
