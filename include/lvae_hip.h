@@ -409,7 +409,8 @@ int lvae_natgrad_update_f64(int L, int M, double* m, double* H, const double* gr
                             void* workspace, void* stream);
 
 /* Full-batch deviance upper bound (DUBO, elbo_functions.py:86-142) of all L latent dims, and its adjoint.
- * P subjects of T consecutive rows each (N = P T rows, no varying T), M inducing points, Q covariates.      */
+ * P subjects of T consecutive rows each (N = P T rows), M inducing points, Q covariates.  Subjects of varying
+ * length: the lvae_*_seg_f64 calls further down.                                                          */
 typedef struct lvae_dubo_dims {
   int32_t L, M, P, T, Q;
   double eps;              /* jitter on K0zz */
@@ -480,6 +481,45 @@ int lvae_gp_elbo_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* 
                          const double* x, const double* z, const double* y, const double* params0,
                          const double* params1, const double* noise, const double* gelbo, double* dy,
                          double* dparams0, double* dparams1, double* dnoise, void* workspace, void* stream);
+
+/* Subjects of varying length for the DUBO and the sampled ELBO (an extension: the reference has neither; the
+ * Hensman bound's recipe, lvae_hensman_dims.seg_len).  The batch is laid out as [P, T] with T = d->T the longest
+ * subject: subject p has its seg_len[p] valid rows first, the rest of its T rows is padding.  x, mu, logv, y (and
+ * dmu, dlogv, dy) keep the shapes of the calls above in this padded layout.
+ *   seg_len: device int32 [P], or NULL = all T rows valid; NULL gives the bits of the calls above, which are
+ *     these calls with seg_len == NULL.
+ *   PRECONDITION: 1 <= seg_len[p] <= T for every p -- a full batch has no empty subject (the Hensman bound allows
+ *     0, these calls do not: lvae_*_bwd_z_f64 reads its cotangent factor back from row 0 of subject 0).  The
+ *     kernels clamp what they read to [0, T]: a bad array gives wrong numbers, never an out-of-range access.
+ *   Padding rows of x may hold any finite covariates.  Padding rows of mu, logv and y are never read (they may
+ *     hold anything, NaN included).  Padding rows of dmu, dlogv and dy are written as exact 0.
+ *   N of the constants (-N of the DUBO, -N/2 log 2 pi of the ELBO) is sum_p seg_len[p], summed on the device: the
+ *     host never reads seg_len.
+ * Per dim the padding rows of k0(x, z) and the padding rows / columns of K0_p are zeroed and those of B_p set to
+ * the identity, so B_p^-1 is the identity there and log|B_p| that of the valid block; a failing B_p still reports
+ * 20000 + col, and col lies inside the valid block.  In the fused subject pass (T <= 32) a subject's matrix-core
+ * trip counts follow seg_len[p], not T.  Everything else -- return codes and their order, info, the workspace
+ * and its size (lvae_dubo_workspace_size / lvae_gp_elbo_workspace_size of the same d), no atomics and the same
+ * bits on every call -- is as the calls above.  lvae_dubo_bwd_z_f64 / lvae_gp_elbo_bwd_z_f64 follow a *_bwd_seg
+ * call unchanged: the padding rows of the cotangent of k0(x, z) are exact zeros.                            */
+int lvae_dubo_fwd_seg_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, const lvae_dubo_dims* d,
+                          const int32_t* seg_len, const double* x, const double* z, const double* mu,
+                          const double* logv, const double* params0, const double* params1, const double* noise,
+                          double* dubo, int32_t* info, void* workspace, void* stream);
+int lvae_dubo_bwd_seg_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, const lvae_dubo_dims* d,
+                          const int32_t* seg_len, const double* x, const double* z, const double* mu,
+                          const double* logv, const double* params0, const double* params1, const double* noise,
+                          const double* gdubo, double* dmu, double* dlogv, double* dparams0, double* dparams1,
+                          double* dnoise, void* workspace, void* stream);
+int lvae_gp_elbo_fwd_seg_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1,
+                             const lvae_gp_elbo_dims* d, const int32_t* seg_len, const double* x, const double* z,
+                             const double* y, const double* params0, const double* params1, const double* noise,
+                             double* elbo, int32_t* info, void* workspace, void* stream);
+int lvae_gp_elbo_bwd_seg_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1,
+                             const lvae_gp_elbo_dims* d, const int32_t* seg_len, const double* x, const double* z,
+                             const double* y, const double* params0, const double* params1, const double* noise,
+                             const double* gelbo, double* dy, double* dparams0, double* dparams1, double* dnoise,
+                             void* workspace, void* stream);
 
 /* Learnable inducing points: the gradient of the three inducing-point bounds with respect to z [L, M, Q] (the
  * reference gets it from autograd once LVAE.py:204-208, 269 / training.py:349 are uncommented).  Each bound's

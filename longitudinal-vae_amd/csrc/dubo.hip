@@ -21,8 +21,13 @@
 // (dB_p is the adjoint of the dense form up to an antisymmetric part, which the symmetric Gram adjoint and the
 // trace of dnoise do not see: F U^T + U F^T -> 2 F U^T.)
 // (the Grams and their adjoints, the argument check, W's inverse, the info merge and the blocks of the subject walk
-// that gp_elbo.hip's has too: gp_bound.hpp / gp_bound.hip; the workspace carving: common.hpp)
-#include "gp_bound.hpp"
+// that gp_elbo.hip's has too: gp_bound.hpp / gp_bound.hip; the workspace carving: common.hpp; the subject kernel
+// itself: bound_subject.hpp)
+// Subjects of varying length (lvae_dubo_*_seg_f64, seg [P] valid rows of a [P, T] padded layout): the Grams are
+// masked after bound_grams_fwd (padding rows of X and K0_p zero, B_p the identity there: gp_bound.hpp), every kernel
+// that reads mu / logv skips the padding rows, N becomes sum_p seg[p], and the adjoint's outputs and the cotangents
+// GB / GK0 are zero on the padding.  seg == NULL is the uniform call, launch for launch.
+#include "bound_subject.hpp"
 
 namespace lvae {
 namespace {
@@ -72,93 +77,6 @@ struct DWs {
   }
 };
 
-// The fused subject pass: grid (groups, L), 512 threads.  Group g walks subjects [g kBoundS, (g + 1) kBoundS).
-// Per subject: iB_p [T,T], X_p [T,M], m_p, v_p into LDS (zero padded to whole MFMA steps); iBK_p = iB_p X_p on
-// v_mfma_f64_16x16x4 (C[(lane >> 4) + 4 r][lane & 15]) -> LDS and HBM; then Q += X_p^T iBK_p and
-// R += iBK_p^T D_p iBK_p on the lower 16 x 16 tiles, tile t = wave + 8 k in accumulators Qa[k] / Ra[k] for the
-// whole walk, p and the five scalar sums in plain registers.  One partial per (dim, group).
-__global__ __launch_bounds__(512) void dubo_subject_kernel(int M, int P, int T, int L, int nt, int64_t pstride,
-                                                           const double* __restrict__ X,
-                                                           const double* __restrict__ iB,
-                                                           const double* __restrict__ K0st,
-                                                           const double* __restrict__ ldB,
-                                                           const double* __restrict__ mu,
-                                                           const double* __restrict__ logv,
-                                                           double* __restrict__ iBK, double* __restrict__ part) {
-  __shared__ double sB[kBoundT][kBoundT + 1];
-  __shared__ double sX[kBoundT][kBoundLD];
-  __shared__ double sY[kBoundT][kBoundLD];
-  __shared__ double sm[kBoundT], sv[kBoundT];
-  __shared__ double red[8];
-  const int g = blockIdx.x, l = blockIdx.y, G = gridDim.x;
-  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
-  const int tM = (M + 15) >> 4, tT = (T + 15) >> 4, T4 = (T + 3) & ~3;
-  const int64_t N = (int64_t)P * T, TT = (int64_t)T * T;
-  int ti[kBoundTPW], tj[kBoundTPW];
-  bool on[kBoundTPW];
-  bi_f64x4 Qa[kBoundTPW], Ra[kBoundTPW] = {};
-  bound_walk_setup(wv, nt, ti, tj, on, Qa);
-  double pj = 0.0, s_mbm = 0.0, s_dv = 0.0, s_bk0 = 0.0, s_lv = 0.0, s_ldb = 0.0;
-  bound_lds_zero(tid, sB, sX, sY);
-  if (tid < kBoundT) {
-    sm[tid] = 0.0;
-    sv[tid] = 0.0;
-  }
-  const int p0 = g * kBoundS, p1 = p0 + kBoundS < P ? p0 + kBoundS : P;
-  for (int p = p0; p < p1; ++p) {
-    __syncthreads();  // the previous subject's readers are done (and the zero fill is visible)
-    bound_load_subject(tid, T, M, iB + ((int64_t)l * P + p) * TT, K0st + ((int64_t)l * P + p) * TT,
-                       X + ((int64_t)l * N + (int64_t)p * T) * M, sB, sX, s_bk0);
-    if (tid < T) {
-      const int64_t q = ((int64_t)p * T + tid) * L + l;
-      const double lv = logv[q];
-      sm[tid] = mu[q];
-      sv[tid] = exp(lv);
-      s_lv += lv;
-    }
-    if (tid == 0) s_ldb += ldB[(int64_t)l * P + p];
-    __syncthreads();
-    for (int e = tid; e < T * T; e += 512) {
-      const int i = e / T, j = e % T;
-      const double b = sB[i][j];
-      s_mbm += sm[i] * b * sm[j];
-      if (i == j) s_dv += b * sv[i];
-    }
-    // iBK_p = iB_p X_p: tT x tM tiles over the 8 waves
-    double* yp = iBK + ((int64_t)l * N + (int64_t)p * T) * M;
-    for (int tt = wv; tt < tT * tM; tt += 8)
-      bound_ibk_tile((tt / tM) << 4, (tt % tM) << 4, li, lk, T, M, T4, sB, sX, sY, yp);
-    __syncthreads();
-    if (tid < M) {
-      double q = 0.0;
-      for (int r = 0; r < T; ++r) q += sY[r][tid] * sm[r];
-      pj += q;
-    }
-#pragma unroll
-    for (int k = 0; k < kBoundTPW; ++k) {
-      if (on[k]) {
-        const int ci = (ti[k] << 4) + li, cj = (tj[k] << 4) + li;
-        for (int kk = 0; kk < T4; kk += 4) {
-          const double yb = sY[kk + lk][cj];
-          Qa[k] = __builtin_amdgcn_mfma_f64_16x16x4f64(sX[kk + lk][ci], yb, Qa[k], 0, 0, 0);
-          Ra[k] = __builtin_amdgcn_mfma_f64_16x16x4f64(sv[kk + lk] * sY[kk + lk][ci], yb, Ra[k], 0, 0, 0);
-        }
-      }
-    }
-  }
-  double* pp = part + ((int64_t)l * G + g) * pstride;
-  bound_store_tiles(pp, wv, lane, on, Qa);
-  bound_store_tiles(pp + (int64_t)nt * 256, wv, lane, on, Ra);  // R's tiles follow Q's, in the same order
-  double* pv = pp + (int64_t)2 * nt * 256;
-  if (tid < 128) pv[tid] = pj;
-  const double vals[5] = {s_mbm, s_dv, s_bk0, s_lv, s_ldb};
-#pragma unroll
-  for (int q = 0; q < 5; ++q) {
-    const double v = block_sum<512>(vals[q], red);
-    if (tid == 0) pv[128 + q] = v;
-  }
-}
-
 // The groups' partials in group order: grid (2 nt + 1, L), 256 threads.  Blocks [0, nt): a tile of Q, [nt, 2 nt):
 // of R (mirrored into the upper triangle; a diagonal tile holds both of its halves itself), the last: p, scalars.
 __global__ __launch_bounds__(256) void dubo_reduce_kernel(int M, int G, int nt, int64_t pstride,
@@ -181,7 +99,9 @@ __global__ __launch_bounds__(256) void dubo_reduce_kernel(int M, int G, int nt, 
 }
 
 // the large-T route's scalar sums, one workgroup per dim: scal[l] = m.s, diag(iB).v, iB.K0, sum logv, sum log|B_p|
-__global__ __launch_bounds__(256) void dubo_scal_kernel(int P, int T, int L, const double* __restrict__ mu,
+// (seg: the valid rows alone; mu / logv are not read on the padding)
+__global__ __launch_bounds__(256) void dubo_scal_kernel(int P, int T, int L, const int32_t* __restrict__ seg,
+                                                        const double* __restrict__ mu,
                                                         const double* __restrict__ logv,
                                                         const double* __restrict__ s, const double* __restrict__ iB,
                                                         const double* __restrict__ K0st,
@@ -192,6 +112,7 @@ __global__ __launch_bounds__(256) void dubo_scal_kernel(int P, int T, int L, con
   double v0 = 0, v1 = 0, v2 = 0, v3 = 0, v4 = 0;
   for (int64_t i = tid; i < N; i += 256) {
     const int64_t p = i / T, q = i % T;
+    if (!bound_seg_valid(seg, (int)p, (int)q, T)) continue;
     const double lv = logv[i * L + l];
     v0 += mu[i * L + l] * s[l * N + i];
     v1 += iB[l * TT + p * T * T + q * T + q] * exp(lv);
@@ -207,17 +128,20 @@ __global__ __launch_bounds__(256) void dubo_scal_kernel(int P, int T, int L, con
   }
 }
 
-// Y[l][i][:] = exp(logv[i][l]) X[l][i][:]   ([L,N,M])
-__global__ void dubo_rowscale_nm_kernel(int64_t N, int M, int L, const double* __restrict__ logv,
+// Y[l][i][:] = exp(logv[i][l]) X[l][i][:]   ([L,N,M]; seg: 0 on the padding rows, whose logv is not read)
+__global__ void dubo_rowscale_nm_kernel(int64_t N, int M, int L, int T, const int32_t* __restrict__ seg,
+                                        const double* __restrict__ logv,
                                         const double* __restrict__ X, double* __restrict__ Y) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= (int64_t)L * N * M) return;
   const int64_t l = e / (N * M), i = (e / M) % N;
-  Y[e] = exp(logv[i * L + l]) * X[e];
+  Y[e] = bound_seg_valid(seg, (int)(i / T), (int)(i % T), T) ? exp(logv[i * L + l]) * X[e] : 0.0;
 }
 
-// dubo[l] from the reduced sums, one workgroup per dim
-__global__ __launch_bounds__(256) void dubo_final_kernel(int M, double n_rows, const double* __restrict__ iW,
+// dubo[l] from the reduced sums, one workgroup per dim (seg: N = sum_p seg[p] of the P subjects, else n_rows)
+__global__ __launch_bounds__(256) void dubo_final_kernel(int M, double n_rows, int P, int T,
+                                                         const int32_t* __restrict__ seg,
+                                                         const double* __restrict__ iW,
                                                          const double* __restrict__ R, const double* __restrict__ Q,
                                                          const double* __restrict__ iK, const double* __restrict__ p,
                                                          const double* __restrict__ w,
@@ -236,25 +160,31 @@ __global__ __launch_bounds__(256) void dubo_final_kernel(int M, double n_rows, c
   a = block_sum<256>(a, red);
   b = block_sum<256>(b, red);
   c = block_sum<256>(c, red);
+  if (seg) n_rows = bound_seg_rows(seg, P, T, tid, red);
   if (tid == 0) {
     const double* sc = scal + (int64_t)l * kDuboScal;
     dubo[l] = 0.5 * ((sc[1] - a) + (sc[0] - c) - n_rows + (-ldK[l] + sc[4] + ldW[l]) - sc[3] + (sc[2] - b));
   }
 }
 
-// a = s - y;  dmu[i][l] = g_l a
-__global__ void dubo_a_kernel(int64_t N, int L, const double* __restrict__ g, const double* __restrict__ s,
+// a = s - y;  dmu[i][l] = g_l a   (seg: both exact 0 on the padding rows)
+__global__ void dubo_a_kernel(int64_t N, int L, int T, const int32_t* __restrict__ seg,
+                              const double* __restrict__ g, const double* __restrict__ s,
                               const double* __restrict__ y, double* __restrict__ a, double* __restrict__ dmu) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= N * L) return;
   const int64_t l = e / N, i = e % N;
-  const double v = s[e] - y[e];
+  const bool ok = bound_seg_valid(seg, (int)(i / T), (int)(i % T), T);
+  const double v = ok ? s[e] - y[e] : 0.0;
   a[e] = v;
-  dmu[i * L + l] = g[l] * v;
+  dmu[i * L + l] = ok ? g[l] * v : 0.0;
 }
 
-// dlogv[i][l] = g_l / 2 ((iB_ii - sum_j U_ij iBK_ij) v_i - 1): one wave per row
-__global__ __launch_bounds__(256) void dubo_dlogv_kernel(int P, int T, int M, int L, const double* __restrict__ g,
+// dlogv[i][l] = g_l / 2 ((iB_ii - sum_j U_ij iBK_ij) v_i - 1): one wave per row (seg: 0 on the padding rows, whose
+// logv is not read)
+__global__ __launch_bounds__(256) void dubo_dlogv_kernel(int P, int T, int M, int L,
+                                                         const int32_t* __restrict__ seg,
+                                                         const double* __restrict__ g,
                                                          const double* __restrict__ U,
                                                          const double* __restrict__ iBK,
                                                          const double* __restrict__ iB,
@@ -265,6 +195,10 @@ __global__ __launch_bounds__(256) void dubo_dlogv_kernel(int P, int T, int M, in
   const int lane = threadIdx.x & 63;
   if (row >= N * L) return;
   const int64_t l = row / N, i = row % N, p = i / T, q = i % T;
+  if (!bound_seg_valid(seg, (int)p, (int)q, T)) {  // (wave-uniform: a wave has one row)
+    if (lane == 0) dlogv[i * L + l] = 0.0;
+    return;
+  }
   double sum = 0.0;
   for (int j = lane; j < M; j += 64) sum += U[row * M + j] * iBK[row * M + j];
   sum = wave_sum(sum);
@@ -308,20 +242,24 @@ __global__ void dubo_dkz_kernel(int L, int M, const double* __restrict__ g, cons
   dKz[e] = 0.5 * g[l] * (iW[e] + iWRiW[e] + w[l * M + i] * w[l * M + j] - iK[e] + iKQiK[e]);
 }
 
-// VB[l,p][i][j] = v_{l,p,i} iB[l,p][i][j]
-__global__ void dubo_rowscale_tt_kernel(int P, int T, int L, const double* __restrict__ logv,
+// VB[l,p][i][j] = v_{l,p,i} iB[l,p][i][j]   (seg: v = 0 on the padding rows, whose logv is not read)
+__global__ void dubo_rowscale_tt_kernel(int P, int T, int L, const int32_t* __restrict__ seg,
+                                        const double* __restrict__ logv,
                                         const double* __restrict__ iB, double* __restrict__ VB) {
   const int64_t TT = (int64_t)T * T;
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= (int64_t)L * P * TT) return;
   const int64_t lp = e / TT, l = lp / P, p = lp % P;
   const int i = (int)((e % TT) / T);
-  VB[e] = exp(logv[(p * T + i) * L + l]) * iB[e];
+  VB[e] = bound_seg_valid(seg, (int)p, i, T) ? exp(logv[(p * T + i) * L + l]) * iB[e] : 0.0;
 }
 
 // GB = g_l / 2 (iB - iBDiB - iBK0iB - a a^T - GB);  GK0 = g_l / 2 iB
 // (lvae_dubo_bwd_z_f64 reads g_l / 2 back as GK0[l][0] / iB[l][0], bound_dkz_fix_kernel: keep GK0 = (g_l / 2) iB)
-__global__ void dubo_gb_kernel(int P, int T, int L, const double* __restrict__ g, const double* __restrict__ iB,
+// seg: both are 0 on padding rows and columns -- iB's identity there must reach neither dnoise (through dB's trace)
+// nor dparams0 (through K0's diagonal).  Element (0, 0) of subject 0 is valid (seg[0] >= 1), so the read-back holds.
+__global__ void dubo_gb_kernel(int P, int T, int L, const int32_t* __restrict__ seg, const double* __restrict__ g,
+                               const double* __restrict__ iB,
                                const double* __restrict__ a, const double* __restrict__ iBDiB,
                                const double* __restrict__ iBK0iB, double* __restrict__ GB,
                                double* __restrict__ GK0) {
@@ -330,6 +268,12 @@ __global__ void dubo_gb_kernel(int P, int T, int L, const double* __restrict__ g
   if (e >= (int64_t)L * P * TT) return;
   const int64_t lp = e / TT, l = lp / P, p = lp % P;
   const int i = (int)((e % TT) / T), j = (int)(e % T);
+  const int n = bound_seg_n(seg, (int)p, T);
+  if (i >= n || j >= n) {
+    GB[e] = 0.0;
+    GK0[e] = 0.0;
+    return;
+  }
   const double h = 0.5 * g[l];
   const double ai = a[l * N + p * T + i], aj = a[l * N + p * T + j];
   GB[e] = h * (iB[e] - iBDiB[e] - iBK0iB[e] - ai * aj - GB[e]);
@@ -345,10 +289,11 @@ extern "C" {
 
 size_t lvae_dubo_workspace_size(const lvae_dubo_dims* d) { return DWs(nullptr, *d).bytes; }
 
-int lvae_dubo_fwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, const lvae_dubo_dims* dp,
-                      const double* x, const double* z, const double* mu, const double* logv, const double* params0,
-                      const double* params1, const double* noise, double* dubo, int32_t* info, void* workspace,
-                      void* stream) {
+// (seg == NULL is the uniform call: the same launches with the same arguments as before there was a seg)
+int lvae_dubo_fwd_seg_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, const lvae_dubo_dims* dp,
+                          const int32_t* seg, const double* x, const double* z, const double* mu, const double* logv,
+                          const double* params0, const double* params1, const double* noise, double* dubo,
+                          int32_t* info, void* workspace, void* stream) {
   const BoundDims bd = dubo_dims(dp);
   LVAE_TRY(bound_check(spec0, spec1, bd));
   if (!workspace || ((uintptr_t)workspace & 255)) return -4;
@@ -359,38 +304,58 @@ int lvae_dubo_fwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spe
   DWs w((char*)workspace, d);
   LVAE_TRY(bound_grams_fwd(spec0, spec1, bd, x, z, params0, params1, noise, d.eps, w.epsv, w.X, w.Kz, w.K0st, w.Bst,
                            st));
+  if (seg) bound_seg_mask(bd, seg, w.X, w.K0st, w.Bst, st);
   LVAE_TRY(spd_inv_small_f64(M, L, w.Kz, MM, w.iK, MM, w.ldK, w.info, st));
   LVAE_TRY(spd_inv_small_f64(T, L * P, w.Bst, TT, w.iB, TT, w.ldB, w.info + L, st));
   if (T <= kBoundT) {
     const int G = bound_groups(P), nt = bound_tiles(M);
     const int64_t ps = dubo_part_stride(M);
-    dubo_subject_kernel<<<dim3(G, L), 512, 0, st>>>(M, P, T, L, nt, ps, w.X, w.iB, w.K0st, w.ldB, mu, logv, w.iBK,
-                                                   w.part);
+    if (seg)
+      dubo_subject_seg_launch(dim3(G, L), st, M, P, T, L, nt, ps, w.X, w.iB, w.K0st, w.ldB, mu, logv, w.iBK, w.part,
+                              seg);
+    else
+      dubo_subject_kernel<><<<dim3(G, L), 512, 0, st>>>(M, P, T, L, nt, ps, w.X, w.iB, w.K0st, w.ldB, mu, logv, w.iBK,
+                                                       w.part);
     dubo_reduce_kernel<<<dim3(2 * nt + 1, L), 256, 0, st>>>(M, G, nt, ps, w.part, w.Q, w.R, w.p, w.scal);
   } else {
     // large T: iBK, Q, R = iBK^T (D iBK), p = iBK^T m, s = iB m as batched products
+    // (seg: m as a masked copy in UR, idle until the backward -- 0 * NaN from a padding row would be NaN)
+    const double* mm = mu;
+    if (seg) {
+      bound_seg_masked_rows(bd, seg, mu, w.UR, st);
+      mm = w.UR;
+    }
     LVAE_TRY(gemm_small_f64(0, 0, T, M, T, 1.0, w.iB, T, P * TT, TT, w.X, M, NM, (int64_t)T * M, 0.0, w.iBK, M, NM,
                             (int64_t)T * M, L, P, st));
     LVAE_TRY(gemm_small_f64(1, 0, M, M, N, 1.0, w.X, M, NM, 0, w.iBK, M, NM, 0, 0.0, w.Q, M, MM, 0, L, 1, st));
-    dubo_rowscale_nm_kernel<<<blocks((int64_t)L * NM), 256, 0, st>>>(N, M, L, logv, w.iBK, w.tNM);
+    dubo_rowscale_nm_kernel<<<blocks((int64_t)L * NM), 256, 0, st>>>(N, M, L, T, seg, logv, w.iBK, w.tNM);
     LVAE_TRY(gemm_small_f64(1, 0, M, M, N, 1.0, w.iBK, M, NM, 0, w.tNM, M, NM, 0, 0.0, w.R, M, MM, 0, L, 1, st));
-    LVAE_TRY(gemm_small_f64(1, 0, M, 1, N, 1.0, w.iBK, M, NM, 0, mu, L, 1, 0, 0.0, w.p, 1, M, 0, L, 1, st));
-    LVAE_TRY(gemm_small_f64(0, 0, T, 1, T, 1.0, w.iB, T, P * TT, TT, mu, L, 1, (int64_t)T * L, 0.0, w.s, 1, N, T, L, P,
+    LVAE_TRY(gemm_small_f64(1, 0, M, 1, N, 1.0, w.iBK, M, NM, 0, mm, L, 1, 0, 0.0, w.p, 1, M, 0, L, 1, st));
+    LVAE_TRY(gemm_small_f64(0, 0, T, 1, T, 1.0, w.iB, T, P * TT, TT, mm, L, 1, (int64_t)T * L, 0.0, w.s, 1, N, T, L, P,
                             st));
-    dubo_scal_kernel<<<L, 256, 0, st>>>(P, T, L, mu, logv, w.s, w.iB, w.K0st, w.ldB, w.scal);
+    dubo_scal_kernel<<<L, 256, 0, st>>>(P, T, L, seg, mu, logv, w.s, w.iB, w.K0st, w.ldB, w.scal);
   }
   LVAE_TRY(bound_w_inverse(L, M, w.Kz, w.Q, w.W, w.iW0, w.E, w.iW, w.ldW, w.info + L + L * P, st));
   LVAE_TRY(gemm_small_f64(0, 0, M, 1, M, 1.0, w.iW, M, MM, 0, w.p, 1, M, 0, 0.0, w.w, 1, M, 0, L, 1, st));
-  dubo_final_kernel<<<L, 256, 0, st>>>(M, (double)N, w.iW, w.R, w.Q, w.iK, w.p, w.w, w.scal, w.ldK, w.ldW, dubo);
+  dubo_final_kernel<<<L, 256, 0, st>>>(M, (double)N, P, T, seg, w.iW, w.R, w.Q, w.iK, w.p, w.w, w.scal, w.ldK, w.ldW, dubo);
   if (info) bound_info(L, P, w.info, info, st);
   LVAE_CHECK_LAUNCH();
   return 0;
 }
 
-int lvae_dubo_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, const lvae_dubo_dims* dp,
+int lvae_dubo_fwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, const lvae_dubo_dims* dp,
                       const double* x, const double* z, const double* mu, const double* logv, const double* params0,
-                      const double* params1, const double* noise, const double* gdubo, double* dmu, double* dlogv,
-                      double* dparams0, double* dparams1, double* dnoise, void* workspace, void* stream) {
+                      const double* params1, const double* noise, double* dubo, int32_t* info, void* workspace,
+                      void* stream) {
+  return lvae_dubo_fwd_seg_f64(spec0, spec1, dp, nullptr, x, z, mu, logv, params0, params1, noise, dubo, info,
+                               workspace, stream);
+}
+
+int lvae_dubo_bwd_seg_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, const lvae_dubo_dims* dp,
+                          const int32_t* seg, const double* x, const double* z, const double* mu, const double* logv,
+                          const double* params0, const double* params1, const double* noise, const double* gdubo,
+                          double* dmu, double* dlogv, double* dparams0, double* dparams1, double* dnoise,
+                          void* workspace, void* stream) {
   (void)noise;
   const BoundDims bd = dubo_dims(dp);
   LVAE_TRY(bound_check(spec0, spec1, bd));
@@ -403,14 +368,20 @@ int lvae_dubo_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spe
   DWs w((char*)workspace, d);
   // U = iBK iW ; s = iB m ; y = U p ; a = s - y -> dmu ; dlogv
   LVAE_TRY(gemm_small_f64(0, 0, N, M, M, 1.0, w.iBK, M, NM, 0, w.iW, M, MM, 0, 0.0, w.U, M, NM, 0, L, 1, st));
-  LVAE_TRY(gemm_small_f64(0, 0, T, 1, T, 1.0, w.iB, T, P * TT, TT, mu, L, 1, (int64_t)T * L, 0.0, w.s, 1, N, T, L, P,
+  // (seg: m as a masked copy in dX, which this call only forms further down)
+  const double* mm = mu;
+  if (seg) {
+    bound_seg_masked_rows(bd, seg, mu, w.dX, st);
+    mm = w.dX;
+  }
+  LVAE_TRY(gemm_small_f64(0, 0, T, 1, T, 1.0, w.iB, T, P * TT, TT, mm, L, 1, (int64_t)T * L, 0.0, w.s, 1, N, T, L, P,
                           st));
   LVAE_TRY(gemm_small_f64(0, 0, N, 1, M, 1.0, w.U, M, NM, 0, w.p, 1, M, 0, 0.0, w.y, 1, N, 0, L, 1, st));
-  dubo_a_kernel<<<blocks((int64_t)N * L), 256, 0, st>>>(N, L, gdubo, w.s, w.y, w.a, dmu);
-  dubo_dlogv_kernel<<<cdiv((int64_t)N * L, 4), 256, 0, st>>>(P, T, M, L, gdubo, w.U, w.iBK, w.iB, logv, dlogv);
+  dubo_a_kernel<<<blocks((int64_t)N * L), 256, 0, st>>>(N, L, T, seg, gdubo, w.s, w.y, w.a, dmu);
+  dubo_dlogv_kernel<<<cdiv((int64_t)N * L, 4), 256, 0, st>>>(P, T, M, L, seg, gdubo, w.U, w.iBK, w.iB, logv, dlogv);
   // UR = U R ; F = iB (D iBK) ; Z = iBK iK ; dX = (iBK + UR - F) iW, then g (dX - Z - a w^T)
   LVAE_TRY(gemm_small_f64(0, 0, N, M, M, 1.0, w.U, M, NM, 0, w.R, M, MM, 0, 0.0, w.UR, M, NM, 0, L, 1, st));
-  dubo_rowscale_nm_kernel<<<blocks((int64_t)L * NM), 256, 0, st>>>(N, M, L, logv, w.iBK, w.tNM);
+  dubo_rowscale_nm_kernel<<<blocks((int64_t)L * NM), 256, 0, st>>>(N, M, L, T, seg, logv, w.iBK, w.tNM);
   LVAE_TRY(gemm_small_f64(0, 0, T, M, T, 1.0, w.iB, T, P * TT, TT, w.tNM, M, NM, TM, 0.0, w.F, M, NM, TM, L, P, st));
   LVAE_TRY(gemm_small_f64(0, 0, N, M, M, 1.0, w.iBK, M, NM, 0, w.iK, M, MM, 0, 0.0, w.Z, M, NM, 0, L, 1, st));
   dubo_sum3_kernel<<<blocks((int64_t)L * NM), 256, 0, st>>>((int64_t)L * NM, w.iBK, w.UR, w.F, w.tNM);
@@ -423,7 +394,7 @@ int lvae_dubo_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spe
   LVAE_TRY(gemm_small_f64(0, 0, M, M, M, 1.0, w.iKQ, M, MM, 0, w.iK, M, MM, 0, 0.0, w.iKQiK, M, MM, 0, L, 1, st));
   dubo_dkz_kernel<<<blocks(L * MM), 256, 0, st>>>(L, M, gdubo, w.iK, w.iW, w.iWRiW, w.w, w.iKQiK, w.dKz);
   // dB_p, dK0_p (Z now holds U - Z, UR holds UR - 2 F)
-  dubo_rowscale_tt_kernel<<<blocks(LTT), 256, 0, st>>>(P, T, L, logv, w.iB, w.VB);
+  dubo_rowscale_tt_kernel<<<blocks(LTT), 256, 0, st>>>(P, T, L, seg, logv, w.iB, w.VB);
   LVAE_TRY(gemm_small_f64(0, 0, T, T, T, 1.0, w.iB, T, P * TT, TT, w.VB, T, P * TT, TT, 0.0, w.iBDiB, T, P * TT, TT,
                           L, P, st));
   LVAE_TRY(gemm_small_f64(0, 0, T, T, T, 1.0, w.K0st, T, P * TT, TT, w.iB, T, P * TT, TT, 0.0, w.K0iB, T, P * TT, TT,
@@ -432,7 +403,7 @@ int lvae_dubo_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spe
                           TT, L, P, st));
   LVAE_TRY(gemm_small_f64(0, 1, T, T, M, 1.0, w.Z, M, NM, TM, w.iBK, M, NM, TM, 0.0, w.GB, T, P * TT, TT, L, P, st));
   LVAE_TRY(gemm_small_f64(0, 1, T, T, M, 1.0, w.UR, M, NM, TM, w.U, M, NM, TM, 1.0, w.GB, T, P * TT, TT, L, P, st));
-  dubo_gb_kernel<<<blocks(LTT), 256, 0, st>>>(P, T, L, gdubo, w.iB, w.a, w.iBDiB, w.iBK0iB, w.GB, w.GK0);
+  dubo_gb_kernel<<<blocks(LTT), 256, 0, st>>>(P, T, L, seg, gdubo, w.iB, w.a, w.iBDiB, w.iBK0iB, w.GB, w.GK0);
   // hyper-parameter gradients through the four Grams
   LVAE_TRY(bound_grams_bwd(spec0, spec1, bd, x, z, params0, params1, w.dX, w.dKz, w.GK0, w.GB, dparams0, dparams1,
                            dnoise, w.gpart, st));
@@ -440,7 +411,16 @@ int lvae_dubo_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spe
   return 0;
 }
 
-// dz from the dX / dKz lvae_dubo_bwd_f64 left in the workspace (gdubo[l] is already inside them)
+int lvae_dubo_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, const lvae_dubo_dims* dp,
+                      const double* x, const double* z, const double* mu, const double* logv, const double* params0,
+                      const double* params1, const double* noise, const double* gdubo, double* dmu, double* dlogv,
+                      double* dparams0, double* dparams1, double* dnoise, void* workspace, void* stream) {
+  return lvae_dubo_bwd_seg_f64(spec0, spec1, dp, nullptr, x, z, mu, logv, params0, params1, noise, gdubo, dmu, dlogv,
+                               dparams0, dparams1, dnoise, workspace, stream);
+}
+
+// dz from the dX / dKz lvae_dubo_bwd_f64 left in the workspace (gdubo[l] is already inside them).  After a
+// lvae_dubo_bwd_seg_f64 nothing changes: the padding rows of dX are exact zeros.
 int lvae_dubo_bwd_z_f64(const lvae_kernel_spec* spec0, const lvae_dubo_dims* dp, const double* x, const double* z,
                         const double* params0, double* dz, void* workspace, void* zworkspace, void* stream) {
   const BoundDims bd = dubo_dims(dp);

@@ -60,6 +60,32 @@ __global__ void bound_info_kernel(int L, int P, const int32_t* __restrict__ w, i
   info[l] = v;
 }
 
+// varying T: padding rows of X -> 0, padding rows / columns of K0_p -> 0 and of B_p -> I
+__global__ void bound_seg_mask_kernel(int L, int P, int T, int M, const int32_t* __restrict__ seg,
+                                      double* __restrict__ X, double* __restrict__ K0st, double* __restrict__ Bst) {
+  const int64_t N = (int64_t)P * T, nxz = (int64_t)L * N * M, TT = (int64_t)T * T, nst = (int64_t)L * P * TT;
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < nxz) {
+    const int64_t row = (e / M) % N;
+    if (!bound_seg_valid(seg, (int)(row / T), (int)(row % T), T)) X[e] = 0.0;
+  } else if (e < nxz + nst) {
+    const int64_t f = e - nxz;
+    const int p = (int)((f / TT) % P), i = (int)((f % TT) / T), j = (int)(f % T), n = bound_seg_n(seg, p, T);
+    if (i >= n || j >= n) {
+      K0st[f] = 0.0;
+      Bst[f] = (i == j) ? 1.0 : 0.0;
+    }
+  }
+}
+
+__global__ void bound_seg_masked_rows_kernel(int64_t N, int L, int T, const int32_t* __restrict__ seg,
+                                             const double* __restrict__ mu, double* __restrict__ mm) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= N * L) return;
+  const int64_t i = e / L;
+  mm[e] = bound_seg_valid(seg, (int)(i / T), (int)(i % T), T) ? mu[e] : 0.0;
+}
+
 // The four Grams X [N,M], Kz [M,M], K0_p and B_p [P][T,T] as adjoint jobs.  bound_gram_part_doubles passes null
 // pointers: gram_bwd_part_bytes reads the shapes alone.
 void bound_bwd_jobs(const BoundDims& d, const double* x, const double* z, const double* params0,
@@ -105,6 +131,16 @@ int bound_grams_fwd(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1
   return gram_multi_f64(specs, jobs, 4, L, st);
 }
 
+void bound_seg_mask(const BoundDims& d, const int32_t* seg, double* X, double* K0st, double* Bst, hipStream_t st) {
+  const int64_t n = (int64_t)d.L * d.P * d.T * d.M + (int64_t)d.L * d.P * d.T * d.T;
+  bound_seg_mask_kernel<<<blocks(n), 256, 0, st>>>(d.L, d.P, d.T, d.M, seg, X, K0st, Bst);
+}
+
+void bound_seg_masked_rows(const BoundDims& d, const int32_t* seg, const double* mu, double* mm, hipStream_t st) {
+  const int64_t N = (int64_t)d.P * d.T;
+  bound_seg_masked_rows_kernel<<<blocks(N * d.L), 256, 0, st>>>(N, d.L, d.T, seg, mu, mm);
+}
+
 int bound_grams_bwd(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, const BoundDims& d, const double* x,
                     const double* z, const double* params0, const double* params1, const double* dX,
                     const double* dKz, const double* dK0st, const double* dBst, double* dparams0, double* dparams1,
@@ -132,7 +168,9 @@ void bound_z_jobs(int M, int N, int Q, const double* x, const double* z, const d
 
 namespace {
 // out = (first ? dKz : out) + h_l (S - T), h_l = GK0[l][0] / iB[l][0]: the factor the backward gave its iB term
-// (g_l / 2 in the DUBO, -G_l / 2 in the ELBO), which is also the factor of T inside dKz
+// (g_l / 2 in the DUBO, -G_l / 2 in the ELBO), which is also the factor of T inside dKz.  Element [l][0] is row 0,
+// column 0 of subject 0: with varying T (the *_seg_f64 calls) GK0 is zeroed on padding rows and columns, and this
+// one is never padding because seg_len[0] >= 1 -- a mask or a reordering of the subjects must keep it so.
 __global__ void bound_dkz_fix_kernel(int L, int64_t MM, int64_t PTT, int first, const double* __restrict__ dKz,
                                      const double* __restrict__ S, const double* __restrict__ T,
                                      const double* __restrict__ GK0, const double* __restrict__ iB,

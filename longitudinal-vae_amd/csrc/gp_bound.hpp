@@ -90,6 +90,41 @@ void bound_info(int L, int P, const int32_t* w, int32_t* info, hipStream_t st);
 int bound_w_inverse(int L, int M, const double* Kz, const double* Q, double* W, double* iW0, double* E, double* iW,
                     double* ldW, int32_t* info, hipStream_t st);
 
+// ---- varying T (the DUBO's and the ELBO's *_seg_f64 calls): a [P, T] layout, subject p's seg[p] valid rows first ----
+
+// valid rows of subject p, clamped to [0, T]: a bad seg gives wrong numbers, never an index out of range
+// (seg == NULL: all T rows)
+__device__ __forceinline__ int bound_seg_n(const int32_t* __restrict__ seg, int p, int T) {
+  if (!seg) return T;
+  const int n = seg[p];
+  return n < 0 ? 0 : (n > T ? T : n);
+}
+__device__ __forceinline__ bool bound_seg_valid(const int32_t* __restrict__ seg, int p, int q, int T) {
+  return q < bound_seg_n(seg, p, T);
+}
+
+// the subject kernels take seg as an optional trailing argument (a pack of none or one): the uniform instantiation
+// then has the argument list it had before there was a seg
+__device__ __forceinline__ const int32_t* bound_seg_arg() { return nullptr; }
+__device__ __forceinline__ const int32_t* bound_seg_arg(const int32_t* seg) { return seg; }
+
+// sum_p seg[p] as a double (integers: exact in any order), by all 256 threads of a workgroup
+__device__ __forceinline__ double bound_seg_rows(const int32_t* __restrict__ seg, int P, int T, int tid,
+                                                 double* red) {
+  double n = 0.0;
+  for (int p = tid; p < P; p += 256) n += (double)bound_seg_n(seg, p, T);
+  return block_sum<256>(n, red);
+}
+
+// padding rows of X -> 0, padding rows / columns of K0_p -> 0 and of B_p -> I, in one launch (the Hensman bound's
+// recipe, hn_seg_mask_kernel).  iB_p is then the identity on the padding, iBK_p has zero padding rows and log|B_p|
+// is that of the valid block.
+void bound_seg_mask(const BoundDims& d, const int32_t* seg, double* X, double* K0st, double* Bst, hipStream_t st);
+
+// mm[i][l] = mu[i][l] on the valid rows, 0 on the padding rows whatever mu holds there ([N, L] like mu itself: the
+// products that take mu as a GEMM operand must not read the padding, 0 * NaN is NaN)
+void bound_seg_masked_rows(const BoundDims& d, const int32_t* seg, const double* mu, double* mm, hipStream_t st);
+
 // ---- the fused subject walk (512 threads: 8 waves; lane = 16 lk + li) ----
 
 // lower tile t -> (row tile, column tile), row-major over the lower triangle

@@ -1,7 +1,9 @@
 // gp_elbo.hip -- full-batch sampled GP ELBO (type_KL 'GPapprox', elbo_functions.py:36-84) of all L latent dims and
 // all S samples of the latent, and its analytic adjoint.  fp64 throughout; subjects are P blocks of T consecutive
 // rows, N = P T.  The notation is dubo.hip's; what the two share (and share with hensman.hip) is gp_bound.hpp /
-// gp_bound.hip.
+// gp_bound.hip; the subject kernel itself is in bound_subject.hpp.  Subjects of varying length
+// (lvae_gp_elbo_*_seg_f64): as dubo.hip's -- masked Grams, y read on the valid rows only, N = sum_p seg[p], dy and
+// the cotangents GB / GK0 zero on the padding; seg == NULL is the uniform call, launch for launch.
 //
 // Per latent dim (nothing here depends on the sample):
 //   X = k0(x, z) [N,M]   Kz = k0(z, z) + eps I   K0_p = k0(x_p, x_p)   B_p = k1(x_p, x_p) + noise I
@@ -21,12 +23,11 @@
 //   dX    = A Gam Wm^T - G (U - Z)
 //   dKz   = -1/2 (G (iW - iK + iK Q iK) + Wm Gam Wm^T)      dK0_p = -G/2 iB_p
 //   dB_p  = -1/2 (G (iB - iB K0 iB - (U - Z) iBK^T) - A Gam A^T)_p
-#include "gp_bound.hpp"
+#include "bound_subject.hpp"
 
 namespace lvae {
 namespace {
 
-constexpr int kGeS = 16;      // sample columns of one call: one 16-wide MFMA column block (zero padded past S)
 constexpr int kGeScal = 24;   // scalar slots per dim: 0 sum iB.K0, 1 sum log|B_p|, 8 + s: sum_p y_s^T iB_p y_s
 constexpr double kHalfLog2Pi = 0.91893853320467274178;
 
@@ -73,109 +74,6 @@ struct GWs {
   }
 };
 
-// The fused subject pass: grid (groups, L), 512 threads.  Group g walks subjects [g kBoundS, (g + 1) kBoundS).
-// Per subject: iB_p [T,T], X_p [T,M] and the samples Y_p [T,16] (columns S.. zero) into LDS, zero padded to whole
-// MFMA steps; iBK_p = iB_p X_p and s_p = iB_p Y_p on v_mfma_f64_16x16x4 (C[(lane >> 4) + 4 r][lane & 15]), iBK_p
-// -> LDS and HBM, s_p -> HBM with y.s summed per lane (a lane's column IS its sample); then Q += X_p^T iBK_p on
-// the lower 16 x 16 tiles (tile t = wave + 8 k in Qa[k]) and Pm += iBK_p^T Y_p, row tile = wave, both in
-// accumulators for the whole walk.  One partial per (dim, group).
-__global__ __launch_bounds__(512) void gp_elbo_subject_kernel(int M, int P, int T, int L, int S, int nt,
-                                                              int64_t pstride, const double* __restrict__ X,
-                                                              const double* __restrict__ iB,
-                                                              const double* __restrict__ K0st,
-                                                              const double* __restrict__ ldB,
-                                                              const double* __restrict__ y,
-                                                              double* __restrict__ iBK, double* __restrict__ sbuf,
-                                                              double* __restrict__ part) {
-  __shared__ double sB[kBoundT][kBoundT + 1];
-  __shared__ double sX[kBoundT][kBoundLD];
-  __shared__ double sY[kBoundT][kBoundLD];
-  __shared__ double sS[kBoundT][kGeS + 1];
-  __shared__ double sq[8][64];
-  __shared__ double red[8];
-  const int g = blockIdx.x, l = blockIdx.y, G = gridDim.x;
-  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
-  const int tM = (M + 15) >> 4, tT = (T + 15) >> 4, T4 = (T + 3) & ~3;
-  const int64_t N = (int64_t)P * T, TT = (int64_t)T * T;
-  int ti[kBoundTPW], tj[kBoundTPW];
-  bool on[kBoundTPW];
-  bi_f64x4 Qa[kBoundTPW];
-  bi_f64x4 Pa = {0.0, 0.0, 0.0, 0.0};
-  bound_walk_setup(wv, nt, ti, tj, on, Qa);
-  double s_ys = 0.0, s_bk0 = 0.0, s_ldb = 0.0;
-  bound_lds_zero(tid, sB, sX, sY);
-  // (sS likewise: rows T.., sample columns S..)
-  for (int e = tid; e < kBoundT * (kGeS + 1); e += 512) (&sS[0][0])[e] = 0.0;
-  const int p0 = g * kBoundS, p1 = p0 + kBoundS < P ? p0 + kBoundS : P;
-  for (int p = p0; p < p1; ++p) {
-    __syncthreads();  // the previous subject's readers are done (and the zero fill is visible)
-    bound_load_subject(tid, T, M, iB + ((int64_t)l * P + p) * TT, K0st + ((int64_t)l * P + p) * TT,
-                       X + ((int64_t)l * N + (int64_t)p * T) * M, sB, sX, s_bk0);
-    for (int e = tid; e < T * kGeS; e += 512) {
-      const int i = e >> 4, s = e & 15;
-      if (s < S) sS[i][s] = y[((int64_t)s * N + (int64_t)p * T + i) * L + l];
-    }
-    if (tid == 0) s_ldb += ldB[(int64_t)l * P + p];
-    __syncthreads();
-    // iBK_p = iB_p X_p (tT x tM tiles) and s_p = iB_p Y_p (tT tiles) over the 8 waves
-    double* yp = iBK + ((int64_t)l * N + (int64_t)p * T) * M;
-    double* sp = sbuf + ((int64_t)l * N + (int64_t)p * T) * kGeS;
-    for (int tt = wv; tt < tT * tM + tT; tt += 8) {
-      if (tt < tT * tM) {
-        bound_ibk_tile((tt / tM) << 4, (tt % tM) << 4, li, lk, T, M, T4, sB, sX, sY, yp);
-      } else {
-        const int r0 = (tt - tT * tM) << 4;
-        bi_f64x4 acc = {0.0, 0.0, 0.0, 0.0};
-        for (int kk = 0; kk < T4; kk += 4)
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(sB[r0 + li][kk + lk], sS[kk + lk][li], acc, 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int i = r0 + lk + 4 * r;
-          if (i < T) {
-            sp[i * kGeS + li] = acc[r];
-            s_ys += acc[r] * sS[i][li];
-          }
-        }
-      }
-    }
-    __syncthreads();
-    if (wv < tM) {
-      const int ci = (wv << 4) + li;
-      for (int kk = 0; kk < T4; kk += 4)
-        Pa = __builtin_amdgcn_mfma_f64_16x16x4f64(sY[kk + lk][ci], sS[kk + lk][li], Pa, 0, 0, 0);
-    }
-#pragma unroll
-    for (int k = 0; k < kBoundTPW; ++k) {
-      if (on[k]) {
-        const int ci = (ti[k] << 4) + li, cj = (tj[k] << 4) + li;
-        for (int kk = 0; kk < T4; kk += 4)
-          Qa[k] = __builtin_amdgcn_mfma_f64_16x16x4f64(sX[kk + lk][ci], sY[kk + lk][cj], Qa[k], 0, 0, 0);
-      }
-    }
-  }
-  double* pp = part + ((int64_t)l * G + g) * pstride;
-  bound_store_tiles(pp, wv, lane, on, Qa);
-  double* pm = pp + (int64_t)nt * 256;
-  if (wv < tM) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) pm[((wv << 4) + lk + 4 * r) * kGeS + li] = Pa[r];
-  }
-  double* pv = pm + 128 * kGeS;
-  sq[wv][lane] = s_ys;
-  const double bk0 = block_sum<512>(s_bk0, red);  // (its barriers also publish sq)
-  const double ldb = block_sum<512>(s_ldb, red);
-  if (tid == 0) {
-    pv[0] = bk0;
-    pv[1] = ldb;
-  }
-  if (tid < kGeS) {
-    double v = 0.0;
-    for (int w = 0; w < 8; ++w)
-      for (int q = 0; q < 4; ++q) v += sq[w][q * 16 + tid];
-    pv[8 + tid] = v;
-  }
-}
-
 // The groups' partials in group order: grid (nt + 9, L), 256 threads.  Blocks [0, nt): a tile of Q (mirrored into
 // the upper triangle; a diagonal tile holds both of its halves itself), the next 8: 16 rows of Pm [M][16] each
 // (one element a thread), the last: the scalars.
@@ -201,13 +99,14 @@ __global__ __launch_bounds__(256) void gp_elbo_reduce_kernel(int M, int G, int n
   }
 }
 
-// the large-T route: Yp[l][i][s] = y[s][i][l], columns S.. zero
-__global__ void gp_elbo_pack_kernel(int64_t N, int L, int S, const double* __restrict__ y, double* __restrict__ Yp) {
+// the large-T route: Yp[l][i][s] = y[s][i][l], columns S.. zero (seg: the padding rows too, whose y is not read)
+__global__ void gp_elbo_pack_kernel(int64_t N, int L, int S, int T, const int32_t* __restrict__ seg,
+                                    const double* __restrict__ y, double* __restrict__ Yp) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= (int64_t)L * N * kGeS) return;
   const int64_t l = e / (N * kGeS), i = (e / kGeS) % N;
   const int s = (int)(e % kGeS);
-  Yp[e] = s < S ? y[((int64_t)s * N + i) * L + l] : 0.0;
+  Yp[e] = (s < S && bound_seg_valid(seg, (int)(i / T), (int)(i % T), T)) ? y[((int64_t)s * N + i) * L + l] : 0.0;
 }
 
 // the large-T route's scalar sums, one workgroup per dim (thread = (row phase, sample column))
@@ -239,8 +138,9 @@ __global__ __launch_bounds__(256) void gp_elbo_scal_kernel(int P, int T, const d
   }
 }
 
-// elbo[s][l] from the reduced sums, one workgroup per dim
-__global__ __launch_bounds__(256) void gp_elbo_final_kernel(int M, int L, int S, double n_rows,
+// elbo[s][l] from the reduced sums, one workgroup per dim (seg: N = sum_p seg[p] of the P subjects, else n_rows)
+__global__ __launch_bounds__(256) void gp_elbo_final_kernel(int M, int L, int S, double n_rows, int P, int T,
+                                                            const int32_t* __restrict__ seg,
                                                             const double* __restrict__ Q,
                                                             const double* __restrict__ iK,
                                                             const double* __restrict__ Pm,
@@ -258,6 +158,7 @@ __global__ __launch_bounds__(256) void gp_elbo_final_kernel(int M, int L, int S,
   for (int e = tid; e < M * kGeS; e += 256) c += Pm[(int64_t)l * M * kGeS + e] * Wm[(int64_t)l * M * kGeS + e];
   sq[tid] = c;
   b = block_sum<256>(b, red);
+  if (seg) n_rows = bound_seg_rows(seg, P, T, tid, red);
   if (tid < S) {
     double pw = 0.0;
     for (int r = 0; r < 16; ++r) pw += sq[r * 16 + tid];
@@ -282,13 +183,21 @@ __global__ void gp_elbo_g_kernel(int L, int M, int S, const double* __restrict__
 }
 
 // A = s - U Pm (A holds U Pm on entry);  AG = A Gam;  dy[s][i][l] = -g[s][l] A[l][i][s]
-__global__ void gp_elbo_a_kernel(int64_t N, int L, int S, const double* __restrict__ g,
+// (seg: A, AG and dy are exact 0 on the padding rows)
+__global__ void gp_elbo_a_kernel(int64_t N, int L, int S, int T, const int32_t* __restrict__ seg,
+                                 const double* __restrict__ g,
                                  const double* __restrict__ sbuf, double* __restrict__ A, double* __restrict__ AG,
                                  double* __restrict__ dy) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= (int64_t)L * N * kGeS) return;
   const int64_t l = e / (N * kGeS), i = (e / kGeS) % N;
   const int s = (int)(e % kGeS);
+  if (!bound_seg_valid(seg, (int)(i / T), (int)(i % T), T)) {
+    A[e] = 0.0;
+    AG[e] = 0.0;
+    if (s < S) dy[((int64_t)s * N + i) * L + l] = 0.0;
+    return;
+  }
   const double a = sbuf[e] - A[e];
   A[e] = a;
   if (s < S) {
@@ -321,11 +230,23 @@ __global__ void gp_elbo_dkz_kernel(int L, int64_t MM, const double* __restrict__
 
 // GB = -1/2 (G_l (iB - iBK0iB - GB) - AAt);  GK0 = -G_l / 2 iB   (GB holds (U - Z) iBK^T, AAt A Gam A^T on entry)
 // (lvae_gp_elbo_bwd_z_f64 reads -G_l / 2 back as GK0[l][0] / iB[l][0], bound_dkz_fix_kernel: keep GK0 = (-G_l / 2) iB)
-__global__ void gp_elbo_gb_kernel(int64_t PTT, int L, const double* __restrict__ Gs, const double* __restrict__ iB,
+// seg: both are 0 on padding rows and columns -- iB's identity there must reach neither dnoise (through dB's trace)
+// nor dparams0 (through K0's diagonal).  Element (0, 0) of subject 0 is valid (seg[0] >= 1), so the read-back holds.
+__global__ void gp_elbo_gb_kernel(int64_t PTT, int L, int P, int T, const int32_t* __restrict__ seg,
+                                  const double* __restrict__ Gs, const double* __restrict__ iB,
                                   const double* __restrict__ iBK0iB, const double* __restrict__ AAt,
                                   double* __restrict__ GB, double* __restrict__ GK0) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= L * PTT) return;
+  if (seg) {
+    const int64_t TT = (int64_t)T * T;
+    const int p = (int)((e / TT) % P), i = (int)((e % TT) / T), j = (int)(e % T), n = bound_seg_n(seg, p, T);
+    if (i >= n || j >= n) {
+      GB[e] = 0.0;
+      GK0[e] = 0.0;
+      return;
+    }
+  }
   const double G = Gs[e / PTT];
   GB[e] = -0.5 * (G * (iB[e] - iBK0iB[e] - GB[e]) - AAt[e]);
   GK0[e] = -0.5 * G * iB[e];
@@ -345,10 +266,11 @@ extern "C" {
 
 size_t lvae_gp_elbo_workspace_size(const lvae_gp_elbo_dims* d) { return GWs(nullptr, *d).bytes; }
 
-int lvae_gp_elbo_fwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, const lvae_gp_elbo_dims* dp,
-                         const double* x, const double* z, const double* y, const double* params0,
-                         const double* params1, const double* noise, double* elbo, int32_t* info, void* workspace,
-                         void* stream) {
+// (seg == NULL is the uniform call: the same launches with the same arguments as before there was a seg)
+int lvae_gp_elbo_fwd_seg_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1,
+                             const lvae_gp_elbo_dims* dp, const int32_t* seg, const double* x, const double* z,
+                             const double* y, const double* params0, const double* params1, const double* noise,
+                             double* elbo, int32_t* info, void* workspace, void* stream) {
   LVAE_TRY(ge_check(spec0, spec1, dp));
   if (!workspace || ((uintptr_t)workspace & 255)) return -4;
   hipStream_t st = (hipStream_t)stream;
@@ -359,17 +281,22 @@ int lvae_gp_elbo_fwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* 
   GWs w((char*)workspace, d);
   LVAE_TRY(bound_grams_fwd(spec0, spec1, ge_dims(dp), x, z, params0, params1, noise, d.eps, w.epsv, w.X, w.Kz,
                            w.K0st, w.Bst, st));
+  if (seg) bound_seg_mask(ge_dims(dp), seg, w.X, w.K0st, w.Bst, st);
   LVAE_TRY(spd_inv_small_f64(M, L, w.Kz, MM, w.iK, MM, w.ldK, w.info, st));
   LVAE_TRY(spd_inv_small_f64(T, L * P, w.Bst, TT, w.iB, TT, w.ldB, w.info + L, st));
   if (T <= kBoundT) {
     const int G = bound_groups(P), nt = bound_tiles(M);
     const int64_t ps = ge_part_stride(M);
-    gp_elbo_subject_kernel<<<dim3(G, L), 512, 0, st>>>(M, P, T, L, S, nt, ps, w.X, w.iB, w.K0st, w.ldB, y, w.iBK,
-                                                      w.s, w.part);
+    if (seg)
+      gp_elbo_subject_seg_launch(dim3(G, L), st, M, P, T, L, S, nt, ps, w.X, w.iB, w.K0st, w.ldB, y, w.iBK, w.s,
+                                 w.part, seg);
+    else
+      gp_elbo_subject_kernel<><<<dim3(G, L), 512, 0, st>>>(M, P, T, L, S, nt, ps, w.X, w.iB, w.K0st, w.ldB, y, w.iBK,
+                                                          w.s, w.part);
     gp_elbo_reduce_kernel<<<dim3(nt + 9, L), 256, 0, st>>>(M, G, nt, ps, w.part, w.Q, w.Pm, w.scal);
   } else {
     // large T: iBK, Q, Pm = iBK^T Y, s_p = iB_p Y_p as batched products
-    gp_elbo_pack_kernel<<<blocks((int64_t)L * NS), 256, 0, st>>>(N, L, S, y, w.Yp);
+    gp_elbo_pack_kernel<<<blocks((int64_t)L * NS), 256, 0, st>>>(N, L, S, T, seg, y, w.Yp);
     LVAE_TRY(gemm_small_f64(0, 0, T, M, T, 1.0, w.iB, T, P * TT, TT, w.X, M, NM, (int64_t)T * M, 0.0, w.iBK, M, NM,
                             (int64_t)T * M, L, P, st));
     LVAE_TRY(gemm_small_f64(1, 0, M, M, N, 1.0, w.X, M, NM, 0, w.iBK, M, NM, 0, 0.0, w.Q, M, MM, 0, L, 1, st));
@@ -382,16 +309,25 @@ int lvae_gp_elbo_fwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* 
   // Wm = iW Pm
   LVAE_TRY(bound_w_inverse(L, M, w.Kz, w.Q, w.W, w.iW0, w.E, w.iW, w.ldW, w.info + L + L * P, st));
   LVAE_TRY(gemm_small_f64(0, 0, M, kGeS, M, 1.0, w.iW, M, MM, 0, w.Pm, kGeS, MS, 0, 0.0, w.Wm, kGeS, MS, 0, L, 1, st));
-  gp_elbo_final_kernel<<<L, 256, 0, st>>>(M, L, S, (double)N, w.Q, w.iK, w.Pm, w.Wm, w.scal, w.ldK, w.ldW, elbo);
+  gp_elbo_final_kernel<<<L, 256, 0, st>>>(M, L, S, (double)N, P, T, seg, w.Q, w.iK, w.Pm, w.Wm, w.scal, w.ldK, w.ldW, elbo);
   if (info) bound_info(L, P, w.info, info, st);
   LVAE_CHECK_LAUNCH();
   return 0;
 }
 
-int lvae_gp_elbo_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, const lvae_gp_elbo_dims* dp,
+int lvae_gp_elbo_fwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, const lvae_gp_elbo_dims* dp,
                          const double* x, const double* z, const double* y, const double* params0,
-                         const double* params1, const double* noise, const double* gelbo, double* dy,
-                         double* dparams0, double* dparams1, double* dnoise, void* workspace, void* stream) {
+                         const double* params1, const double* noise, double* elbo, int32_t* info, void* workspace,
+                         void* stream) {
+  return lvae_gp_elbo_fwd_seg_f64(spec0, spec1, dp, nullptr, x, z, y, params0, params1, noise, elbo, info, workspace,
+                                  stream);
+}
+
+int lvae_gp_elbo_bwd_seg_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1,
+                             const lvae_gp_elbo_dims* dp, const int32_t* seg, const double* x, const double* z,
+                             const double* y, const double* params0, const double* params1, const double* noise,
+                             const double* gelbo, double* dy, double* dparams0, double* dparams1, double* dnoise,
+                             void* workspace, void* stream) {
   (void)y;
   (void)noise;
   LVAE_TRY(ge_check(spec0, spec1, dp));
@@ -407,7 +343,7 @@ int lvae_gp_elbo_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* 
   LVAE_TRY(gemm_small_f64(0, 0, N, M, M, 1.0, w.iBK, M, NM, 0, w.iK, M, MM, 0, 0.0, w.Z, M, NM, 0, L, 1, st));
   LVAE_TRY(gemm_small_f64(0, 0, N, kGeS, M, 1.0, w.U, M, NM, 0, w.Pm, kGeS, MS, 0, 0.0, w.A, kGeS, NS, 0, L, 1, st));
   gp_elbo_g_kernel<<<blocks((int64_t)L * MS), 256, 0, st>>>(L, M, S, gelbo, w.Wm, w.WG, w.Gs);
-  gp_elbo_a_kernel<<<blocks((int64_t)L * NS), 256, 0, st>>>(N, L, S, gelbo, w.s, w.A, w.AG, dy);
+  gp_elbo_a_kernel<<<blocks((int64_t)L * NS), 256, 0, st>>>(N, L, S, T, seg, gelbo, w.s, w.A, w.AG, dy);
   // dX = (A Gam) Wm^T - G (U - Z)   (one [N,16] x [16,M] product for all samples)
   LVAE_TRY(gemm_small_f64(0, 1, N, M, kGeS, 1.0, w.AG, kGeS, NS, 0, w.Wm, kGeS, MS, 0, 0.0, w.dX, M, NM, 0, L, 1, st));
   gp_elbo_dx_kernel<<<blocks((int64_t)L * NM), 256, 0, st>>>(NM, L, w.Gs, w.U, w.Z, w.dX);
@@ -424,7 +360,7 @@ int lvae_gp_elbo_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* 
   LVAE_TRY(gemm_small_f64(0, 1, T, T, M, 1.0, w.Z, M, NM, TM, w.iBK, M, NM, TM, 0.0, w.GB, T, P * TT, TT, L, P, st));
   LVAE_TRY(gemm_small_f64(0, 1, T, T, kGeS, 1.0, w.AG, kGeS, NS, TS, w.A, kGeS, NS, TS, 0.0, w.AAt, T, P * TT, TT, L,
                           P, st));
-  gp_elbo_gb_kernel<<<blocks(LTT), 256, 0, st>>>(P * TT, L, w.Gs, w.iB, w.iBK0iB, w.AAt, w.GB, w.GK0);
+  gp_elbo_gb_kernel<<<blocks(LTT), 256, 0, st>>>(P * TT, L, P, T, seg, w.Gs, w.iB, w.iBK0iB, w.AAt, w.GB, w.GK0);
   // hyper-parameter gradients through the four Grams
   LVAE_TRY(bound_grams_bwd(spec0, spec1, ge_dims(dp), x, z, params0, params1, w.dX, w.dKz, w.GK0, w.GB, dparams0,
                            dparams1, dnoise, w.gpart, st));
@@ -432,7 +368,16 @@ int lvae_gp_elbo_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* 
   return 0;
 }
 
-// dz from the dX / dKz lvae_gp_elbo_bwd_f64 left in the workspace (gelbo[s][l] is already inside them)
+int lvae_gp_elbo_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, const lvae_gp_elbo_dims* dp,
+                         const double* x, const double* z, const double* y, const double* params0,
+                         const double* params1, const double* noise, const double* gelbo, double* dy,
+                         double* dparams0, double* dparams1, double* dnoise, void* workspace, void* stream) {
+  return lvae_gp_elbo_bwd_seg_f64(spec0, spec1, dp, nullptr, x, z, y, params0, params1, noise, gelbo, dy, dparams0,
+                                  dparams1, dnoise, workspace, stream);
+}
+
+// dz from the dX / dKz lvae_gp_elbo_bwd_f64 left in the workspace (gelbo[s][l] is already inside them).  After a
+// lvae_gp_elbo_bwd_seg_f64 nothing changes: the padding rows of dX are exact zeros.
 int lvae_gp_elbo_bwd_z_f64(const lvae_kernel_spec* spec0, const lvae_gp_elbo_dims* dp, const double* x,
                            const double* z, const double* params0, double* dz, void* workspace, void* zworkspace,
                            void* stream) {

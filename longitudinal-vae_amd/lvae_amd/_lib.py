@@ -147,6 +147,15 @@ SIGNATURES = {
     "lvae_gp_elbo_fwd_f64": (_I32, [_SPEC, _SPEC, _GDIMS, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "lvae_gp_elbo_bwd_f64": (_I32, [_SPEC, _SPEC, _GDIMS, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                     _VP, _VP]),
+    # the same four with seg_len (device int32 [P], or None) after the dims: subjects of varying length
+    "lvae_dubo_fwd_seg_f64": (_I32, [_SPEC, _SPEC, _DDIMS, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                     _VP]),
+    "lvae_dubo_bwd_seg_f64": (_I32, [_SPEC, _SPEC, _DDIMS, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                     _VP, _VP, _VP, _VP, _VP]),
+    "lvae_gp_elbo_fwd_seg_f64": (_I32, [_SPEC, _SPEC, _GDIMS, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                        _VP]),
+    "lvae_gp_elbo_bwd_seg_f64": (_I32, [_SPEC, _SPEC, _GDIMS, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                        _VP, _VP, _VP]),
     "lvae_relu_maxpool2_fwd_f32": (_I32, [_VP, _I64, _I32, _I32, _VP, _VP, _VP]),
     "lvae_relu_maxpool2_bwd_f32": (_I32, [_VP, _VP, _VP, _I64, _I32, _I32, _VP, _VP]),
     "lvae_relu_maxpool2_bias_workspace_size": (_SZ, [_I32, _I32]),

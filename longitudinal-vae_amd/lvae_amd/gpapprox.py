@@ -12,6 +12,10 @@ d log|A| = tr(A^-1 dA)).  The all-dims DUBO is instead one batched HIP forward a
 (lvae_dubo_fwd_f64 / lvae_dubo_bwd_f64, csrc/dubo.hip: a fused pass over the subjects), and so is the all-dims,
 all-samples ELBO ``elbo_batched`` (lvae_gp_elbo_fwd_f64 / lvae_gp_elbo_bwd_f64, csrc/gp_elbo.hip); the per-dim
 functions stay as they are, as their baseline and comparison.
+
+Subjects of varying length (an extension: the reference's two bounds reshape to [P, T]): ``subject_layout``,
+``deviance_upper_bound_varying_T`` and ``elbo_varying_T`` lay the batch out as [P, T_max] and run the same two HIP
+calls with the padding masked out (lvae_dubo_fwd_seg_f64 ... lvae_gp_elbo_bwd_seg_f64).
 """
 import math
 
@@ -143,6 +147,12 @@ def _bound_dz(name, bwd_z, spec0, dims, x64, z64, p0, ws, N, z_dtype):
     return dz.to(z_dtype)
 
 
+def _with_seg(fn, seg):
+    """A lvae_*_seg_f64 call with its seg_len argument (device int32 [P], after the dims) filled in: the argument
+    list of the uniform call"""
+    return lambda spec0, spec1, dims, *rest: fn(spec0, spec1, dims, _lib.ptr(seg), *rest)
+
+
 def _cast_back(ctx, dp0, dp1, dnz):
     """(dparams0, dparams1, dnoise) in the dtypes (and the noise's shape) the forward was given"""
     t0, t1, tn, nshape = ctx.dtypes[:4]
@@ -154,11 +164,13 @@ class _DuboFn(torch.autograd.Function):
     (lvae_dubo_bwd_f64); a z that requires grad adds lvae_dubo_bwd_z_f64 (nothing runs for one that does not)."""
 
     @staticmethod
-    def forward(ctx, params0, params1, noise, mu, logv, x, z, spec0, spec1, dims):
+    def forward(ctx, params0, params1, noise, mu, logv, x, z, spec0, spec1, dims, seg=None):
         lib = _lib.lib()
-        dubo, saved = _bound_fwd("dubo", "deviance_upper_bound", lib.lvae_dubo_fwd_f64, lib.lvae_dubo_workspace_size,
+        fwd = lib.lvae_dubo_fwd_f64 if seg is None else _with_seg(lib.lvae_dubo_fwd_seg_f64, seg)
+        dubo, saved = _bound_fwd("dubo", "deviance_upper_bound", fwd, lib.lvae_dubo_workspace_size,
                                  dims.L, spec0, spec1, dims, params0, params1, noise, x, z, (mu, logv))
         ctx.save_for_backward(*saved)
+        ctx.seg = seg
         ctx.spec0, ctx.spec1, ctx.dims = spec0, spec1, dims
         ctx.dtypes = (params0.dtype, params1.dtype, noise.dtype, noise.shape, mu.dtype, logv.dtype)
         ctx.z_dtype = z.dtype
@@ -171,17 +183,17 @@ class _DuboFn(torch.autograd.Function):
         g = _f64(gdubo).reshape(-1)
         dmu, dlv = torch.empty_like(mu64), torch.empty_like(lv64)
         dp0, dp1, dnz = torch.empty_like(p0), torch.empty_like(p1), torch.empty_like(nz)
-        rc = lib.lvae_dubo_bwd_f64(ctx.spec0, ctx.spec1, ctx.dims, _lib.ptr(x64), _lib.ptr(z64), _lib.ptr(mu64),
-                                   _lib.ptr(lv64), _lib.ptr(p0), _lib.ptr(p1), _lib.ptr(nz), _lib.ptr(g),
-                                   _lib.ptr(dmu), _lib.ptr(dlv), _lib.ptr(dp0), _lib.ptr(dp1), _lib.ptr(dnz),
-                                   _lib.ptr(ws), _lib.stream_ptr())
+        bwd = lib.lvae_dubo_bwd_f64 if ctx.seg is None else _with_seg(lib.lvae_dubo_bwd_seg_f64, ctx.seg)
+        rc = bwd(ctx.spec0, ctx.spec1, ctx.dims, _lib.ptr(x64), _lib.ptr(z64), _lib.ptr(mu64), _lib.ptr(lv64),
+                 _lib.ptr(p0), _lib.ptr(p1), _lib.ptr(nz), _lib.ptr(g), _lib.ptr(dmu), _lib.ptr(dlv), _lib.ptr(dp0),
+                 _lib.ptr(dp1), _lib.ptr(dnz), _lib.ptr(ws), _lib.stream_ptr())
         _lib.check(rc, "dubo_bwd")
         tmu, tlv = ctx.dtypes[4:]
         dz = None
         if ctx.needs_input_grad[6]:
             dz = _bound_dz("dubo", lib.lvae_dubo_bwd_z_f64, ctx.spec0, ctx.dims, x64, z64, p0, ws,
                            ctx.dims.P * ctx.dims.T, ctx.z_dtype)
-        return (*_cast_back(ctx, dp0, dp1, dnz), dmu.to(tmu), dlv.to(tlv), None, dz, None, None, None)
+        return (*_cast_back(ctx, dp0, dp1, dnz), dmu.to(tmu), dlv.to(tlv), None, dz, None, None, None, None)
 
 
 def _dubo_noise(likelihoods, L):
@@ -194,7 +206,8 @@ def _dubo_noise(likelihoods, L):
 
 def _batched_kernels(L, covar_module0, covar_module1, z, train_xt, P, T):
     """(spec0, params0 [L, P0], spec1, params1 [L, P1], z [L, M, Q]) of the all-dims calls from batched modules or
-    per-dim lists and z as [L, M, Q], [M, Q] (shared) or a per-dim list; ValueError on mismatched shapes."""
+    per-dim lists and z as [L, M, Q], [M, Q] (shared) or a per-dim list; ValueError on mismatched shapes.  P None:
+    subjects of varying length, the caller checks the rows against its layout."""
     from .elbo import _stack_modules
     spec0, params0 = _stack_modules(covar_module0)
     spec1, params1 = _stack_modules(covar_module1)
@@ -211,7 +224,7 @@ def _batched_kernels(L, covar_module0, covar_module1, z, train_xt, P, T):
     zz = z if z.dim() == 3 else z.unsqueeze(0).expand(L, -1, -1)
     if zz.shape[0] != L:
         raise ValueError(f"z has {zz.shape[0]} dims, expected {L}")
-    if train_xt.shape[0] != P * T:
+    if P is not None and train_xt.shape[0] != P * T:
         raise ValueError(f"train_xt has {train_xt.shape[0]} rows, expected P*T = {P * T}")
     return spec0, params0, spec1, params1, zz
 
@@ -230,7 +243,7 @@ def deviance_upper_bound_batched(latent_dim, covar_module0, covar_module1, likel
         raise ValueError(f"m / log_v must be [{P * T}, {L}]")
     noise = _dubo_noise(likelihoods, L).to(m.device)
     dims = _lib.DuboDims(L, int(zz.shape[-2]), int(P), int(T), int(train_xt.shape[-1]), float(eps))
-    return _DuboFn.apply(params0, params1, noise, m, log_v, train_xt, zz, spec0, spec1, dims)
+    return _DuboFn.apply(params0, params1, noise, m, log_v, train_xt, zz, spec0, spec1, dims, None)
 
 
 def validation_dubo(latent_dim, covar_module0, covar_module1, likelihood, train_xt, m, log_v, z, P, T, eps):
@@ -249,11 +262,13 @@ class _GpElboFn(torch.autograd.Function):
     one that does not)."""
 
     @staticmethod
-    def forward(ctx, params0, params1, noise, y, x, z, spec0, spec1, dims):
+    def forward(ctx, params0, params1, noise, y, x, z, spec0, spec1, dims, seg=None):
         lib = _lib.lib()
-        out, saved = _bound_fwd("gp_elbo", "elbo_batched", lib.lvae_gp_elbo_fwd_f64, lib.lvae_gp_elbo_workspace_size,
+        fwd = lib.lvae_gp_elbo_fwd_f64 if seg is None else _with_seg(lib.lvae_gp_elbo_fwd_seg_f64, seg)
+        out, saved = _bound_fwd("gp_elbo", "elbo_batched", fwd, lib.lvae_gp_elbo_workspace_size,
                                 (dims.S, dims.L), spec0, spec1, dims, params0, params1, noise, x, z, (y,))
         ctx.save_for_backward(*saved)
+        ctx.seg = seg
         ctx.spec0, ctx.spec1, ctx.dims = spec0, spec1, dims
         ctx.dtypes = (params0.dtype, params1.dtype, noise.dtype, noise.shape, y.dtype)
         ctx.z_dtype = z.dtype
@@ -266,15 +281,16 @@ class _GpElboFn(torch.autograd.Function):
         g = _f64(gelbo)
         dy = torch.empty_like(y64)
         dp0, dp1, dnz = torch.empty_like(p0), torch.empty_like(p1), torch.empty_like(nz)
-        rc = lib.lvae_gp_elbo_bwd_f64(ctx.spec0, ctx.spec1, ctx.dims, _lib.ptr(x64), _lib.ptr(z64), _lib.ptr(y64),
-                                      _lib.ptr(p0), _lib.ptr(p1), _lib.ptr(nz), _lib.ptr(g), _lib.ptr(dy),
-                                      _lib.ptr(dp0), _lib.ptr(dp1), _lib.ptr(dnz), _lib.ptr(ws), _lib.stream_ptr())
+        bwd = lib.lvae_gp_elbo_bwd_f64 if ctx.seg is None else _with_seg(lib.lvae_gp_elbo_bwd_seg_f64, ctx.seg)
+        rc = bwd(ctx.spec0, ctx.spec1, ctx.dims, _lib.ptr(x64), _lib.ptr(z64), _lib.ptr(y64), _lib.ptr(p0),
+                 _lib.ptr(p1), _lib.ptr(nz), _lib.ptr(g), _lib.ptr(dy), _lib.ptr(dp0), _lib.ptr(dp1), _lib.ptr(dnz),
+                 _lib.ptr(ws), _lib.stream_ptr())
         _lib.check(rc, "gp_elbo_bwd")
         dz = None
         if ctx.needs_input_grad[5]:
             dz = _bound_dz("gp_elbo", lib.lvae_gp_elbo_bwd_z_f64, ctx.spec0, ctx.dims, x64, z64, p0, ws,
                            ctx.dims.P * ctx.dims.T, ctx.z_dtype)
-        return (*_cast_back(ctx, dp0, dp1, dnz), dy.to(ctx.dtypes[4]), None, dz, None, None, None)
+        return (*_cast_back(ctx, dp0, dp1, dnz), dy.to(ctx.dtypes[4]), None, dz, None, None, None, None)
 
 
 ELBO_MAX_SAMPLES = 16   # samples of one lvae_gp_elbo_* call (the columns of one MFMA tile)
@@ -300,6 +316,95 @@ def elbo_batched(latent_dim, covar_module0, covar_module1, likelihoods, train_xt
     for s0 in range(0, y.shape[0], ELBO_MAX_SAMPLES):
         ys = y[s0:s0 + ELBO_MAX_SAMPLES]
         dims = _lib.GpElboDims(L, M, int(P), int(T), Q, int(ys.shape[0]), float(eps))
-        out.append(_GpElboFn.apply(params0, params1, noise, ys, train_xt, zz, spec0, spec1, dims))
+        out.append(_GpElboFn.apply(params0, params1, noise, ys, train_xt, zz, spec0, spec1, dims, None))
+    res = out[0] if len(out) == 1 else torch.cat(out, 0)
+    return res[0] if single else res
+
+
+class SubjectLayout:
+    """The [P, T_max] layout of a batch whose subjects differ in length (``subject_layout``): subject p, in
+    torch.unique order of the ids, has its ``seg_len[p]`` rows first, in the order they appear in the batch, and
+    padding after them.  ``gather`` [P * T_max] int64: the batch row of every slot (a padding slot points at its
+    subject's first row, so that padded covariates are real ones); ``valid`` [P * T_max] bool; ``seg_len`` [P]
+    int32.  All three live on the device given; ``P``, ``T_max`` and ``N`` (the rows of the batch) are ints."""
+
+    def __init__(self, gather, valid, seg_len, T_max, N):
+        self.gather, self.valid, self.seg_len = gather, valid, seg_len
+        self.P, self.T_max, self.N = int(seg_len.numel()), int(T_max), int(N)
+
+    def to(self, device):
+        return SubjectLayout(self.gather.to(device), self.valid.to(device), self.seg_len.to(device), self.T_max,
+                             self.N)
+
+
+def subject_layout(ids, device=None):
+    """``SubjectLayout`` of a batch from its id column (one host round trip over ``ids``; rows of a subject may
+    stand anywhere in the batch).  ``device``: where gather / valid / seg_len go (default: that of ``ids``)."""
+    from .elbo import _subject_layout
+    gather, valid, seg, T_max = _subject_layout(ids)
+    dev = ids.device if device is None else device
+    return SubjectLayout(gather.to(dev), valid.to(dev), seg.to(dev), T_max, ids.shape[0])
+
+
+VARYING_T_MAX = 128   # longest subject of the varying-length calls (the T limit of lvae_dubo_dims / lvae_gp_elbo_dims)
+
+
+def _varying_layout(train_xt, id_covariate, layout, n_rows, what):
+    lay = subject_layout(train_xt[:, id_covariate]) if layout is None else layout
+    if lay.N != train_xt.shape[0] or n_rows != lay.N:
+        raise ValueError(f"{what}: the layout has {lay.N} rows, train_xt {train_xt.shape[0]}, the data {n_rows}")
+    if lay.T_max > VARYING_T_MAX:
+        raise ValueError(f"{what}: a subject has {lay.T_max} rows, at most {VARYING_T_MAX} are supported")
+    if lay.gather.device != train_xt.device:
+        lay = lay.to(train_xt.device)
+    return lay
+
+
+def deviance_upper_bound_varying_T(latent_dim, covar_module0, covar_module1, likelihoods, train_xt, m, log_v, z,
+                                   id_covariate, eps, layout=None):
+    """``deviance_upper_bound_batched`` for subjects of varying length (an extension: the reference's DUBO needs P
+    subjects of T rows): [L] fp64.  The subjects are the distinct values of train_xt[:, id_covariate]; their rows
+    may stand in any order.  The batch is laid out as [P, T_max] (``subject_layout``) and runs through the same HIP
+    kernels with the padding masked out (lvae_dubo_fwd_seg_f64 / lvae_dubo_bwd_seg_f64); N of the bound is the
+    number of rows.  Modules, likelihoods and z in every form ``deviance_upper_bound_batched`` takes; gradients
+    flow to the caller's rows of m / log_v [N, L] where they stand, to the kernels, the noise and a z that requires
+    grad.  ``layout``: a ``subject_layout`` of this batch's id column, to skip the host round trip over it.
+    ValueError when a subject has more than 128 rows."""
+    L = int(latent_dim)
+    spec0, params0, spec1, params1, zz = _batched_kernels(L, covar_module0, covar_module1, z, train_xt, None, None)
+    N = train_xt.shape[0]
+    if tuple(m.shape) != (N, L) or tuple(log_v.shape) != (N, L):
+        raise ValueError(f"m / log_v must be [{N}, {L}]")
+    lay = _varying_layout(train_xt, id_covariate, layout, N, "deviance_upper_bound_varying_T")
+    noise = _dubo_noise(likelihoods, L).to(m.device)
+    dims = _lib.DuboDims(L, int(zz.shape[-2]), lay.P, lay.T_max, int(train_xt.shape[-1]), float(eps))
+    # (the padding slots repeat a row of m / log_v that the kernels never read; their cotangent is an exact 0)
+    return _DuboFn.apply(params0, params1, noise, m.index_select(0, lay.gather), log_v.index_select(0, lay.gather),
+                         train_xt.detach().index_select(0, lay.gather), zz, spec0, spec1, dims, lay.seg_len)
+
+
+def elbo_varying_T(latent_dim, covar_module0, covar_module1, likelihoods, train_xt, train_yt, z, id_covariate, eps,
+                   layout=None):
+    """``elbo_batched`` for subjects of varying length (an extension, as ``deviance_upper_bound_varying_T``):
+    train_yt [N, L] -> [L], or [S, N, L] -> [S, L], one batched HIP forward and one adjoint per group of at most 16
+    samples (lvae_gp_elbo_fwd_seg_f64 / lvae_gp_elbo_bwd_seg_f64).  Gradients flow to the caller's rows of train_yt
+    where they stand, to the kernels, the noise and a z that requires grad."""
+    L = int(latent_dim)
+    spec0, params0, spec1, params1, zz = _batched_kernels(L, covar_module0, covar_module1, z, train_xt, None, None)
+    N = train_xt.shape[0]
+    single = train_yt.dim() == 2
+    y = train_yt.unsqueeze(0) if single else train_yt
+    if y.dim() != 3 or y.shape[0] < 1 or tuple(y.shape[1:]) != (N, L):
+        raise ValueError(f"train_yt must be [{N}, {L}] or [S, {N}, {L}], got {tuple(train_yt.shape)}")
+    lay = _varying_layout(train_xt, id_covariate, layout, N, "elbo_varying_T")
+    noise = _dubo_noise(likelihoods, L).to(y.device)
+    M, Q = int(zz.shape[-2]), int(train_xt.shape[-1])
+    x_pad = train_xt.detach().index_select(0, lay.gather)
+    y_pad = y.index_select(1, lay.gather)
+    out = []
+    for s0 in range(0, y.shape[0], ELBO_MAX_SAMPLES):
+        ys = y_pad[s0:s0 + ELBO_MAX_SAMPLES]
+        dims = _lib.GpElboDims(L, M, lay.P, lay.T_max, Q, int(ys.shape[0]), float(eps))
+        out.append(_GpElboFn.apply(params0, params1, noise, ys, x_pad, zz, spec0, spec1, dims, lay.seg_len))
     res = out[0] if len(out) == 1 else torch.cat(out, 0)
     return res[0] if single else res

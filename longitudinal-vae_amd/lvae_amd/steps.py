@@ -15,6 +15,7 @@ updates) so that a data-parallel all-reduce can sit between two captured graphs.
 """
 import contextlib
 import os
+import weakref
 
 import torch
 
@@ -278,32 +279,60 @@ class HensmanStep:
         return out
 
 
+class _VaryingLayout:
+    """The subject layout of the full-batch steps' varying-length path (T=None): built from X's id column on the
+    first call and kept while the same X tensor comes back unchanged (same object, same ``_version``) -- full-batch
+    training passes one X every epoch, and the layout costs a host round trip over the ids."""
+
+    def __init__(self, T, id_covariate, who):
+        if T is None and id_covariate is None:
+            raise ValueError(f"{who}: T=None (subjects of varying length) needs id_covariate")
+        self.id_covariate = id_covariate
+        self.builds = 0
+        self._key, self._layout = None, None
+
+    def __call__(self, X):
+        from .gpapprox import subject_layout
+        if self._key is None or self._key[0]() is not X or self._key[1] != X._version:
+            self._layout = subject_layout(X[:, self.id_covariate])
+            self._key = (weakref.ref(X), X._version)
+            self.builds += 1
+        return self._layout
+
+
 class DuboStep:
     """standard_training's type_KL='GPapprox_closed' branch (training.py:499-575): encode, sample, decode and
     loss, the DUBO of every latent dim from (mu, log_var) in one batched call, recon + weight * sum_l dubo_l / L
     ('mse') or nll + sum_l dubo_l ('nll'), backward; ``apply`` is the optimiser step and the scale constraint.
 
     k0 / k1 / likelihood: batched modules or per-dim lists; z: [L, M, Q], [M, Q] or a per-dim list; X: the full
-    batch's covariates [P*T, Q], subjects in blocks of T rows.  A z that is an nn.Parameter (or a list of them)
+    batch's covariates [P*T, Q], subjects in blocks of T rows.  T=None with id_covariate: subjects of varying
+    length, told apart by X[:, id_covariate], rows in any order (gpapprox.deviance_upper_bound_varying_T; the layout
+    is kept while the same X comes back).  A z that is an nn.Parameter (or a list of them)
     registered with the optimiser is trained like every other parameter (learnable inducing points).  One stream,
     eager; capture into a HIP graph is untested."""
 
     def __init__(self, vae, k0, k1, likelihood, optimiser, z, T, weight=0.15, loss_function="mse", eps=1e-6,
-                 constrain_scales=True, grad_hook=None):
+                 constrain_scales=True, grad_hook=None, id_covariate=None):
         self.vae, self.k0, self.k1, self.lik, self.opt = vae, k0, k1, likelihood, optimiser
         self.z, self.T = z, T
+        self.layout = _VaryingLayout(T, id_covariate, "DuboStep") if T is None else None
         self.weight, self.loss_function, self.eps = weight, loss_function, eps
         self.constrain_scales, self.grad_hook = constrain_scales, grad_hook
 
     def forward_backward(self, img, mask, X, eps=None):
-        from .gpapprox import deviance_upper_bound_batched
+        from .gpapprox import deviance_upper_bound_batched, deviance_upper_bound_varying_T
         self.opt.zero_grad(set_to_none=True)
         recon, mu, log_var = self.vae(img, eps)
         mse, nll = self.vae.loss_function(recon, img, mask)
         recon_loss, nll_loss = mse.sum(), nll.sum()
         L = mu.shape[1]
-        dubo = deviance_upper_bound_batched(L, self.k0, self.k1, self.lik, X, mu, log_var, self.z,
-                                            X.shape[0] // self.T, self.T, self.eps)
+        if self.T is None:
+            dubo = deviance_upper_bound_varying_T(L, self.k0, self.k1, self.lik, X, mu, log_var, self.z,
+                                                  self.layout.id_covariate, self.eps, layout=self.layout(X))
+        else:
+            dubo = deviance_upper_bound_batched(L, self.k0, self.k1, self.lik, X, mu, log_var, self.z,
+                                                X.shape[0] // self.T, self.T, self.eps)
         if self.loss_function == "mse":
             gp = dubo.sum() / L
             net = recon_loss + self.weight * gp
@@ -339,20 +368,22 @@ class ElboStep:
 
     k0 / k1 / likelihood: batched modules or per-dim lists; z: [L, M, Q], [M, Q] or a per-dim list; X: the full
     batch's covariates [P*T, Q], subjects in blocks of T rows; eps [N, L]: the decoder's draw, eps_gp
-    [num_samples, N, L]: the GP term's draws (each drawn if None).  A z that is an nn.Parameter (or a list of them)
+    [num_samples, N, L]: the GP term's draws (each drawn if None).  T=None with id_covariate: subjects of varying
+    length, as DuboStep's (gpapprox.elbo_varying_T).  A z that is an nn.Parameter (or a list of them)
     registered with the optimiser is trained like every other parameter.  One stream, eager; capture into a HIP
     graph is untested."""
 
     def __init__(self, vae, k0, k1, likelihood, optimiser, z, T, weight=0.15, loss_function="mse", eps=1e-6,
-                 constrain_scales=True, grad_hook=None, num_samples=1):
+                 constrain_scales=True, grad_hook=None, num_samples=1, id_covariate=None):
         self.vae, self.k0, self.k1, self.lik, self.opt = vae, k0, k1, likelihood, optimiser
         self.z, self.T = z, T
+        self.layout = _VaryingLayout(T, id_covariate, "ElboStep") if T is None else None
         self.weight, self.loss_function, self.eps = weight, loss_function, eps
         self.constrain_scales, self.grad_hook = constrain_scales, grad_hook
         self.num_samples = int(num_samples)
 
     def forward_backward(self, img, mask, X, eps=None, eps_gp=None):
-        from .gpapprox import elbo_batched
+        from .gpapprox import elbo_batched, elbo_varying_T
         self.opt.zero_grad(set_to_none=True)
         recon, mu, log_var = self.vae(img, eps)
         mse, nll = self.vae.loss_function(recon, img, mask)
@@ -363,7 +394,11 @@ class ElboStep:
         if tuple(eps_gp.shape) != (S,) + tuple(mu.shape):
             raise ValueError(f"eps_gp must be [{S}, {mu.shape[0]}, {L}], got {tuple(eps_gp.shape)}")
         Z = torch.stack([self.vae.sample_latent(mu, log_var, eps_gp[s]) for s in range(S)])
-        el = elbo_batched(L, self.k0, self.k1, self.lik, X, Z, self.z, X.shape[0] // self.T, self.T, self.eps)
+        if self.T is None:
+            el = elbo_varying_T(L, self.k0, self.k1, self.lik, X, Z, self.z, self.layout.id_covariate, self.eps,
+                                layout=self.layout(X))
+        else:
+            el = elbo_batched(L, self.k0, self.k1, self.lik, X, Z, self.z, X.shape[0] // self.T, self.T, self.eps)
         if self.loss_function == "mse":
             gp = -el.sum() / (S * L)
             net = recon_loss + self.weight * gp
