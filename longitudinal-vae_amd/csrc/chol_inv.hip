@@ -44,56 +44,27 @@
 #include "side_stream.hpp"
 #include "x3_c16.hpp"
 
-#ifndef LVAE_CI_C16
-#define LVAE_CI_C16 1
-#endif
-// the pivot's pending update (dev A/B switches): skip the zero half of Y_kk in X = C Y_kk^T, and load X's
-// planes once for X X^T
-#ifndef LVAE_PV_BTRI
-#define LVAE_PV_BTRI 1
-#endif
-#ifndef LVAE_PV_SAMEAB
-#define LVAE_PV_SAMEAB 1
-#endif
-#ifndef LVAE_CI_KREV
-#define LVAE_CI_KREV 1
-#endif
-
 namespace lvae {
 
-// the trtri / lauum planes (Y, Y^T, X^T) in the chunk-major layout and their GEMMs on the c16 core
-// (x3_c16.hpp: a 4-stage ring, 128 KB of LDS beside the epilogues' own); 0: row-major planes on x3_dma.hpp
-constexpr bool kCiC16 = LVAE_CI_C16 != 0;
+// The trtri / lauum planes (Y, Y^T, X^T) are in the chunk-major layout and their GEMMs run on the c16 core
+// (x3_c16.hpp: a 4-stage ring, 128 KB of LDS beside the epilogues' own).
 
-// Few latent dims per call (a sharded rank: L <= kCiPipeMaxL): trtri runs PIPELINED with potrf, by block
-// rows, on the caller's stream between the passes (the GPU is mostly idle beside the pivot chain there):
+// Few latent dims per call (a sharded rank: L <= kCiPipeMaxL): trtri and lauum run PIPELINED with potrf, by
+// block rows, on the caller's stream between the passes (the GPU is mostly idle beside the pivot chain there):
 // once pivot(m) has Y_mm and panel(m) column m of L,
 //   rowY(m)   Y_mj = -Y_mm X_mj for j < m (+ the diagonal Y^T tile from D)   X_mj = sum_{k=j}^{m-1} L_mk Y_kj
 //   Xupd(m)   X_ij += L_im Y_mj for i > m, j <= m (fp32 in the Kinv buffer; row m+1, complete now, as the
 //             split X^T planes rowY(m+1) reads)
-// so that after the last pivot only rowY(nt-1) is left of trtri (recursive doubling: 2 log2(nt) launches
-// of under-filled tiles after potrf).  Same flops; the Y planes (row-major Y, read only by the doubling's
-// Y step) are not produced.
-#ifndef LVAE_CI_PIPE_MAX_L
-#define LVAE_CI_PIPE_MAX_L 2  // (scripts/inv_ab.py: L = 2 2.18 vs 2.60 ms for the inverse; L = 4 2.84 either way)
-#endif
-// the latent-dim bound of the pipelined schedule: LVAE_CI_PIPE_L overrides it for A/B runs (read once per
-// process, so the workspace size query and the calls agree)
-inline int ci_pipe_max_l() {
-  static const int v = getenv("LVAE_CI_PIPE_L") ? atoi(getenv("LVAE_CI_PIPE_L")) : LVAE_CI_PIPE_MAX_L;
-  return v;
-}
-inline bool ci_pipe_alloc(int np_, int L) { return L <= ci_pipe_max_l() && L <= 16 && np_ >= 512; }  // (16: kCiFuseMaxL)
-// 0: recursive-doubling trtri after potrf; 1: pipelined trtri; 2: pipelined trtri + lauum (K^-1 accumulated
-// as the rows of Y arrive: Lupd(m), K^-1_IJ += Y_mI^T Y_mJ for J <= I <= m, fp32 in the Kinv buffer, whose
-// tiles of rows <= m the pipelined X no longer uses; the reduce's lauum is then its epilogue alone).
-// LVAE_CI_PIPE=0 / LVAE_CI_PIPE_LAUUM=0 switch the stages off (A/B runs; read once per process).
-inline int ci_pipe_mode(int np_, int L) {
-  static const bool on = !getenv("LVAE_CI_PIPE") || atoi(getenv("LVAE_CI_PIPE")) != 0;
-  static const bool lau = !getenv("LVAE_CI_PIPE_LAUUM") || atoi(getenv("LVAE_CI_PIPE_LAUUM")) != 0;
-  if (!on || !ci_pipe_alloc(np_, L)) return 0;
-  return lau ? 2 : 1;
-}
+//   Lupd(m)   K^-1_IJ += Y_mI^T Y_mJ for J <= I <= m (fp32 in the Kinv buffer, whose tiles of rows <= m the
+//             pipelined X no longer uses), in Xupd(m)'s launch: K^-1 accumulated as the rows of Y arrive
+// so that after the last pivot only rowY(nt-1) and Lupd(nt-1) are left (recursive doubling: 2 log2(nt) launches
+// of under-filled tiles after potrf) and the reduce's lauum is its epilogue alone.  Same flops; the Y planes
+// (row-major Y, read only by the doubling's Y step) are not produced.
+// (The inverse alone at np = 4096: L = 2 2.18 vs 2.60 ms; L = 4 2.84 either way.)
+constexpr int kCiPipeMaxL = 2;
+// The ONE decision for the pipelined schedule: the scratch layout (the XR planes), the factor's schedule, the
+// lauum's `pre` flag and the exact KL's early-reduce gate (kl_closed.hip) all ask here.
+bool ci_pipe_mode(int np_, int L) { return L <= kCiPipeMaxL && np_ >= 512; }  // (implies schedule (a))
 
 struct CiScratch {
   _Float16 *Ch[2], *Cl[2];  // [L][np][256] planes of the updated column (pass k's C operand), by parity
@@ -105,7 +76,7 @@ struct CiScratch {
   float* ysc;               // [L][nt][nt] (l, i, j): tile (i, j) of Y (both plane orientations; D for i == j)
   float* xsc;               // [L][nt][nt] (l, i, j): tile (i, j) of the trtri intermediate X
   _Float16 *XRh[2], *XRl[2];  // pipelined trtri: the X^T tiles (j, m) of row block m, [L][nt][256 x 256] (one
-                              // chunk-major tile each), by row parity; nullptr unless ci_pipe_alloc
+                              // chunk-major tile each), by row parity; nullptr unless ci_pipe_mode
   float* lout = nullptr;      // potrf-only export (ci_potrf_f32): the pivots write L_kk, the panels L_ik, in fp32
                               // into the lower tiles of this [L][np][np] matrix (not part of `bytes`)
   int* cnt;                   // [L][nt] split pivots: arrival tickets per (dim, pass), zeroed per call (own block)
@@ -137,8 +108,8 @@ struct CiScratch {
     ysc = (float*)take((size_t)L * nt * nt * 4);
     xsc = (float*)take((size_t)L * nt * nt * 4);
     for (int b = 0; b < 2; ++b) {
-      XRh[b] = ci_pipe_alloc(np_, L) ? (_Float16*)take(col * 2) : nullptr;
-      XRl[b] = ci_pipe_alloc(np_, L) ? (_Float16*)take(col * 2) : nullptr;
+      XRh[b] = ci_pipe_mode(np_, L) ? (_Float16*)take(col * 2) : nullptr;
+      XRl[b] = ci_pipe_mode(np_, L) ? (_Float16*)take(col * 2) : nullptr;
     }
     cnt = (int*)take(cnt_bytes(L, nt));
     xs = (float*)take((size_t)L * 8 * 4);
@@ -151,86 +122,13 @@ struct CiScratch {
 
 // ------------------------------------------------------------------------------------------
 // pivot(kb): A_kk (lower triangle) -> L_kk in LDS -> Y_kk = L_kk^-1; out: Y_kk planes (D, row-major)
-// with the split scale of max |Y_kk|, log|A_kk|, info.  One 1024-thread
-// workgroup per dim.  With `pending` (schedule (a), kb > 0) the block still lacks pass kb-1's update,
-// applied here: X = L_{kb,kb-1} = C_kb Y_{kb-1}^T (C planes of pass kb-1, block kb; D of kb-1), split
-// at its exact max into Xh / Xl, then A_kk - X X^T.
+// with the split scale of max |Y_kk|, log|A_kk|, info.  One 1024-thread workgroup per dim does the
+// factorisation.  In schedule (a), for kb > 0, the block still lacks pass kb-1's update (the PENDING pivot):
+// it is applied here, A_kk - X X^T with X = L_{kb,kb-1} = C_kb Y_{kb-1}^T (C planes of pass kb-1, block kb;
+// D of kb-1) -- the split pivot below.
+// (r4: the pending update by the dim's one workgroup took 40 us against 25 us split four ways, the inverse
+// alone 5.67 vs 5.42 ms at L = 16; that form was removed, commit 40b45d9 is the last that contains it.)
 // ------------------------------------------------------------------------------------------
-__device__ inline void ci_pending_update(const float* __restrict__ T, int64_t np_, const CiScratch& S, int l, int kb,
-                                         float* __restrict__ lf, uint32_t* red) {
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, rl = lane & 31, hh = lane >> 5;
-  const int kp = kb - 1;
-  const int64_t oc = (int64_t)l * np_ * kSwB + (int64_t)kb * kSwBB, od = ((int64_t)l * S.nt + kp) * kSwBB;
-  const int64_t ox = (int64_t)l * kSwBB;
-  float sxo;
-  {
-    const _Float16* src[4] = {S.Ch[kp & 1] + oc, S.Cl[kp & 1] + oc, S.Dh + od, S.Dl + od};
-    int bi[4], bj[4];
-#pragma unroll
-    for (int h = 0; h < 4; ++h) bi[h] = (4 * w + h) >> 3, bj[h] = (4 * w + h) & 7;
-    pv_f32x16 x[4];
-#pragma unroll
-    for (int h = 0; h < 4; ++h) x[h] = pv_f32x16{};
-    pv_x3_gemm<4, false, false, LVAE_PV_BTRI != 0>(src, lf, bi, bj, x);  // (D = Y_kk: lower triangular)
-    const float inv = 1.0f / (S.c_scale(l, kp, kb) * S.ysc[((int64_t)l * S.nt + kp) * S.nt + kp]);
-    float m = 0.f;
-#pragma unroll
-    for (int h = 0; h < 4; ++h)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        x[h][e] *= inv;
-        m = fmaxf(m, fabsf(x[h][e]));
-      }
-    const float sx = x3_scale(sw_block_max(m, red));
-    _Float16* xh = S.Xh + ox;
-    _Float16* xl = S.Xl + ox;
-#pragma unroll
-    for (int h = 0; h < 4; ++h)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int r = 32 * bi[h] + pv_row(e, hh), c = 32 * bj[h] + rl;
-        const float y = x[h][e] * sx;
-        const _Float16 yh = (_Float16)y;
-        xh[r * kSwB + c] = yh;
-        xl[r * kSwB + c] = (_Float16)(y - (float)yh);
-      }
-    sxo = sx;
-    __syncthreads();  // the X planes are visible to the workgroup
-  }
-  const float sx = sxo;
-  const _Float16* src[4] = {S.Xh + ox, S.Xl + ox, S.Xh + ox, S.Xl + ox};
-  int bi[3], bj[3];
-#pragma unroll
-  for (int h = 0; h < 3; ++h) {
-    const int n = kLauum[w][h];
-    if (n < 0) {
-      bi[h] = bj[h] = -1;
-    } else {
-      pv_ij(n, bi[h], bj[h]);
-    }
-  }
-  pv_f32x16 acc[3];
-#pragma unroll
-  for (int h = 0; h < 3; ++h) acc[h] = pv_f32x16{};
-  pv_x3_gemm<3, true, LVAE_PV_SAMEAB != 0>(src, lf, bi, bj, acc);  // (X X^T: X's planes loaded once)
-  const float inv = 1.0f / (sx * sx);
-  float old[3][16];
-#pragma unroll
-  for (int h = 0; h < 3; ++h) {
-    if (bi[h] < 0) continue;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) old[h][e] = T[(int64_t)(32 * bi[h] + pv_row(e, hh)) * np_ + 32 * bj[h] + rl];
-  }
-  __syncthreads();  // every wave's last staging read
-#pragma unroll
-  for (int h = 0; h < 3; ++h) {
-    const int n = kLauum[w][h];
-    if (n < 0) continue;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) lf[n * kPvBlk + pv_row(e, hh) * kPvL + rl] = old[h][e] - acc[h][e] * inv;
-  }
-}
-
 // ------------------------------------------------------------------------------------------
 // Split pivot (kCiPvG workgroups per dim, schedule (a)): the pending update's X = C_kb Y_kp^T is computed
 // by the dim's kCiPvG workgroups in row slabs of 256 / kCiPvG rows, each split at its own exact max into
@@ -339,7 +237,7 @@ __device__ inline void ci_pending_reduce(const float* __restrict__ T, int64_t np
   pv_f32x16 acc[3];
 #pragma unroll
   for (int h = 0; h < 3; ++h) acc[h] = pv_f32x16{};
-  pv_x3_gemm<3, true, LVAE_PV_SAMEAB != 0>(src, lf, bi, bj, acc);
+  pv_x3_gemm<3, true, true>(src, lf, bi, bj, acc);  // (X X^T: X's planes loaded once)
   float old[3][16];
 #pragma unroll
   for (int h = 0; h < 3; ++h) {
@@ -373,12 +271,13 @@ static unsigned long long* g_pivot_prof = nullptr;
       prof[((int64_t)(1 + (i) / 8) * L + l) * 8 + (i) % 8] = __builtin_amdgcn_s_memrealtime();        \
   } while (0)
 
-// G == 1: one workgroup per dim (blockIdx = dim); G == kCiPvG (pending only): the split pivot, workgroup b
-// of dim b % Lr, slab b / Lr (Lr = gridDim.x / G, a multiple of 8; dims >= L exit)
+// G == 1: one workgroup per dim (blockIdx = dim) loads its block, which is up to date (pivot 0, schedule (b));
+// G == kCiPvG: the pending, split pivot, workgroup b of dim b % Lr, slab b / Lr (Lr = gridDim.x / G, a multiple
+// of 8; dims >= L exit)
 template <int G>
 __global__ __launch_bounds__(1024) void ci_pivot_kernel(const float* __restrict__ Aall, int np_, int kb, CiScratch S,
                                                         double* __restrict__ logdet, int32_t* __restrict__ info,
-                                                        int pending, int L, unsigned long long* __restrict__ prof) {
+                                                        int L, unsigned long long* __restrict__ prof) {
   __shared__ float lf[kPvBlocks * kPvBlk];
   __shared__ uint32_t ymax_s, xmax_s, dmax_s;
   __shared__ float bsc[kPvBlocks];
@@ -417,9 +316,6 @@ __global__ __launch_bounds__(1024) void ci_pivot_kernel(const float* __restrict_
     }
     __syncthreads();
     ci_pending_reduce(T, np_, S, l, lf);
-  } else if (pending) {
-    __syncthreads();  // xmax_s
-    ci_pending_update(T, np_, S, l, kb, lf, &xmax_s);
   } else {
     const int r = tid >> 5, c = tid & 31;
     float v[kPvBlocks];
@@ -660,30 +556,6 @@ __device__ inline void ci_planes_out(const sx_f32x16 (&acc)[4][2], float mul, fl
       }
 }
 
-// as ci_planes_out through buffer stores (offsets from compile-time parts: fewer address registers beside the
-// c16 core's fragment sets)
-__device__ inline void ci_planes_out_buf(const sx_f32x16 (&acc)[4][2], float mul, float s, _Float16* __restrict__ hi,
-                                         _Float16* __restrict__ lo, int ld) {
-  const __amdgpu_buffer_rsrc_t rh = __builtin_amdgcn_make_buffer_rsrc(hi, (short)0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc(lo, (short)0, 0x7fffffff, 0x00020000);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int vb = (((w >> 2) * 128 + 4 * (lane >> 5)) * ld + (w & 3) * 64 + (lane & 31)) * 2;
-  const float m = mul * s;
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const float y = acc[a][b][e] * m;
-        const _Float16 yh = (_Float16)y;
-        const _Float16 yl = (_Float16)(y - (float)yh);
-        const int so = ((32 * a + (e & 3) + 8 * (e >> 2)) * ld + 32 * b) * 2;
-        __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, yh), rh, vb, so, 0);
-        __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, yl), rl, vb, so, 0);
-      }
-}
-
 __device__ inline float ci_acc_absmax(const sx_f32x16 (&acc)[4][2]) {
   float m = 0.f;
 #pragma unroll
@@ -699,11 +571,10 @@ __device__ inline float ci_acc_absmax(const sx_f32x16 (&acc)[4][2]) {
 // pass-0 C operand: blocks i >= 1 of column 0 of A, each with the split scale of its exact max.
 // grid (nt - 1, L), 256 threads.
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void ci_prep0_kernel(const float* __restrict__ Aall, int np_, CiScratch S,
-                                                       int col = 0) {
+__global__ __launch_bounds__(256) void ci_prep0_kernel(const float* __restrict__ Aall, int np_, CiScratch S) {
   __shared__ uint32_t red;
-  const int l = blockIdx.y, i = col + 1 + blockIdx.x, t = threadIdx.x;
-  const float* T = Aall + (int64_t)l * np_ * np_ + (int64_t)i * kSwB * np_ + (int64_t)col * kSwB;
+  const int l = blockIdx.y, i = 1 + blockIdx.x, t = threadIdx.x;
+  const float* T = Aall + (int64_t)l * np_ * np_ + (int64_t)i * kSwB * np_;
   if (t == 0) red = 0u;
   float m = 0.f;
   for (int e = t; e < kSwBB / 4; e += 256) {
@@ -720,9 +591,9 @@ __global__ __launch_bounds__(256) void ci_prep0_kernel(const float* __restrict__
   for (int e = t; e < kSwBB / 4; e += 256) {
     const int r = e >> 6, c = (e & 63) * 4;
     const f32x4 v = *reinterpret_cast<const f32x4*>(T + (int64_t)r * np_ + c);
-    ci_split4(v, sc, S.Ch[col & 1] + o + r * kSwB + c, S.Cl[col & 1] + o + r * kSwB + c);
+    ci_split4(v, sc, S.Ch[0] + o + r * kSwB + c, S.Cl[0] + o + r * kSwB + c);
   }
-  if (t == 0) S.c_scale(l, col, i) = sc;
+  if (t == 0) S.c_scale(l, 0, i) = sc;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -769,9 +640,10 @@ __global__ __launch_bounds__(512) void ci_panel_kernel(CiScratch S, int np_, int
 // ------------------------------------------------------------------------------------------
 constexpr int kCiU2 = 0, kCiU1 = 1, kCiU12 = 2;  // kCiU12: U1 (without the pivot block) + U2, one launch
 constexpr int kCiFuseMaxL = 16; // latent dims per call up to which the pivot updates its own block
+static_assert(kCiPipeMaxL <= kCiFuseMaxL, "the pipelined schedule is a form of schedule (a)");
 template <int MODE>
 __global__ __launch_bounds__(512) void ci_update_kernel(float* __restrict__ Aall, CiScratch S, int np_, int k,
-                                                        int ntl, int nwg, int n1 = 0, int t0 = 0) {
+                                                        int ntl, int nwg, int n1 = 0) {
   __shared__ __attribute__((aligned(16))) _Float16 lds[2 * 4 * kSxPart];
   __shared__ uint32_t red;
   if (MODE != kCiU2 && threadIdx.x == 0) red = 0u;
@@ -789,7 +661,7 @@ __global__ __launch_bounds__(512) void ci_update_kernel(float* __restrict__ Aall
     const int xcd = orig % 8, q8 = nwg / 8, r8 = nwg % 8;
     const int wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + orig / 8;
     l = wgid / ntl;
-    const int t = t0 + wgid % ntl;  // (t0: the launch's first trailing tile, lookahead split)
+    const int t = wgid % ntl;
     if constexpr (MODE == kCiU1) {
       I = (ntl == nt - k - 1) ? k + 1 + t : k + 2 + t;  // with / without the pivot block
       J = k + 1;
@@ -869,304 +741,6 @@ __global__ __launch_bounds__(512) void ci_update_kernel(float* __restrict__ Aall
   }
 }
 
-// ------------------------------------------------------------------------------------------
-// The trailing update (U1 + U2 as ci_update_kernel<kCiU12>) with a deeper DMA pipeline (r6, opt-in LVAE_CI_URING=1:
-// measured slower, 211 vs 166 us per launch -- twice the barriers per tile and 32-B row pieces): 16-deep
-// K stages in a ring of 4 (4 x 32 KB of LDS, the same 128 KB as the 2 x 32-deep double buffer), each stage's DMA
-// issued THREE stages ahead, so that ~3 stages of MFMAs (~2.2 us) cover an HBM round trip instead of one (the
-// double-buffered form waits on most chunks' DMA: 0.26 MFMA-busy, 0.29 of HBM).  The A tile streams in 16 pieces
-// of 8 accumulator elements, each consumed three stages after its loads were issued; one counted vmcnt per stage
-// covers both (every stage issues a DMA -- past the last chunk a re-read into a dead buffer -- so the count is
-// uniform).  LDS rows of 16 halves (32 B): the two 8-half groups swapped on bit 3 of the row (the c16 planes'
-// swizzle), so a ds_read_b128 phase of 16 consecutive rows covers all 64 banks.
-// ------------------------------------------------------------------------------------------
-constexpr int kU16K = 16, kU16Part = kSwB * kU16K, kU16Ring = 4;
-
-// one stage's DMA: 4 parts x 256 rows x 32 B, one 1 KB instruction per part and wave (4 per thread)
-__device__ inline void u16_issue(const _Float16* __restrict__ ah, const _Float16* __restrict__ al,
-                                 const _Float16* __restrict__ bh, const _Float16* __restrict__ bl, int64_t ld, int k0,
-                                 _Float16* __restrict__ stage) {
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const _Float16* src[4] = {ah, al, bh, bl};
-  // wave w, instruction p: part p, rows 32 w .. 32 w + 31 (2 lanes per row); LDS image [row][16] linear per wave,
-  // the global source's 8-half group chosen so that physical group (lane & 1) holds logical group (lane & 1) ^ bit 3
-  const int row = 32 * w + (lane >> 1), g = (lane & 1) ^ ((row >> 3) & 1);
-  const int64_t go = (int64_t)row * ld + k0 + 8 * g;
-#pragma unroll
-  for (int p = 0; p < 4; ++p)
-    __builtin_amdgcn_global_load_lds((const void*)(src[p] + go), (void*)(stage + p * kU16Part + w * 512), 16, 0, 0);
-}
-
-__device__ inline sx_half8 u16_frag(const _Float16* __restrict__ part, int row, int h) {
-  return *reinterpret_cast<const sx_half8*>(part + row * kU16K + ((h ^ ((row >> 3) & 1)) << 3));
-}
-
-// one 16-deep stage: acc[a][b] += A rows x B rows (x3 products), the wave's 128 x 64 (sx_mma_stage's layout)
-__device__ inline void u16_mma_stage(const _Float16* __restrict__ cur, sx_f32x16 (&acc)[4][2]) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int wm = (w >> 2) * 128, wn = (w & 3) * 64, r32 = lane & 31, kh = lane >> 5;
-  sx_half8 bH[2], bL[2];
-#pragma unroll
-  for (int b = 0; b < 2; ++b) {
-    bH[b] = u16_frag(cur + 2 * kU16Part, wn + 32 * b + r32, kh);
-    bL[b] = u16_frag(cur + 3 * kU16Part, wn + 32 * b + r32, kh);
-  }
-#pragma unroll
-  for (int a = 0; a < 4; ++a) {
-    const sx_half8 aH = u16_frag(cur, wm + 32 * a + r32, kh);
-    const sx_half8 aL = u16_frag(cur + kU16Part, wm + 32 * a + r32, kh);
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(aL, bH[b], acc[a][b], 0, 0, 0);
-      acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(aH, bL[b], acc[a][b], 0, 0, 0);
-      acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(aH, bH[b], acc[a][b], 0, 0, 0);
-    }
-  }
-}
-
-// MODE and arguments as ci_update_kernel (kCiU12 / kCiU2 / kCiU1)
-template <int MODE>
-__global__ __launch_bounds__(512) void ci_update_ring_kernel(float* __restrict__ Aall, CiScratch S, int np_, int k,
-                                                             int ntl, int nwg, int n1 = 0) {
-  __shared__ __attribute__((aligned(16))) _Float16 lds[kU16Ring * 4 * kU16Part];
-  __shared__ uint32_t red;
-  if (MODE != kCiU2 && threadIdx.x == 0) red = 0u;
-  const int nt = np_ / kSwB;
-  const bool u1 = MODE == kCiU1 || (MODE == kCiU12 && (int)blockIdx.x < n1 * (nwg / max(ntl, 1)));
-  int l, I, J;
-  if (MODE == kCiU12 && u1) {
-    l = blockIdx.x / n1;
-    I = k + 2 + blockIdx.x % n1;
-    J = k + 1;
-  } else {
-    const int orig = MODE == kCiU12 ? blockIdx.x - n1 * (nwg / ntl) : blockIdx.x;
-    const int xcd = orig % 8, q8 = nwg / 8, r8 = nwg % 8;
-    const int wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + orig / 8;
-    l = wgid / ntl;
-    const int t = wgid % ntl;
-    if constexpr (MODE == kCiU1) {
-      I = (ntl == nt - k - 1) ? k + 1 + t : k + 2 + t;
-      J = k + 1;
-    } else {
-      sx_tri_blocked(t, nt - k - 2, I, J);
-      I += k + 2;
-      J += k + 2;
-    }
-  }
-  const int64_t np2 = (int64_t)np_ * np_;
-  float* C = Aall + l * np2 + (int64_t)I * kSwB * np_ + J * kSwB;
-  const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(C, (short)0, 0x7fffffff, 0x00020000);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int vo = (((w >> 2) * 128 + 4 * (lane >> 5)) * np_ + (w & 3) * 64 + (lane & 31)) * 4;
-  const int64_t oa = l * np2 + (int64_t)I * kSwB * np_ + k * kSwB, ob = l * np2 + (int64_t)J * kSwB * np_ + k * kSwB;
-  const float cs = S.lsc[((int64_t)l * S.nt + I) * S.nt + k] * S.lsc[((int64_t)l * S.nt + J) * S.nt + k];
-  const float ncs = -cs, ninv = -1.0f / cs;  // acc = L_I L_J^T - A (units of cs); the result is -acc / cs
-  const _Float16* ah = S.Lh + oa;
-  const _Float16* al = S.Ll + oa;
-  const _Float16* bh = S.Lh + ob;
-  const _Float16* bl = S.Ll + ob;
-  sx_f32x16 acc[4][2];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = sx_f32x16{};
-  constexpr int CAUX = 2;
-  constexpr int nk = kSwB / kU16K;  // 16 stages; 128 A elements per thread, 8 per stage
-  float cv[4][8];
-  auto a_load = [&](int s, float (&dst)[8]) {
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const int i = 8 * s + q, a = i >> 5, e = (i >> 1) & 15, b = i & 1;
-      dst[q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
-          rc, vo, ((32 * a + (e & 3) + 8 * (e >> 2)) * np_ + 32 * b) * 4, CAUX));
-    }
-  };
-  auto a_add = [&](int s, const float (&src)[8]) {
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const int i = 8 * s + q, a = i >> 5, e = (i >> 1) & 15, b = i & 1;
-      acc[a][b][e] += src[q] * ncs;
-    }
-  };
-#pragma unroll
-  for (int s = 0; s < kU16Ring - 1; ++s) u16_issue(ah, al, bh, bl, np_, s * kU16K, lds + s * 4 * kU16Part);
-#pragma unroll
-  for (int s = 0; s < nk; ++s) {
-    // issued after DMA s: DMA s+1, s+2 (4 each) and the A pieces s-3 .. s-1 (8 each) -- DMA s and A piece s-3 landed
-    if (s == 0) SX_WAIT_VM(8);
-    else if (s == 1) __builtin_amdgcn_s_waitcnt(0x4F70);  // vmcnt(16)
-    else __builtin_amdgcn_s_waitcnt(0x4F78);              // vmcnt(24)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();  // stage s in LDS for every wave; every wave's reads of stage s-1 retired
-    const int sn = s + kU16Ring - 1 < nk ? s + kU16Ring - 1 : nk - 1;  // (past the end: a re-read into a dead buffer)
-    u16_issue(ah, al, bh, bl, np_, sn * kU16K, lds + ((s + kU16Ring - 1) % kU16Ring) * 4 * kU16Part);
-    a_load(s, cv[s & 3]);
-    if (s >= 3) a_add(s - 3, cv[(s - 3) & 3]);
-    __builtin_amdgcn_s_setprio(1);
-    u16_mma_stage(lds + (s % kU16Ring) * 4 * kU16Part, acc);
-    __builtin_amdgcn_s_setprio(0);
-  }
-  SX_WAIT_VM(0);
-#pragma unroll
-  for (int j = nk - 3; j < nk; ++j) a_add(j, cv[j & 3]);
-  if (u1 && I != J) {
-    // a block of column k+1 = block I of the next pass's C operand: straight to its planes
-    const float sc = x3_scale(sw_block_max(ci_acc_absmax(acc) * fabsf(ninv), &red));
-    const int64_t on = (int64_t)l * np_ * kSwB + (int64_t)I * kSwBB;
-    ci_planes_out(acc, ninv, sc, S.Ch[(k + 1) & 1] + on, S.Cl[(k + 1) & 1] + on, kSwB);
-    if (threadIdx.x == 0) S.c_scale(l, k + 1, I) = sc;
-  } else {
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int e = 0; e < 16; ++e)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc[a][b][e] * ninv), rc, vo,
-                                                ((32 * a + (e & 3) + 8 * (e >> 2)) * np_ + 32 * b) * 4, CAUX);
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// U2 on 128 x 128 sub-tiles (r6, opt-in LVAE_CI_U128=1; measured slower in the step, see ci_factor_f32): A_IJ -=
-// L_Ik L_Jk^T for the lower tiles I >= J >= k+2,
-// each 256-tile as four 256-thread workgroups of 128 x 128 (the upper-right quarter of a diagonal tile skipped: no
-// reader needs A's strict upper part), K = 256 in 8 DMA-staged chunks of 32, double-buffered: 64 KB of LDS and
-// ~128 VGPRs per workgroup, so TWO workgroups share a CU and each one's HBM round trips and barriers hide under
-// the other's MFMAs (the 256-tile form holds a CU alone: 128 KB of LDS, 2 waves per SIMD, and stalls on every
-// chunk's DMA).  The A tile streams in 8 pieces of 8 accumulator elements inside the K loop, as in
-// ci_update_kernel.  Waves 2 x 2, 64 x 64 each = 2 x 2 blocks of v_mfma_f32_32x32x16_f16 x 3 products.
-// ------------------------------------------------------------------------------------------
-constexpr int kU8Rows = 128, kU8Part = kU8Rows * kSxBK;  // rows per operand part; halves per part and stage
-
-// one stage: 4 parts (A hi, A lo, B hi, B lo) x 8 blocks of 16 rows (1 KB each); wave w issues blocks 2w, 2w+1
-__device__ inline void u8_issue(const _Float16* __restrict__ ah, const _Float16* __restrict__ al,
-                                const _Float16* __restrict__ bh, const _Float16* __restrict__ bl, int64_t ld, int k0,
-                                _Float16* __restrict__ stage) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const _Float16* src[4] = {ah, al, bh, bl};
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    const int blk = 2 * w + q;
-    const int row = 16 * blk + (lane >> 2);
-    const int c = (lane & 3) ^ ((row >> 2) & 3);  // logical chunk stored at physical chunk lane & 3 (sx_frag's)
-    const int64_t go = (int64_t)row * ld + k0 + 8 * c;
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-      __builtin_amdgcn_global_load_lds((const void*)(src[p] + go), (void*)(stage + p * kU8Part + blk * 512), 16, 0, 0);
-  }
-}
-
-// one 32-deep stage of the wave's 64 x 64: acc[a][b] (a, b < 2) += A rows x B rows (three products each)
-__device__ inline void u8_mma_stage(const _Float16* __restrict__ cur, sx_f32x16 (&acc)[2][2]) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int wm = (w >> 1) * 64, wn = (w & 1) * 64, r32 = lane & 31, kh = lane >> 5;
-#pragma unroll
-  for (int ks = 0; ks < kSxBK / 16; ++ks) {
-    const int c = 2 * ks + kh;
-    sx_half8 bH[2], bL[2];
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      bH[b] = sx_frag(cur + 2 * kU8Part, wn + 32 * b + r32, c);
-      bL[b] = sx_frag(cur + 3 * kU8Part, wn + 32 * b + r32, c);
-    }
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-      const sx_half8 aH = sx_frag(cur, wm + 32 * a + r32, c);
-      const sx_half8 aL = sx_frag(cur + kU8Part, wm + 32 * a + r32, c);
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(aL, bH[b], acc[a][b], 0, 0, 0);
-        acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(aH, bL[b], acc[a][b], 0, 0, 0);
-        acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(aH, bH[b], acc[a][b], 0, 0, 0);
-      }
-    }
-  }
-}
-
-// grid: 4 ntl L workgroups (ntl trailing 256-tiles per dim, pass k), XCD-contiguous like ci_update_kernel
-__global__ __launch_bounds__(256, 2) void ci_update128_kernel(float* __restrict__ Aall, CiScratch S, int np_, int k,
-                                                              int ntl, int nwg, int n1 = 0) {
-  __shared__ __attribute__((aligned(16))) _Float16 lds[2 * 4 * kU8Part];
-  const int nt = np_ / kSwB;
-  const int orig = blockIdx.x, xcd = orig % 8, q8 = nwg / 8, r8 = nwg % 8;
-  const int wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + orig / 8;
-  const int per = 4 * (n1 + ntl), l = wgid / per, t = (wgid % per) >> 2, si = (wgid & 3) >> 1, sj = wgid & 1;
-  int I, J;
-  if (t < n1) {  // column k+1's tiles (without the pivot block): fp32 into A, split by ci_prep0_kernel(col k+1)
-    I = k + 2 + t;
-    J = k + 1;
-  } else {
-    sx_tri_blocked(t - n1, nt - k - 2, I, J);
-    I += k + 2;
-    J += k + 2;
-  }
-  if (I == J && si < sj) return;  // (uniform) the diagonal tile's upper-right quarter
-  const int64_t np2 = (int64_t)np_ * np_;
-  const int r0 = I * kSwB + si * kU8Rows, c0 = J * kSwB + sj * kU8Rows;
-  float* C = Aall + l * np2 + (int64_t)r0 * np_ + c0;
-  const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(C, (short)0, 0x7fffffff, 0x00020000);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  // accumulator element (a, e, b) of this lane: row (w >> 1) 64 + 32 a + (e & 3) + 8 (e >> 2) + 4 (lane >> 5),
-  // column (w & 1) 64 + 32 b + (lane & 31)
-  const int vo = (((w >> 1) * 64 + 4 * (lane >> 5)) * np_ + (w & 1) * 64 + (lane & 31)) * 4;
-  const int64_t oa = l * np2 + (int64_t)r0 * np_ + k * kSwB, ob = l * np2 + (int64_t)c0 * np_ + k * kSwB;
-  const float cs = S.lsc[((int64_t)l * S.nt + I) * S.nt + k] * S.lsc[((int64_t)l * S.nt + J) * S.nt + k];
-  const float ncs = -cs, ninv = -1.0f / cs;  // acc = L_I L_J^T - A (units of cs); the result is -acc / cs
-  const _Float16* ah = S.Lh + oa;
-  const _Float16* al = S.Ll + oa;
-  const _Float16* bh = S.Lh + ob;
-  const _Float16* bl = S.Ll + ob;
-  sx_f32x16 acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = sx_f32x16{};
-  constexpr int CAUX = 2;
-  constexpr int nk = kSwB / kSxBK;  // 8 chunks; 64 A elements per thread, 8 per chunk
-  float cv[2][8];
-  u8_issue(ah, al, bh, bl, np_, 0, lds);
-#pragma unroll
-  for (int s = 0; s < nk; ++s) {
-    if (s == 0) SX_WAIT_VM(0);
-    else __builtin_amdgcn_s_waitcnt(0x0F78);  // vmcnt(8): DMA s and A piece s - 2 landed (A piece s - 1 may fly)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (s + 1 < nk) u8_issue(ah, al, bh, bl, np_, (s + 1) * kSxBK, lds + ((s + 1) & 1) * 4 * kU8Part);
-    if (s >= 2) {
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int i = 8 * (s - 2) + q, a = i >> 5, e = (i >> 1) & 15, b = i & 1;
-        acc[a][b][e] += cv[s & 1][q] * ncs;
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const int i = 8 * s + q, a = i >> 5, e = (i >> 1) & 15, b = i & 1;
-      cv[s & 1][q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
-          rc, vo, ((32 * a + (e & 3) + 8 * (e >> 2)) * np_ + 32 * b) * 4, CAUX));
-    }
-    __builtin_amdgcn_s_setprio(1);
-    u8_mma_stage(lds + (s & 1) * 4 * kU8Part, acc);
-    __builtin_amdgcn_s_setprio(0);
-  }
-#pragma unroll
-  for (int j = nk - 2; j < nk; ++j)
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const int i = 8 * j + q, a = i >> 5, e = (i >> 1) & 15, b = i & 1;
-      acc[a][b][e] += cv[j & 1][q] * ncs;
-    }
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int e = 0; e < 16; ++e)
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc[a][b][e] * ninv), rc, vo,
-                                              ((32 * a + (e & 3) + 8 * (e >> 2)) * np_ + 32 * b) * 4, CAUX);
-}
-
 // D (the pivots' Y_kk planes) -> the diagonal tiles of the row-major Y planes (the lower tiles of the
 // Kinv plane pair) and, transposed through LDS, of the Y^T planes, for the blocks k0 .. k0 + count - 1.
 // grid (16 count, L): one 256-thread workgroup per 64 x 64 piece (a, b) of a diagonal tile,
@@ -1177,14 +751,12 @@ __global__ __launch_bounds__(256) void ci_diag_copy_kernel(CiScratch S, int np_,
   __shared__ _Float16 tp[2][64][66];
   const int k = k0 + (blockIdx.x >> 4), pa = (blockIdx.x >> 2) & 3, pb = blockIdx.x & 3, l = blockIdx.y, t = threadIdx.x;
   const int64_t od = ((int64_t)l * S.nt + k) * kSwBB + (int64_t)(64 * pa) * kSwB + 64 * pb;
-  const int64_t ot = (int64_t)l * np_ * np_ + (int64_t)k * kSwB * np_ + k * kSwB;
-  const int64_t oy = ot + (int64_t)(64 * pa) * np_ + 64 * pb, oyt = ot + (int64_t)(64 * pb) * np_ + 64 * pa;
   for (int e = t; e < 64 * 8; e += 256) {  // rows of 8-half vectors: direct copy + LDS image
     const int r = e >> 3, c = (e & 7) * 8;
     const x3_half8 h = *reinterpret_cast<const x3_half8*>(S.Dh + od + r * kSwB + c);
     const x3_half8 lo = *reinterpret_cast<const x3_half8*>(S.Dl + od + r * kSwB + c);
     // (chunk-major: an aligned 8-half run stays one 16-B run under the swizzle)
-    const int64_t oyc = kCiC16 ? c16_off(l, np_, k * kSwB + 64 * pa + r, k * kSwB + 64 * pb + c) : oy + (int64_t)r * np_ + c;
+    const int64_t oyc = c16_off(l, np_, k * kSwB + 64 * pa + r, k * kSwB + 64 * pb + c);
     *reinterpret_cast<x3_half8*>(Yh + oyc) = h;
     *reinterpret_cast<x3_half8*>(Yl + oyc) = lo;
 #pragma unroll
@@ -1202,7 +774,7 @@ __global__ __launch_bounds__(256) void ci_diag_copy_kernel(CiScratch S, int np_,
       h[q] = tp[0][r0 + q][c];
       lo[q] = tp[1][r0 + q][c];
     }
-    const int64_t o = kCiC16 ? c16_off(l, np_, k * kSwB + 64 * pb + c, k * kSwB + 64 * pa + r0) : oyt + (int64_t)c * np_ + r0;
+    const int64_t o = c16_off(l, np_, k * kSwB + 64 * pb + c, k * kSwB + 64 * pa + r0);
     *reinterpret_cast<x3_half8*>(YTh + o) = h;
     *reinterpret_cast<x3_half8*>(YTl + o) = lo;
   }
@@ -1210,9 +782,9 @@ __global__ __launch_bounds__(256) void ci_diag_copy_kernel(CiScratch S, int np_,
 
 // ------------------------------------------------------------------------------------------
 // ci_gemm_kernel<MODE>: out tile (i, j) = sum_{kb in [kb0, kb1)} A(i, kb) B(kb, j) over whole 256-blocks
-// on the x3 DMA tile machinery (x3_dma.hpp), operands from full [L, np, np] plane arrays (row stride np:
-// the K range of a row is contiguous), the accumulators rescaled at every block boundary to the new
-// block pair's split scales (powers of two: exact).
+// on the c16 core (x3_c16.hpp), operands from full [L, np, np] plane arrays (chunk-major panels: the K range
+// of a row block is contiguous; the L planes row-major), the accumulators rescaled at every block boundary to
+// the new block pair's split scales (powers of two: exact).
 //   kCiX  (trtri, step 1): X_ij = sum_{k=j}^{o+h-1} L_ik Y_kj      A = L planes (i, k),  B = Y^T planes (j, k)
 //                          -> X^T planes, tile (j, i) (transposed out), scale xsc(i, j)
 //   kCiY  (trtri, step 2): Y_ij = -sum_{k=o+h}^{i} Y_ik X_kj      A = Y planes (i, k),  B = X^T planes (j, k)
@@ -1223,27 +795,16 @@ __global__ __launch_bounds__(256) void ci_diag_copy_kernel(CiScratch S, int np_,
 // (workgroups with i >= nt exit at once); lauum the L nt (nt + 1) / 2 lower tiles.
 // ------------------------------------------------------------------------------------------
 constexpr int kCiX = 0, kCiY = 1, kCiLauum = 2, kCiLauumKL = 3;
-// pipelined trtri (ci_pipe_alloc; h = the pass m):
+// pipelined trtri + lauum (ci_pipe_mode; h = the pass m):
 //   kCiTrY  rowY(m): tile j < m: Y_mj = -Y_mm X_mj   A = D_m (row-major planes), B = the X^T row planes (j)
 //                    of parity m & 1 -> Y^T planes tile (j, m) (transposed out), scale ysc(m, j); workgroups
 //                    t >= m: the 16 64 x 64 pieces of Y^T (m, m) = D_m^T
 //   kCiTrX  Xupd(m): tile (i, j), i > m, j <= m: X_ij (+)= L_im Y_mj   A = L planes (i, m), B = Y^T planes
 //                    (j, m) -> fp32 X in g.Kinv (written at j == m, accumulated after), or for i == m + 1 (its
 //                    last term) the X^T row planes of parity (m + 1) & 1, scale xsc(m + 1, j); workgroups
-//                    t >= g.inst0 (mode 2): Lupd(m), tile (I, J), J <= I <= m: K^-1_IJ (+)= Y_mI^T Y_mJ
+//                    t >= g.inst0: Lupd(m), tile (I, J), J <= I <= m: K^-1_IJ (+)= Y_mI^T Y_mJ
 //                    (A, B = Y^T planes (I, m), (J, m); written at m == I) into g.Kinv
 constexpr int kCiTrY = 4, kCiTrX = 5;
-// potrf's panel and trailing update on the same core, for ci_pair_kernel launches of the pipelined schedule
-// (h = the pass m, dims interleaved: workgroup b of dim b % L):
-//   kCiPanel  tile i = m + 1 + t: L_im = C_i Y_mm^T   A = pass m's C planes (block i, row-major), B = D_m
-//             -> the L planes (i, m), scale lsc(i, m) (as ci_panel_kernel)
-//   kCiU12c   t < g.inst0: column m + 1's tile I = m + 2 + t, else a trailing tile I >= J >= m + 2:
-//             A_IJ - L_Im L_Jm^T (A = g.Kinv, the fp32 matrix), column tiles -> pass m + 1's C planes, scale
-//             csc(m + 1, I), trailing ones in place (as ci_update_kernel<kCiU12>, the A tile read after the K loop)
-constexpr int kCiPanel = 6, kCiU12c = 7;
-#ifndef LVAE_KL_MIRROR
-#define LVAE_KL_MIRROR 0  // 1: the KL lauum also writes the upper tiles of K^-1 (no reader needs them)
-#endif
 struct CiGemmArgs {
   const _Float16 *ah, *al, *bh, *bl;  // full plane arrays
   _Float16 *oh, *ol, *oth, *otl;      // outputs: row-major planes (kCiY), transposed planes (kCiX, kCiY)
@@ -1252,7 +813,7 @@ struct CiGemmArgs {
   int inst0;                           // trtri: first recursive-doubling instance; kCiTrX: its X tiles per dim
   // kCiLauumKL (the exact KL's reduce, kl_closed.hip): mu [L, np] fp64 and sqrt v [L, np] in; out the
   // partials of K^-1 mu, apart[l][s][p] = sum over column block s of Kinv(p, .) mu (every (s, p) once),
-  // and -- if bh -- the fp16 hi / lo planes of B = K^-1 diag(sqrt v) (row stride np) split with the
+  // and -- if bh_out -- the fp16 hi / lo planes of B = K^-1 diag(sqrt v) (chunk-major) split with the
   // dim's scale bsc[l] (ci_bscale_kernel)
   const double* mu;
   const float* sv;
@@ -1263,7 +824,8 @@ struct CiGemmArgs {
   const int* hbon = nullptr;  // kCiLauumKL: *hbon != 0 -> the binned hyper-gradient (kl_hyper.hip) runs: the full
                               // symmetric K^-1 (the mirror) instead of the S GEMM's B planes
   const int* dimflag = nullptr;  // kCiLauum: only the dims l with dimflag[l] != 0 (the others' workgroups exit)
-  int bid0 = 0;  // ci_gemm_kernel: this launch's first workgroup of the list (nwg counts the whole list)
+  int bid0 = 0;  // this launch's first workgroup of the list (nwg counts the whole list): a launch list cut into
+                 // several launches, trtri's early part (ci_trtri_level)
 };
 
 // one halving butterfly step over lane bit D (D <= 16): the lane keeps the half of its N partial sums
@@ -1361,13 +923,14 @@ __device__ inline void ci_diag_t_piece(const CiScratch& S, int np_, int l, int k
   }
 }
 
-// the body of one workgroup of ci_gemm_kernel<MODE>, as workgroup `bid` of its launch, on the caller's
-// LDS objects (ci_pair_kernel runs two modes' bodies in one launch)
+// workgroup blockIdx.x + g.bid0 of the MODE's list (above)
 template <int MODE>
-__device__ inline void ci_gemm_body(const CiGemmArgs& g, const CiScratch& S, const int bid, _Float16* __restrict__ lds,
-                                    float* __restrict__ sprod, uint32_t* __restrict__ redp, float* __restrict__ kl_mu,
-                                    float* __restrict__ kl_sv, float* __restrict__ kl_part) {
-  uint32_t& red = *redp;
+__global__ __launch_bounds__(512) void ci_gemm_kernel(CiGemmArgs g, CiScratch S) {
+  __shared__ __attribute__((aligned(16))) _Float16 lds[2 * 4 * kSxPart];
+  __shared__ float sprod[64];
+  __shared__ uint32_t red;
+  __shared__ float kl_mu[2 * kSwB], kl_sv[2 * kSwB], kl_part[6 * kSwB];  // (kCiLauumKL only)
+  const int bid = blockIdx.x + g.bid0;
   const int nt = g.nt, np_ = g.np_;
   int l, i, j, kb0, kb1;
   if constexpr (MODE == kCiLauum || MODE == kCiLauumKL) {
@@ -1380,22 +943,6 @@ __device__ inline void ci_gemm_body(const CiGemmArgs& g, const CiScratch& S, con
     sx_tri_blocked(wgid % g.per_dim, nt, i, j);
     kb0 = i;
     kb1 = nt;
-  } else if constexpr (MODE == kCiPanel || MODE == kCiU12c) {
-    const int L = g.nwg / g.per_dim, t = bid / L, m = g.h;
-    l = bid % L;
-    if constexpr (MODE == kCiPanel) {
-      i = m + 1 + t;
-      j = m;
-    } else if (t < g.inst0) {
-      i = m + 2 + t;
-      j = m + 1;
-    } else {
-      sx_tri(t - g.inst0, i, j);
-      i += m + 2;
-      j += m + 2;
-    }
-    kb0 = m;
-    kb1 = m + 1;
   } else if constexpr (MODE == kCiTrY || MODE == kCiTrX) {
     // dims interleaved (block b: dim b % L): the first L (m + 1) workgroups of Xupd are row m + 1's tiles
     const int L = g.nwg / g.per_dim, t = bid / L, m = g.h;
@@ -1451,12 +998,6 @@ __device__ inline void ci_gemm_body(const CiGemmArgs& g, const CiScratch& S, con
     } else if constexpr (MODE == kCiY) {
       sa = S.ysc[sl + (int64_t)i * nt + kb];
       sb = S.xsc[sl + (int64_t)kb * nt + j];
-    } else if constexpr (MODE == kCiPanel) {  // (kb = m)
-      sa = S.csc[((int64_t)l * nt + kb) * nt + i];
-      sb = S.ysc[sl + (int64_t)kb * nt + kb];
-    } else if constexpr (MODE == kCiU12c) {  // (kb = m)
-      sa = S.lsc[sl + (int64_t)i * nt + kb];
-      sb = S.lsc[sl + (int64_t)j * nt + kb];
     } else if constexpr (MODE == kCiTrY) {  // (kb = m = i)
       sa = S.ysc[sl + (int64_t)i * nt + i];
       sb = S.xsc[sl + (int64_t)i * nt + j];
@@ -1472,12 +1013,7 @@ __device__ inline void ci_gemm_body(const CiGemmArgs& g, const CiScratch& S, con
   }
   if (threadIdx.x == 0) red = 0u;
   const int64_t np2 = (int64_t)np_ * np_;
-  const int64_t oa = l * np2 + (int64_t)i * kSwB * np_ + (int64_t)kb0 * kSwB;
-  const int64_t ob = l * np2 + (int64_t)j * kSwB * np_ + (int64_t)kb0 * kSwB;
-  const _Float16* ah = g.ah + oa;
-  const _Float16* al = g.al + oa;
-  const _Float16* bh = g.bh + ob;
-  const _Float16* bl = g.bl + ob;
+  const int64_t oa = l * np2 + (int64_t)i * kSwB * np_ + (int64_t)kb0 * kSwB;  // (a row-major A: the L planes)
   sx_f32x16 acc[4][2];
 #pragma unroll
   for (int a = 0; a < 4; ++a)
@@ -1490,67 +1026,24 @@ __device__ inline void ci_gemm_body(const CiGemmArgs& g, const CiScratch& S, con
     kl_sv[t] = g.sv[p];
   }
   float inv;
-  if constexpr (kCiC16) {
-    // operands: A = L planes (row-major) for X, else chunk-major panels from block kb0 on; B chunk-major
-    const int64_t kc0 = (int64_t)kb0 * (kSwB / kC16BK) * kC16Part;
-    C16Opnd A = MODE == kCiX || MODE == kCiTrX ? C16Opnd{ah, g.al - g.ah, np_}
-                                               : C16Opnd{g.ah + c16_panel(l, np_, i) + kc0, g.al - g.ah, 0};
-    C16Opnd B{g.bh + c16_panel(l, np_, j) + kc0, g.bl - g.bh, 0};
-    if constexpr (MODE == kCiTrX) {
-      if ((int)(bid / (g.nwg / g.per_dim)) >= g.inst0)  // Lupd: A = Y^T planes (i, m)
-        A = C16Opnd{g.bh + c16_panel(l, np_, i) + kc0, g.bl - g.bh, 0};
-    }
-    if constexpr (MODE == kCiPanel) {  // A = C block i (pass m's planes, row-major 256 x 256), B = D_m
-      const int64_t oc = (int64_t)l * np_ * kSwB + (int64_t)i * kSwBB, od = ((int64_t)l * nt + kb0) * kSwBB;
-      A = C16Opnd{S.Ch[kb0 & 1] + oc, S.Cl[kb0 & 1] - S.Ch[kb0 & 1], kSwB};
-      B = C16Opnd{S.Dh + od, S.Dl - S.Dh, kSwB};
-    }
-    if constexpr (MODE == kCiU12c) {  // A, B = the L planes (i, m), (j, m), row-major (stride np)
-      A = C16Opnd{S.Lh + oa, S.Ll - S.Lh, np_};
-      B = C16Opnd{S.Lh + ob, S.Ll - S.Lh, np_};
-    }
-    if constexpr (MODE == kCiTrY) {  // A = D_m (row-major, stride 256), B = X^T row tile j (one chunk-major tile)
-      const int64_t od = ((int64_t)l * nt + i) * kSwBB, ox = ((int64_t)l * nt + j) * kSwBB;
-      A = C16Opnd{S.Dh + od, S.Dl - S.Dh, kSwB};
-      B = C16Opnd{S.XRh[i & 1] + ox, S.XRl[i & 1] - S.XRh[i & 1], 0};
-    }
-    if ((MODE == kCiLauum || MODE == kCiLauumKL) && g.pre) {  // (uniform) K^-1 tile from the pipelined lauum
-      const float* T = g.Kinv + l * np2 + (int64_t)i * kSwB * np_ + (int64_t)j * kSwB;
-      const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(T), (short)0, 0x7fffffff,
-                                                                          0x00020000);
-      const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-      const int vo = (((w >> 2) * 128 + 4 * (lane >> 5)) * np_ + (w & 3) * 64 + (lane & 31)) * 4;
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int e = 0; e < 16; ++e)
-#pragma unroll
-          for (int b = 0; b < 2; ++b)
-            acc[a][b][e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
-                rt, vo, ((32 * a + (e & 3) + 8 * (e >> 2)) * np_ + 32 * b) * 4, 0));
-      __syncthreads();  // (kl_mu / kl_sv written above)
-      inv = 1.f;
-    } else {
-      // lauum and trtri's X step: the K ranges of a launch's tiles END together (lauum: at the last block for every
-      // tile; X: at o + h in an instance), so their chunks run from the end (LVAE_CI_KREV=0: in order)
-      constexpr bool krev = LVAE_CI_KREV && (MODE == kCiLauum || MODE == kCiLauumKL || MODE == kCiX);
-      const int nk = nkb * (kSwB / kC16BK);
-      C16BlockRescale rs{sprod, 1.f, krev ? nk : 0};
-      c16_gemm<4>(A, B, nk, lds, acc, rs, krev);
-      inv = 1.0f / rs.scur;
-    }
-  } else {
-    inv = 1.0f / sx_gemm_scaled(ah, al, bh, bl, np_, nkb, sprod, lds, acc);
+  // operands: A = L planes (row-major) for X, else chunk-major panels from block kb0 on; B chunk-major
+  const int64_t kc0 = (int64_t)kb0 * (kSwB / kC16BK) * kC16Part;
+  C16Opnd A = MODE == kCiX || MODE == kCiTrX ? C16Opnd{g.ah + oa, g.al - g.ah, np_}
+                                             : C16Opnd{g.ah + c16_panel(l, np_, i) + kc0, g.al - g.ah, 0};
+  C16Opnd B{g.bh + c16_panel(l, np_, j) + kc0, g.bl - g.bh, 0};
+  if constexpr (MODE == kCiTrX) {
+    if ((int)(bid / (g.nwg / g.per_dim)) >= g.inst0)  // Lupd: A = Y^T planes (i, m)
+      A = C16Opnd{g.bh + c16_panel(l, np_, i) + kc0, g.bl - g.bh, 0};
   }
-  if constexpr (MODE == kCiPanel) {
-    const float slc = x3_scale(sw_block_max(ci_acc_absmax(acc) * inv, &red));
-    const int64_t ot = l * np2 + (int64_t)i * kSwB * np_ + (int64_t)j * kSwB;
-    ci_planes_out_buf(acc, inv, slc, S.Lh + ot, S.Ll + ot, np_);
-    if (threadIdx.x == 0) S.lsc[sl + (int64_t)i * nt + j] = slc;
-  } else if constexpr (MODE == kCiU12c) {
-    const int m = g.h;
-    float* At = g.Kinv + l * np2 + (int64_t)i * kSwB * np_ + (int64_t)j * kSwB;
-    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(At, (short)0, 0x7fffffff, 0x00020000);
+  if constexpr (MODE == kCiTrY) {  // A = D_m (row-major, stride 256), B = X^T row tile j (one chunk-major tile)
+    const int64_t od = ((int64_t)l * nt + i) * kSwBB, ox = ((int64_t)l * nt + j) * kSwBB;
+    A = C16Opnd{S.Dh + od, S.Dl - S.Dh, kSwB};
+    B = C16Opnd{S.XRh[i & 1] + ox, S.XRl[i & 1] - S.XRh[i & 1], 0};
+  }
+  if ((MODE == kCiLauum || MODE == kCiLauumKL) && g.pre) {  // (uniform) K^-1 tile from the pipelined lauum
+    const float* T = g.Kinv + l * np2 + (int64_t)i * kSwB * np_ + (int64_t)j * kSwB;
+    const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(T), (short)0, 0x7fffffff,
+                                                                        0x00020000);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int vo = (((w >> 2) * 128 + 4 * (lane >> 5)) * np_ + (w & 3) * 64 + (lane & 31)) * 4;
 #pragma unroll
@@ -1560,24 +1053,20 @@ __device__ inline void ci_gemm_body(const CiGemmArgs& g, const CiScratch& S, con
 #pragma unroll
         for (int b = 0; b < 2; ++b)
           acc[a][b][e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
-                             ra, vo, ((32 * a + (e & 3) + 8 * (e >> 2)) * np_ + 32 * b) * 4, 2)) -
-                         acc[a][b][e] * inv;
-    if (j == m + 1) {  // (uniform) column m + 1: pass m + 1's C operand
-      const float sc = x3_scale(sw_block_max(ci_acc_absmax(acc), &red));
-      const int64_t on = (int64_t)l * np_ * kSwB + (int64_t)i * kSwBB;
-      ci_planes_out_buf(acc, 1.f, sc, S.Ch[(m + 1) & 1] + on, S.Cl[(m + 1) & 1] + on, kSwB);
-      if (threadIdx.x == 0) S.csc[((int64_t)l * nt + m + 1) * nt + i] = sc;
-    } else {
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int e = 0; e < 16; ++e)
-#pragma unroll
-          for (int b = 0; b < 2; ++b)
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc[a][b][e]), ra, vo,
-                                                  ((32 * a + (e & 3) + 8 * (e >> 2)) * np_ + 32 * b) * 4, 2);
-    }
-  } else if constexpr (MODE == kCiTrY) {
+              rt, vo, ((32 * a + (e & 3) + 8 * (e >> 2)) * np_ + 32 * b) * 4, 0));
+    __syncthreads();  // (kl_mu / kl_sv written above)
+    inv = 1.f;
+  } else {
+    // lauum and trtri's X step: the K ranges of a launch's tiles END together (lauum: at the last block for every
+    // tile; X: at o + h in an instance), so their chunks run from the end (r5, profiles/r5_krev_ab.txt: alone the same
+    // time as in order, with half the HBM fetch in the step and the small far-block terms summed first)
+    constexpr bool krev = MODE == kCiLauum || MODE == kCiLauumKL || MODE == kCiX;
+    const int nk = nkb * (kSwB / kC16BK);
+    C16BlockRescale rs{sprod, 1.f, krev ? nk : 0};
+    c16_gemm<4>(A, B, nk, lds, acc, rs, krev);
+    inv = 1.0f / rs.scur;
+  }
+  if constexpr (MODE == kCiTrY) {
     const float sy = x3_scale(sw_block_max(ci_acc_absmax(acc) * inv, &red));
     ci_transposed_out(acc, -inv, lds, [&](int c, int r0, f32x4 v) {
       const int64_t o = c16_off(l, np_, j * kSwB + c, i * kSwB + r0);  // Y^T tile (j, m)
@@ -1627,24 +1116,17 @@ __device__ inline void ci_gemm_body(const CiGemmArgs& g, const CiScratch& S, con
     }
   } else if constexpr (MODE == kCiX) {
     const float sx = x3_scale(sw_block_max(ci_acc_absmax(acc) * inv, &red));
-    const int64_t ot = l * np2 + (int64_t)j * kSwB * np_ + (int64_t)i * kSwB;  // X^T tile (j, i)
     ci_transposed_out(acc, inv, lds, [&](int c, int r0, f32x4 v) {
-      const int64_t o = kCiC16 ? c16_off(l, np_, j * kSwB + c, i * kSwB + r0) : ot + (int64_t)c * np_ + r0;
+      const int64_t o = c16_off(l, np_, j * kSwB + c, i * kSwB + r0);  // X^T tile (j, i)
       ci_split4(v, sx, g.oth + o, g.otl + o);
     });
     if (threadIdx.x == 0) S.xsc[sl + (int64_t)i * nt + j] = sx;
   } else if constexpr (MODE == kCiY) {
     const float sy = x3_scale(sw_block_max(ci_acc_absmax(acc) * inv, &red));
-    const int64_t ot = l * np2 + (int64_t)i * kSwB * np_ + (int64_t)j * kSwB;   // Y tile (i, j)
-    const int64_t ott = l * np2 + (int64_t)j * kSwB * np_ + (int64_t)i * kSwB;  // Y^T tile (j, i)
-    if constexpr (kCiC16) {
-      const int64_t oc = c16_off(l, np_, i * kSwB, j * kSwB);
-      c16_tile_planes_out(acc, [&](int) { return -inv * sy; }, g.oh + oc, g.ol + oc);
-    } else {
-      ci_planes_out(acc, -inv, sy, g.oh + ot, g.ol + ot, np_);
-    }
+    const int64_t oc = c16_off(l, np_, i * kSwB, j * kSwB);  // Y tile (i, j)
+    c16_tile_planes_out(acc, [&](int) { return -inv * sy; }, g.oh + oc, g.ol + oc);
     ci_transposed_out(acc, -inv, lds, [&](int c, int r0, f32x4 v) {
-      const int64_t o = kCiC16 ? c16_off(l, np_, j * kSwB + c, i * kSwB + r0) : ott + (int64_t)c * np_ + r0;
+      const int64_t o = c16_off(l, np_, j * kSwB + c, i * kSwB + r0);  // Y^T tile (j, i)
       ci_split4(v, sy, g.oth + o, g.otl + o);
     });
     if (threadIdx.x == 0) S.ysc[sl + (int64_t)i * nt + j] = sy;
@@ -1674,49 +1156,26 @@ __device__ inline void ci_gemm_body(const CiGemmArgs& g, const CiScratch& S, con
     }
     if constexpr (MODE == kCiLauumKL) {
       ci_kl_partials(acc, 1.f, g, l, i, j, kl_mu, kl_part);
-      const int64_t tb = l * np2 + (int64_t)i * kSwB * np_ + (int64_t)j * kSwB;   // B tile (i, j)
-      const int64_t tbt = l * np2 + (int64_t)j * kSwB * np_ + (int64_t)i * kSwB;  // B tile (j, i)
       // (uniform) the binned hyper-gradient's plan is on: the mirror of K^-1, no B planes
       const bool hbm = g.bh_out && g.hbon && *g.hbon;
       _Float16* const bho = hbm ? nullptr : g.bh_out;
       _Float16* const blo = hbm ? nullptr : g.bl_out;
       const float sb = bho ? g.bsc[l] : 0.f;  // the dim's split scale of B (ci_bscale_kernel)
-      if (bho && kCiBC16) {
+      if (bho) {
         // B(i, j) = T diag(sqrt v_j), column-scaled, straight from the registers into the chunk-major
         // planes (x3_c16.hpp): tile (i, j) is the 128 KB run of chunks 16 j .. 16 j + 15 of row block i
         const int64_t tc = c16_off(l, np_, i * kSwB, j * kSwB);
         c16_tile_planes_out(acc, [&](int b) { return sb * kl_sv[kSwB + sx_col(b)]; }, bho + tc, blo + tc);
-      } else if (bho) {
-        // B(i, j) = T diag(sqrt v_j): column-scaled, straight from the registers
-        const __amdgpu_buffer_rsrc_t rh = __builtin_amdgcn_make_buffer_rsrc(bho + tb, (short)0, 0x7fffffff, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc(blo + tb, (short)0, 0x7fffffff, 0x00020000);
-        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-        const int vb = (((w >> 2) * 128 + 4 * (lane >> 5)) * np_ + (w & 3) * 64 + (lane & 31)) * 2;
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-          const float mc = sb * kl_sv[kSwB + sx_col(b)];
-#pragma unroll
-          for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-              const float y = acc[a][b][e] * mc;
-              const _Float16 yh = (_Float16)y;
-              const _Float16 yl = (_Float16)(y - (float)yh);
-              const int so = ((32 * a + (e & 3) + 8 * (e >> 2)) * np_ + 32 * b) * 2;
-              __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, yh), rh, vb, so, 0);
-              __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, yl), rl, vb, so, 0);
-            }
-        }
       }
       // (no mirror of K^-1 here: the exact KL's readers -- kl_alpha_sym_kernel, the Gram adjoint, the
       // diagonal -- read its lower tiles only; the B planes need both halves)
-      if (i != j && (bho || hbm || LVAE_KL_MIRROR))
+      if (i != j && (bho || hbm))
         ci_transposed_out(acc, 1.f, lds, [&](int c, int r0, f32x4 v) {
-          if (hbm || LVAE_KL_MIRROR) *reinterpret_cast<f32x4*>(Ot + (int64_t)c * np_ + r0) = v;
+          if (hbm) *reinterpret_cast<f32x4*>(Ot + (int64_t)c * np_ + r0) = v;
           if (bho) {
             const f32x4 s4 = *reinterpret_cast<const f32x4*>(&kl_sv[r0]);
-            // B(j, i) row c, columns r0 .. r0 + 3 (one 4-half run of a chunk either way)
-            const int64_t o = kCiBC16 ? c16_off(l, np_, j * kSwB + c, i * kSwB + r0) : tbt + (int64_t)c * np_ + r0;
+            // B(j, i) row c, columns r0 .. r0 + 3 (one 4-half run of a chunk)
+            const int64_t o = c16_off(l, np_, j * kSwB + c, i * kSwB + r0);
             ci_split4(v * s4, sb, bho + o, blo + o);
           }
         });
@@ -1728,43 +1187,19 @@ __device__ inline void ci_gemm_body(const CiGemmArgs& g, const CiScratch& S, con
   }
 }
 
-
-#define CI_GEMM_LDS                                                                     \
-  __shared__ __attribute__((aligned(16))) _Float16 lds[2 * 4 * kSxPart];                \
-  __shared__ float sprod[64];                                                           \
-  __shared__ uint32_t red;                                                              \
-  __shared__ float kl_mu[2 * kSwB], kl_sv[2 * kSwB], kl_part[6 * kSwB]; /* (kCiLauumKL only) */
-
-template <int MODE>
-__global__ __launch_bounds__(512) void ci_gemm_kernel(CiGemmArgs g, CiScratch S) {
-  CI_GEMM_LDS
-  // (bid0: a launch list cut into several launches, trtri's early part in ci_factor_f32)
-  ci_gemm_body<MODE>(g, S, blockIdx.x + g.bid0, lds, sprod, &red, kl_mu, kl_sv, kl_part);
-}
-
-// two modes in ONE launch (the pipelined schedule's passes: fewer, fuller launches on the caller's stream):
-// workgroups [0, n1) run M1 over g1, the rest M2 over g2
-template <int M1, int M2>
-__global__ __launch_bounds__(512) void ci_pair_kernel(CiGemmArgs g1, CiGemmArgs g2, CiScratch S, int n1) {
-  CI_GEMM_LDS
-  if ((int)blockIdx.x < n1)
-    ci_gemm_body<M1>(g1, S, blockIdx.x, lds, sprod, &red, kl_mu, kl_sv, kl_part);
-  else
-    ci_gemm_body<M2>(g2, S, blockIdx.x - n1, lds, sprod, &red, kl_mu, kl_sv, kl_part);
-}
-
 // ------------------------------------------------------------------------------------------
 // host sequencing
 // ------------------------------------------------------------------------------------------
-// potrf lookahead schedules (the side stream has the highest priority):
-// (a) few latent dims (L <= kCiFuseMaxL): the pivots run back to back on the side stream, each applying
-//     the previous pass's update to its own block (ci_pending_update) and waiting only for U2(m-2), the
-//     last writer of its block before that:
+// ci_factor_f32 does the common setup (checks, zeroing, the fork to the side stream, the early-split decision),
+// then runs one of the two potrf lookahead schedules (the side stream has the highest priority) and the trtri tail:
+// (a) ci_potrf_pending, few latent dims (L <= kCiFuseMaxL): the pivots run back to back on the side stream, each
+//     applying the previous pass's update to its own block (the split pivot, ci_pivot_kernel<kCiPvG>) and waiting
+//     only for U2(m-2), the last writer of its block before that:
 //       side:  pivot(0);  [wait ev_u2(m-1) (ev_c = prep0 for m = 0);  pivot(m+1);  record ev_piv(m+1)]...
 //       main:  prep0;  record ev_c;  [wait ev_piv(m);  panel(m);  U1(m) (without the pivot block) + U2(m), one launch;
-//              record ev_u2(m)]...
-// (b) many latent dims (L > kCiFuseMaxL; the headline L = 16 is still (a)): the chain runs whole on the side stream
-//     beside U2:
+//              record ev_u2(m);  with ci_pipe_mode: rowY(m);  Xupd(m) + Lupd(m)]...
+// (b) ci_potrf_chain, many latent dims (L > kCiFuseMaxL; the headline L = 16 is still (a)): the chain runs whole on
+//     the side stream beside U2:
 //       side:  prep0;  pivot(0);  panel(0);  record ev_prep
 //       main:  [wait ev_prep;  U1(k) (with the pivot block);  record ev_c;  U2(k)]...
 //       side:  [wait ev_c;  pivot(k+1);  panel(k+1);  record ev_prep]...
@@ -1772,9 +1207,9 @@ __global__ __launch_bounds__(512) void ci_pair_kernel(CiGemmArgs g1, CiGemmArgs 
 // their previous readers (panel(k-1), pivot(k)) precede U1(k) on the caller's stream.  The L planes of
 // column k are written once (panel(k)) and read by U1(k), U2(k), and trtri; D by the pivots, the panels
 // and the diagonal copies.
-// Then trtri: the diagonal copy and 2 launches per level; lauum is ci_lauum_f32.  In schedule (b), with
-// LVAE_CI_TRTRI_EARLY=0, under a stream capture and when the caller has lent no early stream
-// (lvae_set_early_stream) all of it follows potrf on the caller's stream.  Else, in schedule (a) (recursive
+// Then trtri (ci_trtri_tail; nothing under ci_pipe_mode, whose passes did it): the diagonal copy and 2 launches
+// per level; lauum is ci_lauum_f32.  In schedule (b), with LVAE_CI_TRTRI_EARLY=0, under a stream capture and when
+// the caller has lent no early stream (lvae_set_early_stream) all of it follows potrf on the caller's stream.  Else, in schedule (a) (recursive
 // doubling, nt >= 2), it is SPLIT at s = the largest power of two below nt, the A-group size of the top level:
 // from pass s on potrf is bound by the pivot chain (64 workgroups per link at L = 16) and the GPU is nearly
 // idle, while the top-left group's part of trtri needs only columns < s:
@@ -1799,68 +1234,184 @@ __global__ __launch_bounds__(512) void ci_pair_kernel(CiGemmArgs g1, CiGemmArgs 
 // runs each on one box; LVAE_CI_TRTRI_EARLY=0 on this library 8.52-8.58.  In the traced step the
 // pivots of passes >= 8 start 134-207 us apart (mean 172) instead of 117-143 (mean 125) beside the early work, and
 // trtri's part after potrf takes 0.83 instead of 1.42 ms (profiles/trtri_early_timeline.txt).  Leaving
-// 128 CUs free instead of the pivot launch's 64 (LVAE_CI_EARLY_FREE) measured the same, 8.19-8.21; none free 8.27-8.28.
+// 128 CUs free instead of the pivot launch's 64 measured the same, 8.19-8.21; none free 8.27-8.28.
 // The same schedule on a stream of the library's own, of the lowest priority, was 11.1-11.6 ms: creating a fifth
 // stream alone cost 2.6 ms, whether used or not -- hence the lent stream.  profiles/trtri_early_ab.txt.)
+//
+// Measured slower and removed, with the environment variables that selected them (commit 40b45d9
+// is the last that contains them):
+//   * each pass's trailing update in two launches, the next pivot's column first (the next pivot waits only for
+//     that part): inverse alone L = 16 5.70 vs 5.59 ms, L = 8 3.60 vs 3.53, L = 4 2.85 vs 2.87
+//     (profiles/r4_lookahead_ab.txt) -- the second launch's tail and the extra launch outweigh the earlier pivot
+//   * the pipelined passes as two fused launches each (panel + rowY, update + Xupd + Lupd) instead of four: L = 2
+//     2.51 vs 2.18 ms for the inverse -- the fused update launch ends later, and the next-but-one pivot waits for it
+//   * the trailing update on 128 x 128 sub-tiles, two workgroups per CU: 116 us for the trailing tiles but + 50 us
+//     for column k+1 as its own launch (9.21 vs 9.14 ms per step), or + a 70 us split pass with the column folded
+//     in (9.58-9.63 vs 9.22); and on a 16-deep DMA ring of 4 stages: 211 vs 166 us per launch, twice the barriers
+//     per tile and 32-B row pieces (r6, profiles/r6_update_ab.txt)
 size_t ci_scratch_bytes(int np_, int L) { return CiScratch(nullptr, np_, L).bytes; }
-int ci_factor_f32(int np_, int L, float* A, void* scratch, _Float16* YT, float* Kinv, double* logdet,
-                  int32_t* info, hipStream_t st, float* lout = nullptr);
+
+static bool ci_ok(hipError_t e) { return e == hipSuccess; }
+
+// Kinv is written last (lauum): until then one plane pair for the X^T planes (kCiX writes tiles (j, i), j < i:
+// strictly upper) and the row-major Y planes (tiles (i, j), i >= j: lower and diagonal) -- the same tile
+// offsets (c16_off), so disjoint tiles.  Nothing of trtri lives in A: the early part may write Y tiles while
+// potrf's trailing updates still run on A.  (The pipelined schedule keeps fp32 X in Kinv and produces no Y planes.)
+struct CiPlanes {
+  _Float16 *YTh, *YTl;  // Y^T (the caller's YT)
+  _Float16 *Yh, *Yl;    // Y, lower and diagonal tiles; X^T, strictly upper tiles (both in Kinv)
+};
+
+// level h of the recursive doubling over the instances [i0, i0 + ni): its X and / or Y launch on q, whole
+// (cap == 0) or cut into launches of at most cap workgroups (the list is longest K first: a launch's tiles are
+// of nearly one length, so cutting it leaves short tails)
+static void ci_trtri_level(const CiScratch& S, const CiPlanes& P, int np_, int L, int h, int i0, int ni, bool do_x,
+                           bool do_y, hipStream_t q, int cap) {
+  const int nt = S.nt, per = ni * h * h, nwg = per * L;
+  if (nwg <= 0) return;
+  if (do_x) {
+    CiGemmArgs gx{S.Lh, S.Ll, P.YTh, P.YTl, nullptr, nullptr, P.Yh, P.Yl, nullptr, np_, nt, h, per, nwg, i0};
+    for (int b0 = 0; b0 < nwg; b0 += cap > 0 ? cap : nwg) {
+      gx.bid0 = b0;
+      ci_gemm_kernel<kCiX><<<min(nwg - b0, cap > 0 ? cap : nwg), 512, 0, q>>>(gx, S);
+    }
+  }
+  if (do_y) {
+    CiGemmArgs gy{P.Yh, P.Yl, P.Yh, P.Yl, P.Yh, P.Yl, P.YTh, P.YTl, nullptr, np_, nt, h, per, nwg, i0};
+    for (int b0 = 0; b0 < nwg; b0 += cap > 0 ? cap : nwg) {
+      gy.bid0 = b0;
+      ci_gemm_kernel<kCiY><<<min(nwg - b0, cap > 0 ? cap : nwg), 512, 0, q>>>(gy, S);
+    }
+  }
+}
+
+// schedule (a).  pipe: trtri + lauum by block rows between the passes (ci_pipe_mode).  s_early > 0: after
+// panel(s_early - 1) the top-left group's part of trtri is forked to the lent stream, its launches capped at ecap
+// workgroups (ci_trtri_tail joins it)
+static int ci_potrf_pending(int np_, int L, float* A, const CiScratch& S, const CiPlanes& P, float* Kinv,
+                            double* logdet, int32_t* info, hipStream_t st, SideStream* sd, bool pipe, int s_early,
+                            int ecap) {
+  const int nt = S.nt;
+  ci_pivot_kernel<1><<<L, 1024, 0, sd->s>>>(A, np_, 0, S, logdet, info, L, g_pivot_prof);
+  if (!ci_ok(hipEventRecord(sd->piv[0], sd->s))) return LVAE_ERR_LAUNCH;
+  if (nt > 1) ci_prep0_kernel<<<dim3(nt - 1, L), 256, 0, st>>>(A, np_, S);
+  if (!ci_ok(hipEventRecord(sd->c, st))) return LVAE_ERR_LAUNCH;
+  for (int m = 0; m < nt; ++m) {
+    if (m + 1 < nt) {
+      if (!ci_ok(hipStreamWaitEvent(sd->s, m == 0 ? sd->c : sd->u2p[(m - 1) & 1], 0))) return LVAE_ERR_LAUNCH;
+      const int Lr = (L + 7) / 8 * 8;
+      ci_pivot_kernel<kCiPvG><<<kCiPvG * Lr, 1024, 0, sd->s>>>(A, np_, m + 1, S, logdet, info, L, g_pivot_prof);
+      if (!ci_ok(hipEventRecord(sd->piv[(m + 1) & 1], sd->s))) return LVAE_ERR_LAUNCH;
+    }
+    if (!ci_ok(hipStreamWaitEvent(st, sd->piv[m & 1], 0))) return LVAE_ERR_LAUNCH;
+    if (m + 1 < nt) {
+      ci_panel_kernel<<<dim3(nt - m - 1, L), 512, 0, st>>>(S, np_, m);
+      if (m == s_early - 1) {
+        // the fork: columns < s_early of L and D are complete.  On the early stream: the top-left group's
+        // diagonal tiles and levels, then the top level's X step
+        if (!ci_ok(hipEventRecord(sd->efork, st)) || !ci_ok(hipStreamWaitEvent(sd->early, sd->efork, 0)))
+          return LVAE_ERR_LAUNCH;
+        {
+          ProfScope pe(LVAE_PH_POTRI, sd->early);
+          ci_diag_copy_kernel<<<dim3(16 * s_early, L), 256, 0, sd->early>>>(S, np_, P.Yh, P.Yl, P.YTh, P.YTl, 0);
+          for (int h = 1; h < s_early; h *= 2)
+            ci_trtri_level(S, P, np_, L, h, 0, s_early / (2 * h), true, true, sd->early, ecap);
+          ci_trtri_level(S, P, np_, L, s_early, 0, 1, true, false, sd->early, ecap);
+        }
+        if (!ci_ok(hipEventRecord(sd->edone, sd->early))) return LVAE_ERR_LAUNCH;
+      }
+      // column m+1 without the pivot block + the trailing tiles
+      const int n1 = nt - m - 2, n2 = (nt - m - 2) * (nt - m - 1) / 2;
+      if (n2 > 0) {
+        ProfScope pu(LVAE_PH_SWEEP_UPD, st);
+        ci_update_kernel<kCiU12><<<(n1 + n2) * L, 512, 0, st>>>(A, S, np_, m, n2, n2 * L, n1);
+      }
+      if (!ci_ok(hipEventRecord(sd->u2p[m & 1], st))) return LVAE_ERR_LAUNCH;
+    }
+    if (pipe) {  // trtri + lauum by block rows beside the chain (after U2(m): off pivot(m+2)'s path)
+      ProfScope pt(LVAE_PH_POTRI, st);
+      const int pery = m + 16;
+      CiGemmArgs gy{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, P.YTh, P.YTl, nullptr, np_, nt, m, pery,
+                    pery * L, 0};
+      ci_gemm_kernel<kCiTrY><<<pery * L, 512, 0, st>>>(gy, S);
+      // Xupd(m) + Lupd(m), one launch
+      const int perx = (nt - m - 1) * (m + 1), perl = (m + 1) * (m + 2) / 2;
+      CiGemmArgs gx{S.Lh, S.Ll, P.YTh, P.YTl, nullptr, nullptr, nullptr, nullptr, Kinv, np_, nt, m, perx + perl,
+                    (perx + perl) * L, perx};
+      ci_gemm_kernel<kCiTrX><<<(perx + perl) * L, 512, 0, st>>>(gx, S);
+    }
+  }
+  return 0;
+}
+
+// schedule (b)
+static int ci_potrf_chain(int np_, int L, float* A, const CiScratch& S, double* logdet, int32_t* info, hipStream_t st,
+                          SideStream* sd) {
+  const int nt = S.nt;
+  if (nt > 1) ci_prep0_kernel<<<dim3(nt - 1, L), 256, 0, sd->s>>>(A, np_, S);
+  ci_pivot_kernel<1><<<L, 1024, 0, sd->s>>>(A, np_, 0, S, logdet, info, L, g_pivot_prof);
+  if (nt > 1) ci_panel_kernel<<<dim3(nt - 1, L), 512, 0, sd->s>>>(S, np_, 0);
+  if (!ci_ok(hipEventRecord(sd->prep, sd->s))) return LVAE_ERR_LAUNCH;
+  for (int k = 0; k + 1 < nt; ++k) {
+    if (!ci_ok(hipStreamWaitEvent(st, sd->prep, 0))) return LVAE_ERR_LAUNCH;  // pivot(k), panel(k)
+    const int n1 = nt - k - 1;  // column k+1 with the pivot block
+    ci_update_kernel<kCiU1><<<n1 * L, 512, 0, st>>>(A, S, np_, k, n1, n1 * L);
+    if (!ci_ok(hipEventRecord(sd->c, st))) return LVAE_ERR_LAUNCH;
+    if (!ci_ok(hipStreamWaitEvent(sd->s, sd->c, 0))) return LVAE_ERR_LAUNCH;
+    ci_pivot_kernel<1><<<L, 1024, 0, sd->s>>>(A, np_, k + 1, S, logdet, info, L, g_pivot_prof);
+    if (k + 2 < nt) ci_panel_kernel<<<dim3(nt - k - 2, L), 512, 0, sd->s>>>(S, np_, k + 1);
+    if (!ci_ok(hipEventRecord(sd->prep, sd->s))) return LVAE_ERR_LAUNCH;
+    const int n2 = (nt - k - 2) * (nt - k - 1) / 2;
+    if (n2 > 0) {
+      ProfScope pu(LVAE_PH_SWEEP_UPD, st);
+      ci_update_kernel<kCiU2><<<n2 * L, 512, 0, st>>>(A, S, np_, k, n2, n2 * L);
+    }
+  }
+  if (!ci_ok(hipStreamWaitEvent(st, sd->prep, 0))) return LVAE_ERR_LAUNCH;  // the last pivot
+  return 0;
+}
+
+// trtri after potrf (recursive doubling, 2 launches per level): with lauum (ci_lauum_f32) the rest of potri.
+// s_early > 0: the early part runs on the lent stream already (ci_potrf_pending)
+static int ci_trtri_tail(int np_, int L, const CiScratch& S, const CiPlanes& P, hipStream_t st, SideStream* sd,
+                         int s_early) {
+  const int nt = S.nt;
+  ProfScope ps(LVAE_PH_POTRI, st);
+  if (s_early > 0) {
+    // the rest: the bottom-right group's diagonal tiles and levels, then (the join) the top level's Y step
+    std::lock_guard<std::recursive_mutex> lock(side_mutex());
+    ci_diag_copy_kernel<<<dim3(16 * (nt - s_early), L), 256, 0, st>>>(S, np_, P.Yh, P.Yl, P.YTh, P.YTl, s_early);
+    for (int h = 1; h < s_early; h *= 2) {
+      const int i0 = s_early / (2 * h);
+      ci_trtri_level(S, P, np_, L, h, i0, (nt + 2 * h - 1) / (2 * h) - i0, true, true, st, 0);
+    }
+    if (!ci_ok(hipStreamWaitEvent(st, sd->edone, 0))) return LVAE_ERR_LAUNCH;
+    ci_trtri_level(S, P, np_, L, s_early, 0, 1, false, true, st, 0);
+  } else {
+    ci_diag_copy_kernel<<<dim3(16 * nt, L), 256, 0, st>>>(S, np_, P.Yh, P.Yl, P.YTh, P.YTl, 0);
+    for (int h = 1; h < nt; h *= 2) ci_trtri_level(S, P, np_, L, h, 0, (nt + 2 * h - 1) / (2 * h), true, true, st, 0);
+  }
+  return 0;
+}
 
 // potrf + trtri: Y = L^-1 as the Y^T planes YT (+ the per-tile scales in the scratch); A and Kinv are
 // overwritten (Kinv holds the X^T planes)
 // (lout: potrf only -- no trtri, no pipelined schedule -- with L written in fp32 into lout's lower tiles)
 int ci_factor_f32(int np_, int L, float* A, void* scratch, _Float16* YT, float* Kinv, double* logdet,
-                  int32_t* info, hipStream_t st, float* lout) {
+                  int32_t* info, hipStream_t st, float* lout = nullptr) {
   if (np_ <= 0 || np_ % kSwB || np_ / kSwB > 64) return -1;
   if (L <= 0) return -2;
   CiScratch S((char*)scratch, np_, L);
   S.lout = lout;
   const int nt = S.nt;
   const int64_t full = (int64_t)L * np_ * np_;
-  _Float16* YTh = YT;
-  _Float16* YTl = YT + full;
-  // Kinv is written last (lauum): until then one plane pair for the X^T planes (kCiX writes tiles (j, i), j < i:
-  // strictly upper) and the row-major Y planes (tiles (i, j), i >= j: lower and diagonal) -- the same tile
-  // offsets (c16_off, or row-major), so disjoint tiles.  Nothing of trtri lives in A: the early part below may
-  // write Y tiles while potrf's trailing updates still run on A.  (The pipelined schedule keeps fp32 X in Kinv
-  // and produces no Y planes.)
-  _Float16* XTh = reinterpret_cast<_Float16*>(Kinv);
-  _Float16* XTl = XTh + full;
-  _Float16* Yh = XTh;
-  _Float16* Yl = XTl;
-  auto ok = [](hipError_t e) { return e == hipSuccess; };
-  bool pipe = false;
-  // trtri's early part (schedule (a), recursive doubling, nt >= 2; see the schedules above): the top level's
-  // A-group size s_top, the early launches' stream and grid cap
+  _Float16* const kh = reinterpret_cast<_Float16*>(Kinv);
+  const CiPlanes P{YT, YT + full, kh, kh + full};
+  const bool fuse = L <= kCiFuseMaxL;
+  const bool pipe = !lout && ci_pipe_mode(np_, L);  // (implies fuse and the XR planes)
   static const bool early_env = !getenv("LVAE_CI_TRTRI_EARLY") || atoi(getenv("LVAE_CI_TRTRI_EARLY")) != 0;
-  // the compute units the early launches leave free (A/B runs; read once per process): by default the pending
-  // pivot launch's workgroup count, and never less than a quarter of the device for the early work
-  static const int free_env = getenv("LVAE_CI_EARLY_FREE") ? atoi(getenv("LVAE_CI_EARLY_FREE")) : -1;
-  bool early = false;
-  int s_top = 1, ecap = 0;
-  while (2 * s_top < nt) s_top *= 2;
   SideStream* sd = nullptr;
-  // level h of the recursive doubling over the instances [i0, i0 + ni): its X and / or Y launch on q, whole
-  // (cap == 0) or cut into launches of at most cap workgroups (the list is longest K first: a launch's tiles are
-  // of nearly one length, so cutting it leaves short tails)
-  auto trtri_level = [&](int h, int i0, int ni, bool do_x, bool do_y, hipStream_t q, int cap) {
-    const int per = ni * h * h, nwg = per * L;
-    if (nwg <= 0) return;
-    if (do_x) {
-      CiGemmArgs gx{S.Lh, S.Ll, YTh, YTl, nullptr, nullptr, XTh, XTl, nullptr, np_, nt, h, per, nwg, i0};
-      for (int b0 = 0; b0 < nwg; b0 += cap > 0 ? cap : nwg) {
-        gx.bid0 = b0;
-        ci_gemm_kernel<kCiX><<<min(nwg - b0, cap > 0 ? cap : nwg), 512, 0, q>>>(gx, S);
-      }
-    }
-    if (do_y) {
-      CiGemmArgs gy{Yh, Yl, XTh, XTl, Yh, Yl, YTh, YTl, nullptr, np_, nt, h, per, nwg, i0};
-      for (int b0 = 0; b0 < nwg; b0 += cap > 0 ? cap : nwg) {
-        gy.bid0 = b0;
-        ci_gemm_kernel<kCiY><<<min(nwg - b0, cap > 0 ? cap : nwg), 512, 0, q>>>(gy, S);
-      }
-    }
-  };
+  int s_early = 0;  // trtri's early part: the top level's A-group size, 0 without one
   {
     ProfScope ps(LVAE_PH_POTRF, st);
     std::lock_guard<std::recursive_mutex> lock(side_mutex());
@@ -1868,176 +1419,24 @@ int ci_factor_f32(int np_, int L, float* A, void* scratch, _Float16* YT, float* 
     (void)zero_async(logdet, sizeof(double) * L, st);
     (void)zero_async(info, sizeof(int32_t) * L, st);
     (void)zero_async(S.cnt, CiScratch::cnt_bytes(L, nt), st);  // the split pivots' tickets
-    if (!ok(hipEventRecord(sd->fork, st)) || !ok(hipStreamWaitEvent(sd->s, sd->fork, 0))) return LVAE_ERR_LAUNCH;
-    const bool fuse = L <= kCiFuseMaxL;
-    const int pmode = lout ? 0 : ci_pipe_mode(np_, L);  // (implies fuse and the XR planes)
-    // the split pivot (kCiPvG workgroups per pending pivot); LVAE_PIVOT_SPLIT=0: one workgroup per dim
-    static const bool split_env = !getenv("LVAE_PIVOT_SPLIT") || atoi(getenv("LVAE_PIVOT_SPLIT")) != 0;
-    const bool split = split_env;
-    // LVAE_CI_PAIR=1: the pipelined passes as two ci_pair_kernel launches each instead of four (measured
-    // slower: the fused update launch ends later, and the next-but-one pivot waits for it -- scripts/inv_ab.py,
-    // L = 2: 2.51 vs 2.18 ms for the inverse)
-    static const bool pair = getenv("LVAE_CI_PAIR") && atoi(getenv("LVAE_CI_PAIR")) != 0;
-    // LVAE_CI_LOOKAHEAD=1: each pass's trailing update in two launches, the next pivot's column first (the
-    // next pivot waits only for that part).  Measured slower (scripts/inv_ab.py, inverse alone: L = 16
-    // 5.70 vs 5.59 ms, L = 8 3.60 vs 3.53, L = 4 2.85 vs 2.87; profiles/r4_lookahead_ab.txt): the second
-    // launch's tail and the extra launch outweigh the earlier pivot start.  Off by default.
-    static const bool la = getenv("LVAE_CI_LOOKAHEAD") && atoi(getenv("LVAE_CI_LOOKAHEAD")) != 0;
-    // LVAE_CI_U128=1 (opt-in): the trailing update by the 128 x 128 sub-tile kernel (ci_update128_kernel) instead of
-    // whole 256-tiles fused with column m+1's (ci_update_kernel<kCiU12>, the default)
-    const bool u128 = getenv("LVAE_CI_U128") && atoi(getenv("LVAE_CI_U128")) != 0;
-    // LVAE_CI_URING=1: the fused update on the 16-deep ring (ci_update_ring_kernel) instead of the double-buffered
-    // 32-deep stages (ci_update_kernel).  Both opt-in forms measured slower (r6, profiles/r6_update_ab.txt): the ring
-    // 211 vs 166 us per launch, the 128 x 128 sub-tiles 116 us for the trailing tiles but + 50 us for column k+1 as
-    // its own launch (9.21 vs 9.14 ms per step), or + a 70 us split pass with the column folded in (9.58-9.63 vs 9.22)
-    const bool uring = getenv("LVAE_CI_URING") && atoi(getenv("LVAE_CI_URING")) != 0;
-    pipe = pmode > 0;
+    if (!ci_ok(hipEventRecord(sd->fork, st)) || !ci_ok(hipStreamWaitEvent(sd->s, sd->fork, 0))) return LVAE_ERR_LAUNCH;
     // (the lent stream stays out of a capture of the caller's: a captured call keeps the unsplit order)
     hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
-    if (!ok(hipStreamIsCapturing(st, &cap_st))) return LVAE_ERR_LAUNCH;
-    early = early_env && fuse && !pipe && !lout && nt >= 2 && sd->early && sd->early != st &&
-            cap_st == hipStreamCaptureStatusNone;
-    {
-      const int pvwg = split ? kCiPvG * ((L + 7) / 8 * 8) : L;
-      ecap = max(sd->cus - (free_env >= 0 ? free_env : pvwg), max(sd->cus / 4, 1));
-    }
-    if (fuse) {
-      ci_pivot_kernel<1><<<L, 1024, 0, sd->s>>>(A, np_, 0, S, logdet, info, 0, L, g_pivot_prof);
-      if (!ok(hipEventRecord(sd->piv[0], sd->s))) return LVAE_ERR_LAUNCH;
-      if (nt > 1) ci_prep0_kernel<<<dim3(nt - 1, L), 256, 0, st>>>(A, np_, S);
-      if (!ok(hipEventRecord(sd->c, st))) return LVAE_ERR_LAUNCH;
-      for (int m = 0; m < nt; ++m) {
-        if (m + 1 < nt) {
-          if (!ok(hipStreamWaitEvent(sd->s, m == 0 ? sd->c : sd->u2p[(m - 1) & 1], 0))) return LVAE_ERR_LAUNCH;
-          if (split) {
-            const int Lr = (L + 7) / 8 * 8;
-            ci_pivot_kernel<kCiPvG><<<kCiPvG * Lr, 1024, 0, sd->s>>>(A, np_, m + 1, S, logdet, info, 1, L, g_pivot_prof);
-          } else {
-            ci_pivot_kernel<1><<<L, 1024, 0, sd->s>>>(A, np_, m + 1, S, logdet, info, 1, L, g_pivot_prof);
-          }
-          if (!ok(hipEventRecord(sd->piv[(m + 1) & 1], sd->s))) return LVAE_ERR_LAUNCH;
-        }
-        if (!ok(hipStreamWaitEvent(st, sd->piv[m & 1], 0))) return LVAE_ERR_LAUNCH;
-        if (pipe && pair) {
-          // two launches per pass: [panel(m) + rowY(m)] then [U1 + U2(m) + Xupd(m) (+ Lupd(m))] -- the
-          // caller's stream keeps up with the pivot chain (four separate launches per pass did not)
-          ProfScope pt(LVAE_PH_POTRI, st);
-          const int npn = nt - m - 1, ny = m + 16;
-          CiGemmArgs gp{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, np_, nt, m,
-                        max(npn, 1), npn * L, 0};
-          CiGemmArgs gy{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, YTh, YTl, nullptr, np_, nt, m, ny, ny * L, 0};
-          ci_pair_kernel<kCiPanel, kCiTrY><<<(npn + ny) * L, 512, 0, st>>>(gp, gy, S, npn * L);
-          const int n1 = max(nt - m - 2, 0), n2 = max(nt - m - 2, 0) * max(nt - m - 1, 0) / 2, nu = n1 + n2;
-          const int perx = (nt - m - 1) * (m + 1), perl = pmode == 2 ? (m + 1) * (m + 2) / 2 : 0;
-          CiGemmArgs gu{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, A, np_, nt, m,
-                        max(nu, 1), nu * L, n1};
-          CiGemmArgs gx{S.Lh, S.Ll, YTh, YTl, nullptr, nullptr, nullptr, nullptr, Kinv, np_, nt, m, max(perx + perl, 1),
-                        (perx + perl) * L, perx};
-          if (nu + perx + perl > 0) ci_pair_kernel<kCiU12c, kCiTrX><<<(nu + perx + perl) * L, 512, 0, st>>>(gu, gx, S, nu * L);
-          if (m + 1 < nt && !ok(hipEventRecord(sd->u2p[m & 1], st))) return LVAE_ERR_LAUNCH;
-          continue;
-        }
-        if (m + 1 < nt) {
-          ci_panel_kernel<<<dim3(nt - m - 1, L), 512, 0, st>>>(S, np_, m);
-          if (early && m == s_top - 1) {
-            // the fork: columns < s_top of L and D are complete.  On the early stream: the top-left group's
-            // diagonal tiles and levels, then the top level's X step
-            if (!ok(hipEventRecord(sd->efork, st)) || !ok(hipStreamWaitEvent(sd->early, sd->efork, 0)))
-              return LVAE_ERR_LAUNCH;
-            {
-              ProfScope pe(LVAE_PH_POTRI, sd->early);
-              ci_diag_copy_kernel<<<dim3(16 * s_top, L), 256, 0, sd->early>>>(S, np_, Yh, Yl, YTh, YTl, 0);
-              for (int h = 1; h < s_top; h *= 2) trtri_level(h, 0, s_top / (2 * h), true, true, sd->early, ecap);
-              trtri_level(s_top, 0, 1, true, false, sd->early, ecap);
-            }
-            if (!ok(hipEventRecord(sd->edone, sd->early))) return LVAE_ERR_LAUNCH;
-          }
-          // column m+1 without the pivot block + the trailing tiles
-          const int n1 = nt - m - 2, n2 = (nt - m - 2) * (nt - m - 1) / 2;
-          if (n2 > 0 && la && n2 > 1) {
-            // lookahead split: first what pivot(m+2) reads -- column m+1 (the next C planes) and the trailing
-            // tile (m+2, m+2) (sx_tri_blocked's tile 0) -- then the rest, which runs beside pivot(m+2)
-            ProfScope pu(LVAE_PH_SWEEP_UPD, st);  // (both launches: the pass's whole trailing update)
-            ci_update_kernel<kCiU12><<<(n1 + 1) * L, 512, 0, st>>>(A, S, np_, m, 1, L, n1, 0);
-            if (!ok(hipEventRecord(sd->u2p[m & 1], st))) return LVAE_ERR_LAUNCH;
-            ci_update_kernel<kCiU12><<<(n2 - 1) * L, 512, 0, st>>>(A, S, np_, m, n2 - 1, (n2 - 1) * L, 0, 1);
-          } else {
-            if (n2 > 0) {
-              ProfScope pu(LVAE_PH_SWEEP_UPD, st);
-              if (u128) {  // column m+1 and the trailing tiles as 128 x 128 sub-tiles, two workgroups per CU; then
-                           // column m+1's fp32 tiles split into pass m+1's C planes (each 256-tile's exact-max scale)
-                ci_update128_kernel<<<4 * (n1 + n2) * L, 256, 0, st>>>(A, S, np_, m, n2, 4 * (n1 + n2) * L, n1);
-                ci_prep0_kernel<<<dim3(n1, L), 256, 0, st>>>(A, np_, S, m + 1);
-              } else if (uring) {
-                ci_update_ring_kernel<kCiU12><<<(n1 + n2) * L, 512, 0, st>>>(A, S, np_, m, n2, n2 * L, n1);
-              } else {
-                ci_update_kernel<kCiU12><<<(n1 + n2) * L, 512, 0, st>>>(A, S, np_, m, n2, n2 * L, n1);
-              }
-            }
-            if (!ok(hipEventRecord(sd->u2p[m & 1], st))) return LVAE_ERR_LAUNCH;
-          }
-        }
-        if (pipe) {  // trtri by block rows beside the chain (after U2(m): off pivot(m+2)'s path)
-          ProfScope pt(LVAE_PH_POTRI, st);
-          const int pery = m + 16;
-          CiGemmArgs gy{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, YTh, YTl, nullptr, np_, nt, m, pery,
-                        pery * L, 0};
-          ci_gemm_kernel<kCiTrY><<<pery * L, 512, 0, st>>>(gy, S);
-          // Xupd(m) (+ Lupd(m) in mode 2), one launch
-          const int perx = (nt - m - 1) * (m + 1), perl = pmode == 2 ? (m + 1) * (m + 2) / 2 : 0;
-          if (perx + perl > 0) {
-            CiGemmArgs gx{S.Lh, S.Ll, YTh, YTl, nullptr, nullptr, nullptr, nullptr, Kinv, np_, nt, m, perx + perl,
-                          (perx + perl) * L, perx};
-            ci_gemm_kernel<kCiTrX><<<(perx + perl) * L, 512, 0, st>>>(gx, S);
-          }
-        }
-      }
-    } else {
-      if (nt > 1) ci_prep0_kernel<<<dim3(nt - 1, L), 256, 0, sd->s>>>(A, np_, S);
-      ci_pivot_kernel<1><<<L, 1024, 0, sd->s>>>(A, np_, 0, S, logdet, info, 0, L, g_pivot_prof);
-      if (nt > 1) ci_panel_kernel<<<dim3(nt - 1, L), 512, 0, sd->s>>>(S, np_, 0);
-      if (!ok(hipEventRecord(sd->prep, sd->s))) return LVAE_ERR_LAUNCH;
-      for (int k = 0; k + 1 < nt; ++k) {
-        if (!ok(hipStreamWaitEvent(st, sd->prep, 0))) return LVAE_ERR_LAUNCH;  // pivot(k), panel(k)
-        const int n1 = nt - k - 1;  // column k+1 with the pivot block
-        ci_update_kernel<kCiU1><<<n1 * L, 512, 0, st>>>(A, S, np_, k, n1, n1 * L);
-        if (!ok(hipEventRecord(sd->c, st))) return LVAE_ERR_LAUNCH;
-        if (!ok(hipStreamWaitEvent(sd->s, sd->c, 0))) return LVAE_ERR_LAUNCH;
-        ci_pivot_kernel<1><<<L, 1024, 0, sd->s>>>(A, np_, k + 1, S, logdet, info, 0, L, g_pivot_prof);
-        if (k + 2 < nt) ci_panel_kernel<<<dim3(nt - k - 2, L), 512, 0, sd->s>>>(S, np_, k + 1);
-        if (!ok(hipEventRecord(sd->prep, sd->s))) return LVAE_ERR_LAUNCH;
-        const int n2 = (nt - k - 2) * (nt - k - 1) / 2;
-        if (n2 > 0) {
-          ProfScope pu(LVAE_PH_SWEEP_UPD, st);
-          if (u128)
-            ci_update128_kernel<<<4 * n2 * L, 256, 0, st>>>(A, S, np_, k, n2, 4 * n2 * L);
-          else
-            ci_update_kernel<kCiU2><<<n2 * L, 512, 0, st>>>(A, S, np_, k, n2, n2 * L);
-        }
-      }
-      if (!ok(hipStreamWaitEvent(st, sd->prep, 0))) return LVAE_ERR_LAUNCH;  // the last pivot
-    }
+    if (!ci_ok(hipStreamIsCapturing(st, &cap_st))) return LVAE_ERR_LAUNCH;
+    if (early_env && fuse && !pipe && !lout && nt >= 2 && sd->early && sd->early != st &&
+        cap_st == hipStreamCaptureStatusNone)
+      for (s_early = 1; 2 * s_early < nt;) s_early *= 2;
+    // the early launches leave the pending pivot launch's workgroup count of compute units free, and keep at
+    // least a quarter of the device
+    const int ecap = max(sd->cus - kCiPvG * ((L + 7) / 8 * 8), max(sd->cus / 4, 1));
+    if (fuse)
+      LVAE_TRY(ci_potrf_pending(np_, L, A, S, P, Kinv, logdet, info, st, sd, pipe, s_early, ecap));
+    else
+      LVAE_TRY(ci_potrf_chain(np_, L, A, S, logdet, info, st, sd));
   }
   LVAE_CHECK_LAUNCH();
   if (lout) return 0;
-  if (!pipe) {
-    // trtri (recursive doubling, 2 launches per level): with lauum (ci_lauum_f32) the rest of potri
-    ProfScope ps(LVAE_PH_POTRI, st);
-    if (early) {
-      // the rest: the bottom-right group's diagonal tiles and levels, then (the join) the top level's Y step
-      std::lock_guard<std::recursive_mutex> lock(side_mutex());
-      ci_diag_copy_kernel<<<dim3(16 * (nt - s_top), L), 256, 0, st>>>(S, np_, Yh, Yl, YTh, YTl, s_top);
-      for (int h = 1; h < s_top; h *= 2) {
-        const int i0 = s_top / (2 * h);
-        trtri_level(h, i0, (nt + 2 * h - 1) / (2 * h) - i0, true, true, st, 0);
-      }
-      if (!ok(hipStreamWaitEvent(st, sd->edone, 0))) return LVAE_ERR_LAUNCH;
-      trtri_level(s_top, 0, 1, false, true, st, 0);
-    } else {
-      ci_diag_copy_kernel<<<dim3(16 * nt, L), 256, 0, st>>>(S, np_, Yh, Yl, YTh, YTl, 0);
-      for (int h = 1; h < nt; h *= 2) trtri_level(h, 0, (nt + 2 * h - 1) / (2 * h), true, true, st, 0);
-    }
-  }
+  if (!pipe) LVAE_TRY(ci_trtri_tail(np_, L, S, P, st, sd, s_early));
   LVAE_CHECK_LAUNCH();
   return 0;
 }
@@ -2081,7 +1480,7 @@ int ci_lauum_f32(int np_, int L, void* scratch, const _Float16* YT, float* Kinv,
   const int64_t full = (int64_t)L * np_ * np_;
   ProfScope ps(LVAE_PH_POTRI, st);
   CiGemmArgs gl{YT, YT + full, YT, YT + full, nullptr, nullptr, nullptr, nullptr, Kinv, np_, nt, 0, per, nwg, 0};
-  gl.pre = ci_pipe_mode(np_, L) == 2;  // (the factor accumulated K^-1 already: the same decision)
+  gl.pre = ci_pipe_mode(np_, L);  // (the factor accumulated K^-1 already: the same decision)
   if (mu) {
     gl.mu = mu;
     gl.sv = sv;
@@ -2112,8 +1511,6 @@ int ci_lauum_flagged_f32(int np_, int L, void* scratch, const _Float16* YT, floa
   LVAE_CHECK_LAUNCH();
   return 0;
 }
-
-int ci_pipe_mode_of(int np_, int L) { return ci_pipe_mode(np_, L); }
 
 // the per-tile split scales of Y (ysc(l, i, j), both plane orientations) in the factor's scratch
 const float* ci_ysc_ptr(void* scratch, int np_, int L) { return CiScratch((char*)scratch, np_, L).ysc; }

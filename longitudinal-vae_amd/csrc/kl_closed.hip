@@ -81,7 +81,7 @@ int kl_refine_apply(const lvae_kernel_spec* spec, const double* x, int ldx, int 
                     hipStream_t st);
 int ci_lauum_flagged_f32(int np_, int L, void* scratch, const _Float16* YT, float* Kinv, const int* flag, hipStream_t st);
 const float* ci_ysc_ptr(void* scratch, int np_, int L);
-int ci_pipe_mode_of(int np_, int L);
+bool ci_pipe_mode(int np_, int L);
 size_t kl_refine_part_bytes(int np_, int L);
 int kl_refine_diag(const lvae_kernel_spec* spec, const double* x, int ldx, int n, int np_, int L,
                    const double* params, const double* noise, const float* Kinv, double* kdiag, double* K64,
@@ -462,7 +462,7 @@ int lvae_kl_closed_factor_f32(const lvae_kernel_spec* spec, const double* x, int
   KLWorkspace ws((char*)workspace, np_, L);
   // the early reduce: this call's LVAE_KL_EARLY, non-pipelined factors only; recorded for the calls that follow on
   // this workspace
-  kl_early_record(workspace, kl_early_env() && ci_pipe_mode_of(np_, L) == 0);
+  kl_early_record(workspace, kl_early_env() && !ci_pipe_mode(np_, L));
   // the binned residual's plan (x only) goes on the side stream behind the Cholesky's pivot chain, beside
   // the trailing updates / trtri; the reduce waits for it (event rb)
   const bool rb_on = kl_resid_bins_enabled(spec, n);

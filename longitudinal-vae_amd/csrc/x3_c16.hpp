@@ -24,9 +24,8 @@
 
 namespace lvae {
 
-// the S GEMM's operand planes (B = K^-1 diag(sqrt v), written by the exact KL's lauum epilogue) are in
-// this layout and the S GEMM runs on this core (false: row-major planes and syrk_tiles_kernel)
-constexpr bool kCiBC16 = true;
+// (the S GEMM's operand planes, B = K^-1 diag(sqrt v), written by the exact KL's lauum epilogue, are in this
+// layout, and the S GEMM runs on this core)
 #ifndef LVAE_C16NS
 #define LVAE_C16NS 5
 #endif

@@ -5,7 +5,7 @@ fresh child each), with two calls in flight on the shared early stream, and unde
 The early stream is one the caller lends (lvae_set_early_stream; the library creates none: a fifth stream in a step
 that already uses the process's 4 hardware queues serialises it).  Every process here lends one before its first call.
 
-All shapes have L >= 3 latent dims per call: off the pipelined schedule (LVAE_CI_PIPE_MAX_L = 2), which has no
+All shapes have L >= 3 latent dims per call: off the pipelined schedule (kCiPipeMaxL = 2), which has no
 recursive doubling to split.  s = the largest power of two below nt = n / 256 is the split point."""
 import ctypes
 import functools
