@@ -263,7 +263,7 @@ int lvae_kl_closed_resid_state(int n, int L, const void* workspace, int32_t* cov
  * 256-block tiles read, overwritten); Ainv [L, np, np] full symmetric out; logdet [L]; info [L]
  * LAPACK-style (first bad column + 1); scratch: lvae_spd_inv_chol_scratch_size(np, L) bytes, 256-B
  * aligned.  Backward-stable in the Cholesky sense: |I - A Ainv| ~ cond(A) 2^-24 (the rounds 1-2 block
- * Gauss-Jordan sweep, ~100x less accurate at cond 1e5, is retired: csrc/retired/spd_sweep.hip, not built).
+ * Gauss-Jordan sweep, ~100x less accurate at cond 1e5, is gone: commit 97b7453 is the last that holds spd_sweep.hip).
  * Replaces torch.cholesky + cholesky_solve(I) + the log-det (elbo_functions.py:26-29).
  * Returns 0, LVAE_ERR_LAUNCH, or before any launch: -3 (A NULL) -4 (scratch NULL or misaligned) -5 (Ainv NULL)
  * -6 (logdet NULL) -7 (info NULL) -1 (np <= 0, np % 256 != 0 or np > 16384) -2 (L <= 0), checked in that order. */

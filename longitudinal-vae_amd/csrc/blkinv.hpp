@@ -11,7 +11,7 @@
 // (row J's values to every lane group) v_permlane32_swap + v_permlane16_swap: no LDS round trip.  In fp64 the panel L_ik is formed by
 // substitution, as LAPACK's potrf (trsm) does; only the diagonal-block solves of passes 2/3 use the
 // explicit X_k (as LAPACK's blocked trtri).  Explicit-inverse panels (X_k or D_k^-1 = X_k^T X_k) or a
-// Gauss-Jordan sweep lose 1.5 to 5 digits at cond ~1e8 (K0zz with its 1e-6 jitter; scripts/micro).
+// Gauss-Jordan sweep lose 1.5 to 5 digits at cond ~1e8 (K0zz with its 1e-6 jitter).
 //
 // Barriers: 2 per block step in pass 1, 1 in passes 2 and 3 (32 at n = 128, vs 96 steps of the
 // four-column element-wise formulation); the pivot-block factorisation is the only serial part.
@@ -94,11 +94,6 @@ __device__ inline double bi_group_bcast(double v) {
   const unsigned long long u = (unsigned long long)__double_as_longlong(v);
   const unsigned lo = bi_group_bcast32<G>((unsigned)u), hi = bi_group_bcast32<G>((unsigned)(u >> 32));
   return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-
-template <typename T>
-__device__ inline T bi_pick4(T v0, T v1, T v2, T v3, int idx) {
-  return idx == 0 ? v0 : (idx == 1 ? v1 : (idx == 2 ? v2 : v3));
 }
 
 // Pivot J of the in-register 16x16 Cholesky: s = trailing Schur complement (full symmetric tile),

@@ -6,9 +6,10 @@
 // scale s = x3_scale(max |block|) per 256 x 256 block from the block's exact max, taken by the kernel
 // that writes the block).
 //
-// Why Cholesky and not the block sweep (spd_sweep.hip): the sweep (Gauss-Jordan on SPD) updates the
-// already inverted part in every pass, and its K^-1 error grows ~100x faster with cond(K) (emulated
-// in fp32 at N = 1024, cond 1.3e5: |I - K X|_2 = 2.7 against 0.03 here).  Same n^3 flops.
+// Why Cholesky and not the rounds 1-2 block sweep (spd_sweep.hip, last held by commit 97b7453): the sweep
+// (Gauss-Jordan on SPD) updates the already inverted part in every pass, and its K^-1 error grows ~100x
+// faster with cond(K) (emulated in fp32 at N = 1024, cond 1.3e5: |I - K X|_2 = 2.7 against 0.03 here).
+// Same n^3 flops.
 //
 //   1. potrf, right-looking, one pass per block column k (all L dims in every launch):
 //        pivot(k)  A_kk -> L_kk (blocked Cholesky in LDS on fp32 MFMA, pv_lds.hpp), log|A_kk|, info,
@@ -117,7 +118,6 @@ struct CiScratch {
   }
   static size_t cnt_bytes(int L, int nt) { return ((size_t)L * nt * 4 + 15) & ~size_t(15); }
   __device__ float& c_scale(int l, int k, int i) const { return csc[((int64_t)l * nt + k) * nt + i]; }
-  __device__ float& t_scale(float* s, int l, int i, int j) const { return s[((int64_t)l * nt + i) * nt + j]; }
 };
 
 // ------------------------------------------------------------------------------------------
@@ -395,7 +395,7 @@ __global__ __launch_bounds__(1024) void ci_pivot_kernel(const float* __restrict_
   CI_STAMP(3);
 #endif
 
-  // 2. L^-1 in place by recursive doubling (levels of 64, 128, 256 rows; see spd_sweep.hip's pivot)
+  // 2. L^-1 in place by recursive doubling (levels of 64, 128, 256 rows)
   if (w < 4) {
     const int a = 2 * w;
     pv_f32x16 X = {}, Y = {};
@@ -632,8 +632,7 @@ __global__ __launch_bounds__(512) void ci_panel_kernel(CiScratch S, int np_, int
 // ------------------------------------------------------------------------------------------
 // update(k): A_IJ -= L_Ik L_Jk^T on lower 256-tiles, K = 256, one 512-thread workgroup per tile on the
 // pre-split planes of L (DMA-staged, double-buffered chunks of 32); A enters in 8 chunks of 16
-// accumulator elements INSIDE the K loop (non-temporal: the A stream does not evict the planes), as in
-// the sweep's update (spd_sweep.hip).  MODE:
+// accumulator elements INSIDE the K loop (non-temporal: the A stream does not evict the planes).  MODE:
 //   kCiU1  column k+1 (tiles (I, k+1), I >= k+1 with the next pivot block, I >= k+2 without it):
 //          written as the planes of pass k+1's C operand (the diagonal tile in fp32, for the pivot)
 //   kCiU2  the trailing tiles I >= J >= k+2, in place

@@ -18,8 +18,6 @@
 
 namespace lvae {
 
-constexpr int kWave = 64;
-
 inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 

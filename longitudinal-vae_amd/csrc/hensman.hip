@@ -275,16 +275,6 @@ __global__ void gb_kernel(int P_b, int T, int L, double kc, const double* __rest
   GK0[e] = ok ? c * iB[e] : 0.0;
 }
 
-// Y[l][i][j] += a * X[l][j][i]
-__global__ void add_transpose_kernel(int L, int M, double a, const double* __restrict__ X, double* __restrict__ Y) {
-  const int64_t MM = (int64_t)M * M;
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= L * MM) return;
-  const int64_t l = e / MM;
-  const int i = (int)((e % MM) / M), j = (int)(e % M);
-  Y[e] += a * X[l * MM + (int64_t)j * M + i];
-}
-
 }  // namespace
 }  // namespace lvae
 

@@ -175,27 +175,8 @@ __global__ __launch_bounds__(256) void kl_alpha0_kernel(const float* __restrict_
   kdiag[o] = (double)Kinv[(int64_t)l * np_ * np_ + (int64_t)p * np_ + p];
 }
 
-// alpha = base + K^-1 u (one wave per row, fp64 accumulation of the fp32 K^-1 row times the fp64 u)
-__global__ __launch_bounds__(256) void kl_alpha_kernel(const float* __restrict__ Kinv, const double* __restrict__ u,
-                                                       int np_, const double* base, double* alpha) {
-  const int l = blockIdx.y, lane = threadIdx.x & 63;
-  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (i >= np_) return;
-  const float* row = Kinv + (int64_t)l * np_ * np_ + (int64_t)i * np_;
-  const double* m = u + (int64_t)l * np_;
-  double acc = 0.0;
-  for (int j = lane * 4; j < np_; j += 256) {
-    const float4 k4 = *reinterpret_cast<const float4*>(row + j);
-    acc += (double)k4.x * m[j] + (double)k4.y * m[j + 1] + (double)k4.z * m[j + 2] + (double)k4.w * m[j + 3];
-  }
-  acc = wave_sum(acc);
-  if (lane == 0) {
-    const int64_t o = (int64_t)l * np_ + i;
-    alpha[o] = base[o] + acc;
-  }
-}
-
-// The same product over the lower 64-tiles only (K^-1 is symmetric; half the bytes): tile (I, J), I >= J,
+// alpha = base + K^-1 u (fp64 accumulation of the fp32 K^-1 times the fp64 u) over the lower 64-tiles only (K^-1
+// is symmetric; half the bytes of a product over whole rows): tile (I, J), I >= J,
 // gives its row sums K_IJ u_J to rows of block I and, off the diagonal, its column sums K_IJ^T u_I to rows
 // of block J, each written once to part[l][other block][row]; kl_alpha_reduce adds them in a fixed order
 // (deterministic).  Grid (G, L), the tiles t = g, g + G, ...; thread (tr, tc) reads rows 4 tr + a,

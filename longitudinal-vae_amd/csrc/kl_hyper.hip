@@ -447,7 +447,7 @@ __device__ inline void hb_split8(const float* a, hb_u32x4& hi, hb_u32x4& mid, hb
 __global__ __launch_bounds__(kHbSlabThreads, 2) void hb_slab_kernel(GramTab tb, HbWs ws, int n, int np_,
                                                                     const float* __restrict__ Kinv,
                                                                     const float* __restrict__ vv,
-                                                                    const double* __restrict__ alpha, int dbg) {
+                                                                    const double* __restrict__ alpha) {
   __shared__ HbDev d;
   // the near window's fp32 columns x V^(1/2) of the tile's rows, column-major [window column][row]: columns
   // 0 .. 63 the previous slab's (a run starting there only), 64 .. 127 this slab's
@@ -640,7 +640,7 @@ __global__ __launch_bounds__(kHbSlabThreads, 2) void hb_slab_kernel(GramTab tb, 
     __syncthreads();
     // (kHbDepth tiles ahead, in flight under this tile's work and the other workgroup's)
     fetch(I + kHbDepth < nt ? I + kHbDepth : nt - 1, p);
-    if (!(dbg & 1) && it0) {
+    if (it0) {
       auto onehot = [&](int g, int b0, int ks) {  // A operand: [bin b0 + (lane & 31)][rows 16 ks + 8 hh + 0..7]
         const unsigned mybin = (unsigned)(b0 + (lane & 31));
         const uint2 rb = *reinterpret_cast<const uint2*>(&rbin[g][16 * ks + 8 * hh]);
@@ -678,38 +678,36 @@ __global__ __launch_bounds__(kHbSlabThreads, 2) void hb_slab_kernel(GramTab tb, 
     }
     // near blocks: C[r][c] += sum over the tile's 64 rows m of Tc[16 bi + r][m] Tc[16 bj + c][m]; lane group lk
     // takes rows 16 lk .. 16 lk + 15 (the k slots of 16 MFMAs: any row order works when A and B share it)
-    if (!(dbg & 2)) {
 #pragma unroll
-      for (int q = 0; q < kHbNQ; ++q) {
-        const int t = w + kHbSlabWaves * q;
-        if (t < nbl) {  // (uniform)
-          const int bb = blist[t], bi = bb >> 3, bj = bb & 7;
-          const float* pa = &Tc[(16 * bi + li) * kHbTP + 16 * lk];
-          const float* pb = &Tc[(16 * bj + li) * kHbTP + 16 * lk];
-          hb_f32x4 a4[4], b4[4];
+    for (int q = 0; q < kHbNQ; ++q) {
+      const int t = w + kHbSlabWaves * q;
+      if (t < nbl) {  // (uniform)
+        const int bb = blist[t], bi = bb >> 3, bj = bb & 7;
+        const float* pa = &Tc[(16 * bi + li) * kHbTP + 16 * lk];
+        const float* pb = &Tc[(16 * bj + li) * kHbTP + 16 * lk];
+        hb_f32x4 a4[4], b4[4];
 #pragma unroll
-          for (int s4 = 0; s4 < 4; ++s4) {
-            a4[s4] = *reinterpret_cast<const hb_f32x4*>(pa + 4 * s4);
-            b4[s4] = *reinterpret_cast<const hb_f32x4*>(pb + 4 * s4);
+        for (int s4 = 0; s4 < 4; ++s4) {
+          a4[s4] = *reinterpret_cast<const hb_f32x4*>(pa + 4 * s4);
+          b4[s4] = *reinterpret_cast<const hb_f32x4*>(pb + 4 * s4);
+        }
+        bi_f32x4 x0 = {0.f, 0.f, 0.f, 0.f}, x1 = {0.f, 0.f, 0.f, 0.f};  // (two chains: half the dependency)
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4) {
+          x0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[s4][0], b4[s4][0], x0, 0, 0, 0);
+          x1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[s4][1], b4[s4][1], x1, 0, 0, 0);
+          x0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[s4][2], b4[s4][2], x0, 0, 0, 0);
+          x1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[s4][3], b4[s4][3], x1, 0, 0, 0);
+        }
+        nac[q] += x0 + x1;
+        if (fold_now) {  // fold into the fp64 blocks: element e = C[4 lk + e][li]
+          double* nb = Ns + t * 256 + (4 * lk) * 16 + li;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            if (fold_first) nb[e * 16] = (double)nac[q][e];
+            else unsafeAtomicAdd(nb + e * 16, (double)nac[q][e]);
           }
-          bi_f32x4 x0 = {0.f, 0.f, 0.f, 0.f}, x1 = {0.f, 0.f, 0.f, 0.f};  // (two chains: half the dependency)
-#pragma unroll
-          for (int s4 = 0; s4 < 4; ++s4) {
-            x0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[s4][0], b4[s4][0], x0, 0, 0, 0);
-            x1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[s4][1], b4[s4][1], x1, 0, 0, 0);
-            x0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[s4][2], b4[s4][2], x0, 0, 0, 0);
-            x1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[s4][3], b4[s4][3], x1, 0, 0, 0);
-          }
-          nac[q] += x0 + x1;
-          if (fold_now) {  // fold into the fp64 blocks: element e = C[4 lk + e][li]
-            double* nb = Ns + t * 256 + (4 * lk) * 16 + li;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              if (fold_first) nb[e * 16] = (double)nac[q][e];
-              else unsafeAtomicAdd(nb + e * 16, (double)nac[q][e]);
-            }
-            nac[q] = bi_f32x4{0.f, 0.f, 0.f, 0.f};
-          }
+          nac[q] = bi_f32x4{0.f, 0.f, 0.f, 0.f};
         }
       }
     }
@@ -780,22 +778,20 @@ __global__ __launch_bounds__(kHbSlabThreads, 2) void hb_slab_kernel(GramTab tb, 
   double nacc[kHbNear];
 #pragma unroll
   for (int k = 0; k < kHbNear; ++k) nacc[k] = 0.0;
-  if (!(dbg & 2)) {
-    for (unsigned long long rm = runends; rm; rm &= rm - 1) {
-      const int e = __builtin_ctzll(rm), s0 = rstart[e], len = e + 1 - (s0 - J0);
-      for (int pq = tid; pq < len * len; pq += kHbSlabThreads) {
-        const int wi = s0 - J0 + kHbT + pq / len, wj = s0 - J0 + kHbT + pq % len;  // window columns
-        const int lo_ = min(wi, wj), hi_ = max(wi, wj);
-        const int t = blkid[((hi_ >> 4) << 3) | (lo_ >> 4)];
-        const double sv = t >= 0 ? Ns[t * 256 + (hi_ & 15) * 16 + (lo_ & 15)] : 0.0;  // (t >= 0: <= 24 blocks)
-        const unsigned c = hb_pair_code(ckey[wi], ckey[wj], catbits, tb.ng);
-        const int cb8 = (int)(c & 0xffu) * kTabR;
+  for (unsigned long long rm = runends; rm; rm &= rm - 1) {
+    const int e = __builtin_ctzll(rm), s0 = rstart[e], len = e + 1 - (s0 - J0);
+    for (int pq = tid; pq < len * len; pq += kHbSlabThreads) {
+      const int wi = s0 - J0 + kHbT + pq / len, wj = s0 - J0 + kHbT + pq % len;  // window columns
+      const int lo_ = min(wi, wj), hi_ = max(wi, wj);
+      const int t = blkid[((hi_ >> 4) << 3) | (lo_ >> 4)];
+      const double sv = t >= 0 ? Ns[t * 256 + (hi_ & 15) * 16 + (lo_ & 15)] : 0.0;  // (t >= 0: <= 24 blocks)
+      const unsigned c = hb_pair_code(ckey[wi], ckey[wj], catbits, tb.ng);
+      const int cb8 = (int)(c & 0xffu) * kTabR;
 #pragma unroll
-        for (int k2 = 0; k2 < kHbNear; ++k2) {
-          if (k2 >= nnear) break;
-          const int g = sgrp[k2];
-          nacc[k2] += sv * (double)tab[k2 * tstride + cb8 + (int)((c >> (8 * (g + 1))) & 0xffu)];
-        }
+      for (int k2 = 0; k2 < kHbNear; ++k2) {
+        if (k2 >= nnear) break;
+        const int g = sgrp[k2];
+        nacc[k2] += sv * (double)tab[k2 * tstride + cb8 + (int)((c >> (8 * (g + 1))) & 0xffu)];
       }
     }
   }
@@ -839,7 +835,7 @@ __global__ __launch_bounds__(256) void hb_sum_kernel(HbWs ws, int np_) {
 __global__ __launch_bounds__(256) void hb_final_kernel(GramTab tb, HbWs ws, int n, int np_,
                                                        const double* __restrict__ alpha,
                                                        const double* __restrict__ kdiag, double* __restrict__ part,
-                                                       int G, int dbg) {
+                                                       int G) {
   __shared__ HbDev d;
   __shared__ double Gb[kHbBins2];   // (Q - M - a a^T) / 2 per far bin pair
   __shared__ double raw[kBwdSlotsHb];
@@ -879,7 +875,7 @@ __global__ __launch_bounds__(256) void hb_final_kernel(GramTab tb, HbWs ws, int 
   }
   const int tstride = (1 << tb.nbits) * kTabR;
   // far slots: sum over the bin pairs of the slot's binning
-  for (int k = 0; k < ((dbg & 16) ? 0 : tb.pbeg[tb.ng]); ++k) {
+  for (int k = 0; k < tb.pbeg[tb.ng]; ++k) {
     const int p = tb.porder[k], r = tb.pcomp[p], g = d.cbin[r];
     if (g < 0) continue;  // (uniform) near
     const int nb = d.bn[g], grp = d.bgrp[g], W = grp >= 0 ? d.wrng[grp] : 1;
@@ -919,11 +915,6 @@ __global__ __launch_bounds__(256) void hb_final_kernel(GramTab tb, HbWs ws, int 
 // ------------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------------
-static int hb_dbg() {  // (timing only: LVAE_HB_DBG bits skip the slab pass's parts -- wrong results)
-  const char* v = getenv("LVAE_HB_DBG");
-  return v ? atoi(v) : 0;
-}
-
 static int hb_enabled() {  // (read per call: A/B runs and tests switch it inside one process)
   const char* v = getenv("LVAE_KL_HYPER");
   return !v || atoi(v) != 0;
@@ -981,10 +972,10 @@ int kl_hyper_bwd(const lvae_kernel_spec* spec, const double* x, int ldx, int n, 
   hb_near_kernel<<<dim3(nt, L), 256, ndyn, st>>>(tb, ws, n, np_, Kinv, alpha);
   {
     ProfScope ps(LVAE_PH_HB_SLAB, st);
-    hb_slab_kernel<<<dim3(nt, L), kHbSlabThreads, sdyn, st>>>(tb, ws, n, np_, Kinv, v, alpha, hb_dbg());
+    hb_slab_kernel<<<dim3(nt, L), kHbSlabThreads, sdyn, st>>>(tb, ws, n, np_, Kinv, v, alpha);
   }
   hb_sum_kernel<<<dim3((2 * kHbBins2 + kHbTail + 255) / 256, L), 256, 0, st>>>(ws, np_);
-  hb_final_kernel<<<L, 256, tabb, st>>>(tb, ws, n, np_, alpha, kdiag, part, G, hb_dbg());
+  hb_final_kernel<<<L, 256, tabb, st>>>(tb, ws, n, np_, alpha, kdiag, part, G);
   LVAE_CHECK_LAUNCH();
   return 0;
 }

@@ -1,9 +1,9 @@
 // pv_lds.hpp -- device helpers of the 256 x 256 pivot-block kernels (one 1024-thread workgroup per
-// latent dim, the 36 lower 32 x 32 blocks of the block in LDS): shared by the block sweep
-// (spd_sweep.hip) and the blocked Cholesky inverse (chol_inv.hip).  Blocked Cholesky panels as rank-1
-// steps inside v_mfma_f32_32x32x2f32 accumulators, the triangular inverse of a 32 x 32 factor, x3
-// f16-split block products straight from LDS, and an x3 tile GEMM from global fp16 planes staged
-// through the pivot's LDS.
+// latent dim, the 36 lower 32 x 32 blocks of the block in LDS) of the blocked Cholesky inverse and potrf
+// (chol_inv.hip, potrf.hip; first written for the block sweep, spd_sweep.hip, last held by commit 97b7453).
+// Blocked Cholesky panels as rank-1 steps inside v_mfma_f32_32x32x2f32 accumulators, the triangular inverse
+// of a 32 x 32 factor, x3 f16-split block products straight from LDS, and an x3 tile GEMM from global fp16
+// planes staged through the pivot's LDS.
 #pragma once
 #include "mfma_x3.hpp"
 #include "x3_dma.hpp"
@@ -95,53 +95,6 @@ __device__ inline void pv_mma3(pv_f32x16& acc, const float* X, const float* Y, f
   acc += t * (sgn / (sX * sY));
 }
 
-// As pv_mma3 on blocks already split IN PLACE (pv_pack_blocks: each fp32 word replaced by the packed
-// fp16 pair (hi | lo << 16) of x s): a fragment is 8 LDS words regrouped by v_perm_b32 into its hi and
-// lo halves (1 VALU per element instead of 5).
-typedef unsigned int pv_u32x4 __attribute__((ext_vector_type(4)));
-template <bool TX, bool TY>
-__device__ inline void pv_mma3p(pv_f32x16& acc, const float* X, const float* Y, float sX, float sY, int rl, int hh) {
-  pv_f32x16 t = {};
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    unsigned wa[8], wb[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int k = 16 * s + 8 * hh + j;
-      wa[j] = __float_as_uint(TX ? X[k * kPvL + rl] : X[rl * kPvL + k]);
-      wb[j] = __float_as_uint(TY ? Y[k * kPvL + rl] : Y[rl * kPvL + k]);
-    }
-    pv_u32x4 ah, al, bh, bl;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      ah[q] = __builtin_amdgcn_perm(wa[2 * q + 1], wa[2 * q], 0x05040100u);
-      al[q] = __builtin_amdgcn_perm(wa[2 * q + 1], wa[2 * q], 0x07060302u);
-      bh[q] = __builtin_amdgcn_perm(wb[2 * q + 1], wb[2 * q], 0x05040100u);
-      bl[q] = __builtin_amdgcn_perm(wb[2 * q + 1], wb[2 * q], 0x07060302u);
-    }
-    const x3_half8 aH = __builtin_bit_cast(x3_half8, ah), aL = __builtin_bit_cast(x3_half8, al);
-    const x3_half8 bH = __builtin_bit_cast(x3_half8, bh), bL = __builtin_bit_cast(x3_half8, bl);
-    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(aL, bH, t, 0, 0, 0);
-    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(aH, bL, t, 0, 0, 0);
-    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(aH, bH, t, 0, 0, 0);
-  }
-  acc += t * (1.0f / (sX * sY));
-}
-
-// every element of the 36 LDS blocks x -> the packed fp16 pair (hi | lo << 16) of x bsc[block], then a
-// barrier (the blocks are read only through pv_mma3p afterwards, until overwritten)
-__device__ inline void pv_pack_blocks(float* lf, const float* bsc) {
-  for (int e = threadIdx.x; e < kPvBlocks * 1024; e += 1024) {
-    const int n = e >> 10, r = (e >> 5) & 31, c = e & 31;
-    float* p = lf + n * kPvBlk + r * kPvL + c;
-    const float y = *p * bsc[n];
-    const _Float16 h = (_Float16)y, lo = (_Float16)(y - (float)h);
-    *p = __uint_as_float((unsigned)__builtin_bit_cast(unsigned short, h) |
-                         ((unsigned)__builtin_bit_cast(unsigned short, lo) << 16));
-  }
-  __syncthreads();
-}
-
 // bsc[n] = x3_scale(max |block n|) for the 36 lower blocks in LDS (wave w: blocks w, w + 16, w + 32),
 // then a barrier
 __device__ inline void pv_block_scales(const float* lf, float* bsc, int w, int lane, int rl, int hh) {
@@ -168,51 +121,6 @@ __device__ inline void pv_block_scales(const float* lf, float* bsc, int w, int l
 __device__ inline int pv_hh(int r) { return (r >> 2) & 1; }            // half holding row r
 __device__ inline int pv_e(int r) { return (r & 3) | ((r >> 3) << 2); }  // its element
 
-// The Cholesky panel q, by waves 0 .. 7-q (wave w: row block i = q + w):
-//   every wave factors the diagonal block X = A_qq in its own accumulator, X -= u u^T / d_p (u = row
-//   p of X: the Schur complement step; L_qq[:, p] = u / sqrt d_p), and wave w > 0 applies the same
-//   steps to Bt = A_iq^T (Bt -= u b^T / d_p, b = row p of Bt = A'_iq[:, p]; L_iq[:, p] = b / sqrt d_p)
-// so the panel needs no L_qq^-1 and the whole panel is 32 steps deep.  Wave 0 writes L_qq (zero
-// upper part), waves > 0 their L_iq, into LDS; wave 0 also returns sum log d_p and the first
-// non-positive pivot.
-__device__ inline void pv_panel(float* lf, int q, int w, int lane, double& ld, int& bad) {
-  const int rl = lane & 31, hh = lane >> 5, i = q + w;
-  float* Dq = pv_blk(lf, q, q);
-  float* Bi = pv_blk(lf, i, q);
-  pv_f32x16 X, Bt;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) {
-    const int r = pv_row(e, hh);
-    X[e] = r >= rl ? Dq[r * kPvL + rl] : Dq[rl * kPvL + r];
-    Bt[e] = (w > 0) ? Bi[rl * kPvL + r] : 0.0f;
-  }
-  float dp = 0.f;  // lane p: pivot d_p
-  __syncthreads();  // every panel wave has its copy of A_qq before wave 0 overwrites it with L_qq
-#pragma unroll
-  for (int p = 0; p < 32; ++p) {
-    const int ep = pv_e(p), hp = pv_hh(p);
-    const float d = pv_rl(X[ep], p + 32 * hp);
-    const float id = __builtin_amdgcn_rcpf(d), is = __builtin_amdgcn_rsqf(d);
-    const bool mine = (hh == hp);
-    const float u = (mine && rl >= p) ? X[ep] : 0.0f;
-    if (w > 0) {
-      const float bp = mine ? Bt[ep] : 0.0f;
-      if (mine) Bi[rl * kPvL + p] = bp * is;
-      Bt = __builtin_amdgcn_mfma_f32_32x32x2f32(-u, bp * id, Bt, 0, 0, 0);
-    } else {
-      if (mine) Dq[rl * kPvL + p] = u * is;
-      if (lane == p) dp = d;
-    }
-    X = __builtin_amdgcn_mfma_f32_32x32x2f32(-u, u * id, X, 0, 0, 0);
-  }
-  if (w == 0) {
-    const double lv = (lane < 32) ? log((double)dp) : 0.0;
-    ld += wave_sum(lv);
-    const unsigned long long nb = __ballot(lane < 32 && !(dp > 0.0f && isfinite(dp)));
-    if (nb) bad = min(bad, 32 * q + (int)__builtin_ctzll(nb));
-  }
-}
-
 // the value v of lane (rl, h) in every lane (rl, .): v_permlane32_swap of v with itself gives the lower
 // half's values in both halves (first result) and the upper half's (second)
 __device__ inline float pv_from_half(float v, int h) {
@@ -220,7 +128,14 @@ __device__ inline float pv_from_half(float v, int h) {
   return __uint_as_float(h ? r[1] : r[0]);
 }
 
-// pv_panel with TWO elimination steps per MFMA: rows p and p+1 (p even) sit in the same half of the
+// The Cholesky panel q, by waves 0 .. 7-q (wave w: row block i = q + w):
+//   every wave factors the diagonal block X = A_qq in its own accumulator, X -= u u^T / d_p (u = row
+//   p of X: the Schur complement step; L_qq[:, p] = u / sqrt d_p), and wave w > 0 applies the same
+//   steps to Bt = A_iq^T (Bt -= u b^T / d_p, b = row p of Bt = A'_iq[:, p]; L_iq[:, p] = b / sqrt d_p)
+// so the panel needs no L_qq^-1 and the whole panel is 32 steps deep.  Wave 0 writes L_qq (zero
+// upper part), waves > 0 their L_iq, into LDS; wave 0 also returns sum log d_p and the first
+// non-positive pivot.
+// With TWO elimination steps per MFMA: rows p and p+1 (p even) sit in the same half of the
 // accumulator lanes, so step p+1's vectors follow from step p's by one FMA per lane
 //   u1 = X[p+1, :] - X[p, p+1] u0 / d_p,   d_{p+1} = X[p+1, p+1] - X[p, p+1]^2 / d_p   (b1 likewise)
 // and the MFMA carries step p in k-slot h(p) and step p+1 in the other one (its operands moved across

@@ -1,5 +1,5 @@
-// side_stream.hpp -- the one high-priority side stream (per device) on which the blocked inverses
-// (spd_sweep.hip, chol_inv.hip) run their critical chain of pivot-block kernels beside the bulk updates,
+// side_stream.hpp -- the one high-priority side stream (per device) on which the blocked inverse
+// (chol_inv.hip) runs its critical chain of pivot-block kernels beside the bulk updates,
 // and the early stream the caller may LEND (lvae_set_early_stream), on which chol_inv.hip starts the part of
 // trtri that needs only the first block columns beside potrf's pivot-bound tail.  The library creates no
 // second stream of its own: a process here has 4 hardware queues, and a fifth stream of the step serialises

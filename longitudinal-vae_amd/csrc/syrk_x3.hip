@@ -96,7 +96,7 @@ __global__ __launch_bounds__(512) void syrk_c16_kernel(const _Float16* __restric
   }
 }
 
-// CUs the S GEMM leaves free when its tiles outnumber the chip (LVAE_SYRK_RESERVE, default below): the
+// CUs the S GEMM leaves free when its tiles outnumber the chip (LVAE_SYRK_RESERVE, compile-time, 0 = none): the
 // exact KL's backward runs the S GEMM on the caller's stream while the encoder backward runs on the ConvVAE
 // stream; with one 160 KB-LDS workgroup on every CU those small kernels wait for whole S-GEMM tiles
 static int syrk_grid(int nwg) {
@@ -107,7 +107,7 @@ static int syrk_grid(int nwg) {
     cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount
                                                                                                 : 256;
   }
-  static const int reserve = getenv("LVAE_SYRK_RESERVE") ? atoi(getenv("LVAE_SYRK_RESERVE")) : LVAE_SYRK_RESERVE;
+  constexpr int reserve = LVAE_SYRK_RESERVE;
   if (reserve <= 0 || nwg <= cus) return nwg;
   const int g = (cus - reserve) / 8 * 8;
   return g >= 8 ? g : nwg;

@@ -460,21 +460,23 @@ __global__ __launch_bounds__(256) void wgrad_sum_kernel(const float* __restrict_
 // gradient: gx[ci][a][b] = sum_{co, ky, kx} g0[co][a + 1 - ky][b + 1 - kx] W[co][ci][ky][kx], g0 the routed
 // full-resolution gradient (gy at each window's argmax where y > 0, 0 elsewhere).  One block per image, one
 // thread per output pixel with all CI input channels in registers (pairs: packed fp32 FMAs).  g0 is formed in
-// LDS with a zero border straight from (gy, y, idx) -- never written to HBM -- CC channels per stage (a
-// smaller LDS stage: more blocks per CU); the 9 taps of a co are read from LDS once for the CI channels, and
-// W's addresses are uniform across the block (scalar loads).  Replaces relu_maxpool2_bwd's full-resolution
-// write plus MIOpen's backward-data conv and its NCHW <-> NHWC transposes.
+// LDS with a zero border straight from (gy, y, idx) -- never written to HBM -- all C channels in one stage
+// (at the headline shape 243-256 us vs 257-269 with 16-channel stages and 268-278 with 8: a smaller stage's
+// extra blocks per CU do not pay for its extra barriers; profiles/r5_conv_dgrad_ab.txt); the 9 taps of a co are
+// read from LDS once for the CI channels, and W's addresses are uniform across the block (scalar loads).
+// Replaces relu_maxpool2_bwd's full-resolution write plus MIOpen's backward-data conv and its NCHW <-> NHWC
+// transposes.
 template <int CI>
 __global__ __launch_bounds__(1024) void conv3x3_pool_dgrad_kernel(const float* __restrict__ gy,
                                                                   const float* __restrict__ y,
                                                                   const uint8_t* __restrict__ idx,
                                                                   const float* __restrict__ w, int C, int Ho, int Wo,
-                                                                  int CC, float* __restrict__ gx) {
+                                                                  float* __restrict__ gx) {
   extern __shared__ float sm[];
   const int H = 2 * Ho, W = 2 * Wo, Wp = W + 2, HWp = (H + 2) * Wp, P = Ho * Wo;
   const int t = threadIdx.x, nthr = blockDim.x;
   const int64_t n = blockIdx.x;
-  for (int e = t; e < CC * HWp; e += nthr) sm[e] = 0.f;  // (the border stays zero: each stage rewrites the interior)
+  for (int e = t; e < C * HWp; e += nthr) sm[e] = 0.f;  // (the border stays zero: only the interior is rewritten)
   const int64_t b0 = n * C * P;
   const bool act = t < H * W;
   const int a = t / W, b = t % W;
@@ -483,37 +485,34 @@ __global__ __launch_bounds__(1024) void conv3x3_pool_dgrad_kernel(const float* _
   for (int c = 0; c < CI / 2; ++c) acc[c] = vo_f32x2{0.f, 0.f};
   // tap (ky, kx) of output (a, b) reads g0 at padded (a + 2 - ky, b + 2 - kx)
   const float* g0 = sm + a * Wp + b;
-  for (int c0 = 0; c0 < C; c0 += CC) {
-    const int cc = min(CC, C - c0);
-    __syncthreads();  // the previous stage's reads (and the zeroing) are done
-    for (int e = t; e < cc * P; e += nthr) {
-      const int c = e / P, r = e % P, i = r / Wo, j = r % Wo;
-      const int64_t s = b0 + (int64_t)c0 * P + e;
-      const float yv = y[s], gv = gy[s];
-      const int k = idx[s];
-      const float g = yv <= 0.f ? 0.f : gv;
-      float* q = sm + c * HWp + (2 * i + 1) * Wp + 2 * j + 1;
-      q[0] = k == 0 ? g : 0.f;
-      q[1] = k == 1 ? g : 0.f;
-      q[Wp] = k == 2 ? g : 0.f;
-      q[Wp + 1] = k == 3 ? g : 0.f;
-    }
-    __syncthreads();
-    if (act) {
-      for (int co = 0; co < cc; ++co) {
-        const float* gc = g0 + co * HWp;
-        const float* wc = w + (int64_t)(c0 + co) * CI * 9;
-        float gt[9];
+  __syncthreads();  // the zeroing is done
+  for (int e = t; e < C * P; e += nthr) {
+    const int c = e / P, r = e % P, i = r / Wo, j = r % Wo;
+    const int64_t s = b0 + e;
+    const float yv = y[s], gv = gy[s];
+    const int k = idx[s];
+    const float g = yv <= 0.f ? 0.f : gv;
+    float* q = sm + c * HWp + (2 * i + 1) * Wp + 2 * j + 1;
+    q[0] = k == 0 ? g : 0.f;
+    q[1] = k == 1 ? g : 0.f;
+    q[Wp] = k == 2 ? g : 0.f;
+    q[Wp + 1] = k == 3 ? g : 0.f;
+  }
+  __syncthreads();
+  if (act) {
+    for (int co = 0; co < C; ++co) {
+      const float* gc = g0 + co * HWp;
+      const float* wc = w + (int64_t)co * CI * 9;
+      float gt[9];
 #pragma unroll
-        for (int k = 0; k < 9; ++k) gt[k] = gc[(2 - k / 3) * Wp + 2 - k % 3];
+      for (int k = 0; k < 9; ++k) gt[k] = gc[(2 - k / 3) * Wp + 2 - k % 3];
 #pragma unroll
-        for (int k = 0; k < 9; ++k) {
-          const vo_f32x2 g2{gt[k], gt[k]};
+      for (int k = 0; k < 9; ++k) {
+        const vo_f32x2 g2{gt[k], gt[k]};
 #pragma unroll
-          for (int c = 0; c < CI / 2; ++c) {
-            const vo_f32x2 w2{wc[(2 * c) * 9 + k], wc[(2 * c + 1) * 9 + k]};
-            acc[c] = __builtin_elementwise_fma(g2, w2, acc[c]);
-          }
+        for (int c = 0; c < CI / 2; ++c) {
+          const vo_f32x2 w2{wc[(2 * c) * 9 + k], wc[(2 * c + 1) * 9 + k]};
+          acc[c] = __builtin_elementwise_fma(g2, w2, acc[c]);
         }
       }
     }
@@ -1308,15 +1307,8 @@ static size_t conv3x3_pool_wgrad_lds(int C, int Cin, int H, int W) {
   return sizeof(float) * (stage > 2560 ? stage : 2560);
 }
 
-// images per block of conv3x3_pool_wgrad_kernel: imgs_per_block, or LVAE_WGRAD_PER (A/B runs; read once, so the
-// workspace size query and the launch agree)
-static int wgrad_per(int N) {
-  static const int v = getenv("LVAE_WGRAD_PER") ? atoi(getenv("LVAE_WGRAD_PER")) : 0;
-  return v > 0 ? v : imgs_per_block(N);
-}
-
 // the second encoder conv's shape takes the dense f32-MFMA form (LVAE_WGRAD_MFMA=0: the sparse VALU form; read
-// once, so the workspace size query and the launch agree): 4 partial rows per block of 2 wgrad_per images
+// once, so the workspace size query and the launch agree): 4 partial rows per block of 2 imgs_per_block images
 static bool wgrad_mfma(int C, int Cin, int H, int W) {
   static const bool on = !getenv("LVAE_WGRAD_MFMA") || atoi(getenv("LVAE_WGRAD_MFMA")) != 0;
   return on && Cin == 16 && C == 32 && H == 18 && W == 18;
@@ -1324,7 +1316,7 @@ static bool wgrad_mfma(int C, int Cin, int H, int W) {
 
 size_t lvae_conv3x3_pool_wgrad_workspace_size(int N, int C, int Cin) {
   if (N <= 0 || C <= 0 || Cin <= 0) return 0;
-  const size_t rows = (size_t)cdiv(N, wgrad_per(N)), rows2 = 4 * (size_t)cdiv(N, 2 * wgrad_per(N));
+  const size_t rows = (size_t)cdiv(N, imgs_per_block(N)), rows2 = 4 * (size_t)cdiv(N, 2 * imgs_per_block(N));
   // (the MFMA form's rows when the shape can take it: H, W are not arguments here)
   return sizeof(float) * ((size_t)C * Cin * 9 + C) * (wgrad_mfma(C, Cin, 18, 18) && rows2 > rows ? rows2 : rows);
 }
@@ -1343,7 +1335,7 @@ int lvae_conv3x3_pool_wgrad_f32(const float* gy, const float* y, const uint8_t* 
     (void)zero_async(db, sizeof(float) * C, st);
     return 0;
   }
-  const int per = wgrad_per(N), nb = (int)cdiv(N, per), m = Q * 9 + C;
+  const int per = imgs_per_block(N), nb = (int)cdiv(N, per), m = Q * 9 + C;
   float* part = (float*)workspace;
   const int Ho = H / 2, Wo = W / 2;
   // the second encoder conv's shape: the dense f32-MFMA form (LVAE_WGRAD_MFMA=0: the sparse VALU form), twice the
@@ -1366,16 +1358,9 @@ int lvae_conv3x3_pool_wgrad_f32(const float* gy, const float* y, const uint8_t* 
   return 0;
 }
 
-// channels per LDS stage of conv3x3_pool_dgrad_kernel: LVAE_DGRAD_CC (A/B runs), default 0 = all C in one stage
-// (at the headline shape 243-256 us vs 257-269 with 16-channel stages and 268-278 with 8: the smaller stage's
-// extra blocks per CU do not pay for its extra barriers; profiles/r5_conv_dgrad_ab.txt)
-static int dgrad_cc(int C) {
-  static const int v = getenv("LVAE_DGRAD_CC") ? atoi(getenv("LVAE_DGRAD_CC")) : 0;
-  return v <= 0 || v > C ? C : v;
-}
-
+// the VALU dgrad kernels' LDS stage: all C channels of one image's routed gradient with its zero border
 size_t lvae_conv3x3_pool_dgrad_lds(int C, int H, int W) {
-  return sizeof(float) * (size_t)dgrad_cc(C) * (H + 2) * (W + 2);
+  return sizeof(float) * (size_t)C * (H + 2) * (W + 2);
 }
 
 int lvae_conv3x3_pool_dgrad_f32(const float* gy, const float* y, const uint8_t* idx, const float* w, int N, int C,
@@ -1395,13 +1380,12 @@ int lvae_conv3x3_pool_dgrad_f32(const float* gy, const float* y, const uint8_t* 
   if (mfma && C == 32 && H == 18 && W == 18) {
     const int per = N >= 4096 ? 8 : N >= 2048 ? 4 : N >= 1024 ? 2 : 1;
     conv3x3_pool_dgrad_mfma_kernel<<<cdiv(N, per), 256, 0, (hipStream_t)stream>>>(gy, y, idx, w, N, per, gx);
-  } else if (pair && dgrad_cc(C) == C) {
+  } else if (pair) {
     const int nthr = (int)cdiv((int64_t)H * W / 2, 64) * 64;
     conv3x3_pool_dgrad2_kernel<16><<<N, nthr, lds, (hipStream_t)stream>>>(gy, y, idx, w, C, H / 2, W / 2, gx);
   } else {
     const int nthr = (int)cdiv((int64_t)H * W, 64) * 64;
-    conv3x3_pool_dgrad_kernel<16><<<N, nthr, lds, (hipStream_t)stream>>>(gy, y, idx, w, C, H / 2, W / 2,
-                                                                         dgrad_cc(C), gx);
+    conv3x3_pool_dgrad_kernel<16><<<N, nthr, lds, (hipStream_t)stream>>>(gy, y, idx, w, C, H / 2, W / 2, gx);
   }
   LVAE_CHECK_LAUNCH();
   return 0;

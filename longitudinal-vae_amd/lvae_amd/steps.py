@@ -34,20 +34,10 @@ def bwd_thread_ctx():
     return torch.autograd.set_multithreading_enabled(False) if _BWD_ON_CALLER else contextlib.nullcontext()
 
 
-def _graph_vae_default():
-    # opt-in (LVAE_GRAPH_VAE=1): measured SLOWER on ROCm 7 -- the ConvVAE's graph replays on its stream held
-    # back the other streams' kernels (rank share of 8 GPUs 3.8 -> 10.9 ms per step, headline 11.7 -> 16.6 ms)
-    import os
-    return os.environ.get("LVAE_GRAPH_VAE", "0") == "1"
-
-
 class ClosedStep:
     def __init__(self, vae, kernel, likelihood, optimiser, weight=0.15, loss_function="mse",
-                 constrain_scales=True, grad_hook=None, vae_stream_priority=-1, graph_vae=None):
+                 constrain_scales=True, grad_hook=None, vae_stream_priority=-1):
         self.vae, self.kernel, self.lik, self.opt = vae, kernel, likelihood, optimiser
-        # the ConvVAE as replayed graphs (GraphedConvVAE; opt-in, see _graph_vae_default)
-        from .vae import GraphedConvVAE
-        self.gvae = GraphedConvVAE(vae) if (_graph_vae_default() if graph_vae is None else graph_vae) else None
         self.weight, self.loss_function, self.constrain_scales = weight, loss_function, constrain_scales
         self.grad_hook = grad_hook  # e.g. the data-parallel all-reduce
         # The ConvVAE's stream is created with a high priority by default: its kernels are small and
@@ -80,18 +70,13 @@ class ClosedStep:
             # hyper-parameter half (S GEMM + Gram adjoint, elbo._KLHyperFn).  (Two extra streams at
             # most: the box exposes 4 hardware queues, and the inverse keeps one side stream of its own.)
             main = torch.cuda.current_stream(img.device)
-            capturing = torch.cuda.is_current_stream_capturing()  # (an outer graph capture: the ConvVAE eager)
             vst = self._stream("_vae_stream", img.device)
             vst.wait_stream(main)  # the previous step's updates, before the factorisation is queued
             factor = kl_closed_prefactor(self.kernel, X, self.lik, self.vae.latent_dim, main)
             enc_done = torch.cuda.Event()
             mse_mode = self.loss_function == "mse"
             with torch.cuda.stream(vst):
-                gv = None if capturing else self.gvae
-                if gv is not None:
-                    mu, log_var = gv.encode(img, mask)
-                else:
-                    mu, log_var = self.vae.encode(img)
+                mu, log_var = self.vae.encode(img)
                 enc_done.record(vst)
                 z = self.vae.sample_latent(mu, log_var, eps)
                 # The decoder and the recon loss run from a detached copy of z, and their backward is enqueued
@@ -100,12 +85,9 @@ class ClosedStep:
                 # of behind the KL's host work.  Its dLoss/dz joins the KL's d/d(mu, logvar) in ONE encoder
                 # backward below (the same sums as the single backward over both loss terms).
                 zd = z.detach().requires_grad_()
-                if gv is not None:
-                    recon_loss, nll_loss = gv.decode_loss(zd, img, mask)
-                else:
-                    recon = self.vae.decode(zd)
-                    mse, nll = self.vae.loss_function(recon, img, mask)
-                    recon_loss, nll_loss = mse.sum(), nll.sum()
+                recon = self.vae.decode(zd)
+                mse, nll = self.vae.loss_function(recon, img, mask)
+                recon_loss, nll_loss = mse.sum(), nll.sum()
                 rec_term = recon_loss if mse_mode else nll_loss
                 rec_term.backward()
             factor.wait_enqueued()  # (its launches on `main` all precede the wait below)
@@ -454,8 +436,6 @@ class GraphedStep:
 
     def __init__(self, step, inputs, warmup=3, shared_pool=False, capture_comm=None):
         self.step, self.inputs = step, inputs
-        if getattr(step, "gvae", None) is not None:
-            step.gvae = None  # (the whole step is one graph here: no graphed ConvVAE parts inside the capture)
         comm = getattr(step, "grad_hook", None) is not None or getattr(step, "ng_reduce", None) is not None
         if capture_comm is None:
             capture_comm = _comm_capturable()

@@ -18,7 +18,6 @@ _CONV_DGRAD = os.environ.get("LVAE_CONV_DGRAD", "1") != "0"
 # LVAE_CONV_BWD_FORK=0: that layer's weight-gradient and input-gradient kernels one after the other on the
 # backward's stream instead of side by side (the weight gradient on a side stream, joined before returning)
 _CONV_BWD_FORK = os.environ.get("LVAE_CONV_BWD_FORK", "1") != "0"
-_FORK_UNDER_CAPTURE = os.environ.get("LVAE_FORK_UNDER_CAPTURE", "0") == "1"
 # LVAE_CONV_FUSED=0: the second encoder conv's forward and the first decoder transposed conv (forward and backward)
 # on MIOpen (+ the fused bias / relu / pool passes) instead of the direct HIP kernels (vae_ops.hip)
 _CONV2_FUSED = os.environ.get("LVAE_CONV_FUSED", "1") != "0"
@@ -139,10 +138,10 @@ class _ConvReluMaxPool2(torch.autograd.Function):
             cur = torch.cuda.current_stream(gy.device)
             # (eager only: with this fork inside a HIP graph capture the process segfaults in torch.cuda.graph's
             # capture_end, i.e. in the runtime's hipStreamEndCapture / graph instantiation -- still after r6's
-            # memset fix, so not the memset nodes (profiles/r6_fork_under_capture_segv.log,
-            # LVAE_FORK_UNDER_CAPTURE=1); captured steps keep the one-stream order)
-            side = (_side_stream(gy.device) if dgrad and _CONV_BWD_FORK and (
-                _FORK_UNDER_CAPTURE or not torch.cuda.is_current_stream_capturing()) else None)
+            # memset fix, so not the memset nodes (profiles/r6_fork_under_capture_segv.log); captured steps keep
+            # the one-stream order)
+            side = (_side_stream(gy.device)
+                    if dgrad and _CONV_BWD_FORK and not torch.cuda.is_current_stream_capturing() else None)
             if side is not None:  # (the weight gradient beside the input gradient; joined below)
                 side.wait_stream(cur)
             with torch.cuda.stream(side if side is not None else cur):
@@ -527,68 +526,3 @@ class _ReparamFn(torch.autograd.Function):
 
 def _glue_ok(*ts):
     return all(t.is_cuda and t.dtype == torch.float32 for t in ts)
-
-
-class _EncoderPart(nn.Module):
-    """ConvVAE.encode as a module owning only the encoder's parameters (for make_graphed_callables)."""
-
-    def __init__(self, vae):
-        super().__init__()
-        for n in ("conv1", "conv2", "fc1", "fc21", "fc211", "fc221"):
-            setattr(self, n, getattr(vae, n))
-        self._vae = [vae]
-
-    def forward(self, x):
-        return self._vae[0].encode(x)
-
-
-class _DecoderLossPart(nn.Module):
-    """decode + loss_function summed over images: (sum of per-image MSE, sum of per-image NLL)."""
-
-    def __init__(self, vae):
-        super().__init__()
-        for n in ("fc3", "fc31", "fc4", "deconv1", "deconv2"):
-            setattr(self, n, getattr(vae, n))
-        self._log_vy = vae._log_vy
-        self._vae = [vae]
-
-    def forward(self, z, img, mask):
-        v = self._vae[0]
-        mse, nll = v.loss_function(v.decode(z), img, mask)
-        return mse.sum(), nll.sum()
-
-
-class GraphedConvVAE:
-    """The ConvVAE's encoder and its decoder + recon loss, each replayed as a HIP graph forward and a HIP graph
-    backward (torch.cuda.make_graphed_callables: torch.cuda.CUDAGraph is a hipGraph on ROCm), for the exact-KL
-    step's ConvVAE stream.  Eager, the ConvVAE is ~100 small launches a step, which host overhead paces once
-    the GPU work per launch is small (a rank's share of the images on several GPUs).  The graphs are built on
-    first use for the batch's shapes (and rebuilt when they change); the arithmetic is the eager modules'."""
-
-    def __init__(self, vae, warmup=3):
-        self.vae = vae
-        self.warmup = warmup
-        self._key = None
-        self.enc = self.dec = None
-
-    def _build(self, img, mask):
-        n = img.shape[0]
-        L = self.vae.latent_dim
-        x = img.detach().clone()
-        z = torch.zeros(n, L, device=img.device, dtype=img.dtype, requires_grad=True)
-        m = mask.detach().clone()
-        self.enc, self.dec = torch.cuda.make_graphed_callables(
-            (_EncoderPart(self.vae), _DecoderLossPart(self.vae)), ((x,), (z, x, m)), num_warmup_iters=self.warmup)
-        self._key = (tuple(img.shape), tuple(mask.shape), img.dtype, img.device, self.vae.training)
-
-    def _ensure(self, img, mask):
-        if self._key != (tuple(img.shape), tuple(mask.shape), img.dtype, img.device, self.vae.training):
-            self._build(img, mask)
-
-    def encode(self, img, mask):
-        self._ensure(img, mask)
-        return self.enc(img)
-
-    def decode_loss(self, z, img, mask):
-        self._ensure(img, mask)
-        return self.dec(z, img, mask)

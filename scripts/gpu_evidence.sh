@@ -26,7 +26,7 @@ head -8 $OUT/headline_kernel_stats.txt
 cd $ROOT
 PMC_NAME=ev_$TAG/pmc bash scripts/pmc.sh > $OUT/pmc.log 2>&1 || { tail -20 $OUT/pmc.log; exit 1; }
 NAME=ev_$TAG/mfma bash scripts/gpu_mfma_pmc.sh > $OUT/mfma.log 2>&1 || { tail -20 $OUT/mfma.log; exit 1; }
-MASKS=0 bash scripts/gpu_hbpmc.sh > $OUT/hbpmc.txt 2>&1 || { tail -20 $OUT/hbpmc.txt; exit 1; }
+bash scripts/gpu_hbpmc.sh > $OUT/hbpmc.txt 2>&1 || { tail -20 $OUT/hbpmc.txt; exit 1; }
 # the bench line reads profiles/${TAG}_*: this run's files (the same ones get committed)
 cp $OUT/headline_kernel_stats.csv profiles/${TAG}_headline_kernel_stats.csv
 cp $OUT/headline_kernel_stats.txt profiles/${TAG}_headline_kernel_stats.txt

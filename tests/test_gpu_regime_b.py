@@ -176,7 +176,7 @@ def test_gram_batched_semantics(hip):
     assert rel(got, raw.grad) < 1e-12
 
 
-# (the rounds 1-2 block sweep, spd_sweep.hip, is retired and no longer built: csrc/retired/)
+# (the rounds 1-2 block sweep is gone from the tree)
 INV_KINDS = ["chol"]
 
 
