@@ -521,6 +521,51 @@ int lvae_gp_elbo_bwd_seg_f64(const lvae_kernel_spec* spec0, const lvae_kernel_sp
                              const double* gelbo, double* dy, double* dparams0, double* dparams1, double* dnoise,
                              void* workspace, void* stream);
 
+/* The DUBO conditioned on a frozen prior, for inferring the latents of new subjects (the second half of
+ * variational_inference_optimization, training.py:688-749: kernels, noise, inducing points and the other subjects'
+ * (mu, logv) are fixed; only Pn "free" subjects' latents move).  Per latent dim, with m, l the free rows' mean and
+ * log-variance, Nn = Pn T rows ordered (free subject in free_idx order, t):
+ *   dubo_l(m, l) = c + 1/2 (m^T A m - 2 r^T m + sum_i a_i e^{l_i} - sum_i l_i)
+ *   A = blockdiag(B_p^-1 : p free) - G W^-1 G^T  (G: the free rows of B^-1 K0xz),  a = diag(A),
+ *   r = G W^-1 sum_{p not free} (B_p^-1 K0xz,p)^T m_p,   c = dubo_l(joint batch, m_free = 0, l_free = 0) - 1/2 sum_i a_i
+ * -- the joint lvae_dubo_fwd_seg_f64 value exactly, as a function of the free rows.
+ *
+ * lvae_dubo_cond_state_size: bytes of the state (c, r, a, A and a row-validity mask) for L dims and Pn free
+ *   subjects of T rows; a multiple of 256; 0 if an argument is < 1.  Needs no device.
+ *
+ * lvae_dubo_cond_prepare_f64 READS d, seg_len, x, z, mu, logv, params0, params1, noise exactly as
+ *   lvae_dubo_fwd_seg_f64 on the joint [P, T] batch does (free and fixed subjects in any order), except that the free
+ *   subjects' rows of mu / logv are taken as 0: those rows are never read and may hold anything, NaN included.
+ *   free_idx: device int32 [Pn], strictly increasing subject indices in [0, P).  The host reads neither free_idx nor
+ *   seg_len; the kernels clamp what they read from them: a bad array gives wrong numbers, never an out-of-range
+ *   access.  It WRITES the whole state (overwritten, whatever it held), info [L] (may be NULL; the forward's
+ *   meaning: a dim with a non-zero word has a meaningless state, the other dims are unaffected) and the workspace
+ *   (lvae_dubo_workspace_size(d) bytes: the forward runs in it, and the copies of mu / logv, G and G W^-1 take
+ *   [L, N, M] buffers the forward leaves idle; the matrix products run on the fp64 matrix cores).  With seg_len the
+ *   padding rows and columns of A and the padding entries of a and r are exact 0.
+ *   Return codes, in this order, before any launch (nothing is written): -1 / -2 / -3: as lvae_dubo_fwd_f64, -3 also
+ *   for Pn < 1 or Pn > P; -4: workspace NULL or not 256-byte aligned; -5: state NULL or not 256-byte aligned;
+ *   -6: free_idx NULL.  0 = ok.
+ *
+ * lvae_dubo_cond_eval_f64 READS the state (never written: several evals may share it) and m, logv [Pn*T, L] fp64
+ *   row-major in the state's row order, g [L] cotangents (device; NULL = ones).  Padding rows of m / logv are never
+ *   read.  It WRITES (overwrites) dubo [L], the values; dm = g_l (A m - r) and dlogv = g_l / 2 (a e^l - 1)
+ *   [Pn*T, L], exact 0 on the padding rows.  One launch for Nn <= 256; beyond that the rows split over workgroups of
+ *   256 rows whose partial sums are added in a fixed order by a second launch (they pass through dlogv, which that
+ *   launch then overwrites: dlogv must not alias an input).  L, Pn, T must be those of the state's prepare.
+ *   Return codes, in this order, before any launch: -3: L, Pn or T < 1; -5: state NULL or not 256-byte aligned;
+ *   -7: m, logv, dubo, dm or dlogv NULL.  0 = ok.
+ * Both calls: kernel launches only, on the caller's stream; nothing is allocated; no atomics: the same inputs give
+ * the same bits on every call.                                                                            */
+size_t lvae_dubo_cond_state_size(int L, int Pn, int T);
+int lvae_dubo_cond_prepare_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, const lvae_dubo_dims* d,
+                               const int32_t* seg_len, int Pn, const int32_t* free_idx, const double* x,
+                               const double* z, const double* mu, const double* logv, const double* params0,
+                               const double* params1, const double* noise, void* state, int32_t* info,
+                               void* workspace, void* stream);
+int lvae_dubo_cond_eval_f64(int L, int Pn, int T, const void* state, const double* m, const double* logv,
+                            const double* g, double* dubo, double* dm, double* dlogv, void* stream);
+
 /* Learnable inducing points: the gradient of the three inducing-point bounds with respect to z [L, M, Q] (the
  * reference gets it from autograd once LVAE.py:204-208, 269 / training.py:349 are uncommented).  Each bound's
  * backward leaves the cotangents of X = k0(x, z) [L, N, M] and of Kz = k0(z, z) + eps I [L, M, M] in its

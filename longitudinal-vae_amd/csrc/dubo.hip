@@ -22,60 +22,16 @@
 // trace of dnoise do not see: F U^T + U F^T -> 2 F U^T.)
 // (the Grams and their adjoints, the argument check, W's inverse, the info merge and the blocks of the subject walk
 // that gp_elbo.hip's has too: gp_bound.hpp / gp_bound.hip; the workspace carving: common.hpp; the subject kernel
-// itself: bound_subject.hpp)
+// itself: bound_subject.hpp; the workspace's layout, which dubo_cond.hip reads too: dubo_ws.hpp)
 // Subjects of varying length (lvae_dubo_*_seg_f64, seg [P] valid rows of a [P, T] padded layout): the Grams are
 // masked after bound_grams_fwd (padding rows of X and K0_p zero, B_p the identity there: gp_bound.hpp), every kernel
 // that reads mu / logv skips the padding rows, N becomes sum_p seg[p], and the adjoint's outputs and the cotangents
 // GB / GK0 are zero on the padding.  seg == NULL is the uniform call, launch for launch.
 #include "bound_subject.hpp"
+#include "dubo_ws.hpp"
 
 namespace lvae {
 namespace {
-
-constexpr int kDuboScal = 8;   // scalar slots per dim: m.iB.m, diag(iB).v, iB.K0, sum logv, sum log|B_p|
-
-// doubles of one (dim, group) partial: Q and R lower tiles in accumulator order, p [128], the scalars
-inline int64_t dubo_part_stride(int M) { return (int64_t)2 * bound_tiles(M) * 256 + 128 + kDuboScal; }
-
-// (a null d: all zero, which bound_check answers with -3)
-inline BoundDims dubo_dims(const lvae_dubo_dims* d) {
-  return d ? BoundDims{d->L, d->M, d->P, d->T, d->Q} : BoundDims{};
-}
-
-struct DWs {
-  double *X, *iBK, *U, *UR, *F, *Z, *tNM, *dX;                                    // [L,N,M]
-  double *Kz, *iK, *Q, *R, *W, *iW0, *E, *iW, *iWR, *iWRiW, *iKQ, *iKQiK, *dKz;  // [L,M,M]
-  double *K0st, *Bst, *iB, *VB, *iBDiB, *K0iB, *iBK0iB, *GB, *GK0;               // [L,P,T,T]
-  double *p, *w;                                                                  // [L,M]
-  double *s, *y, *a;                                                              // [L,N]
-  double *ldK, *ldB, *ldW, *epsv, *scal, *part, *gpart;
-  int32_t* info;
-  size_t bytes;
-  DWs(char* base, const lvae_dubo_dims& d) {
-    WsCarve c(base);
-    const size_t L = d.L, M = d.M, N = (size_t)d.P * d.T, TT = (size_t)d.P * d.T * d.T;
-    double** nm[] = {&X, &iBK, &U, &UR, &F, &Z, &tNM, &dX};
-    for (auto q : nm) *q = c.take(L * N * M);
-    double** mm[] = {&Kz, &iK, &Q, &R, &W, &iW0, &E, &iW, &iWR, &iWRiW, &iKQ, &iKQiK, &dKz};
-    for (auto q : mm) *q = c.take(L * M * M);
-    double** tt[] = {&K0st, &Bst, &iB, &VB, &iBDiB, &K0iB, &iBK0iB, &GB, &GK0};
-    for (auto q : tt) *q = c.take(L * TT);
-    p = c.take(L * M);
-    w = c.take(L * M);
-    s = c.take(L * N);
-    y = c.take(L * N);
-    a = c.take(L * N);
-    ldK = c.take(L);
-    ldB = c.take(L * d.P);
-    ldW = c.take(L);
-    epsv = c.take(L);
-    scal = c.take(L * kDuboScal);
-    part = c.take(L * (size_t)bound_groups(d.P) * (size_t)dubo_part_stride(d.M));
-    info = (int32_t*)c.take(L * (2 + (size_t)d.P));
-    gpart = c.take(bound_gram_part_doubles(dubo_dims(&d)));
-    bytes = c.off;
-  }
-};
 
 // The groups' partials in group order: grid (2 nt + 1, L), 256 threads.  Blocks [0, nt): a tile of Q, [nt, 2 nt):
 // of R (mirrored into the upper triangle; a diagonal tile holds both of its halves itself), the last: p, scalars.

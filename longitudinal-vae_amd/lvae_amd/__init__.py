@@ -23,7 +23,8 @@ from .elbo import (HensmanPrior, KL_closed, KL_closed_batched, check_pending, kl
                    set_sync_checks)
 from .predict import batch_predict_varying_T, predict_exact, sample_predictions  # noqa: F401
 from .evaluation import MSE_test, MSE_test_GPapprox  # noqa: F401
-from .gpapprox import (deviance_upper_bound, deviance_upper_bound_batched, deviance_upper_bound_varying_T,  # noqa: F401
-                       elbo, elbo_batched, elbo_varying_T, spd_inverse, subject_layout, validation_dubo)
+from .gpapprox import (DuboCondition, condition_dubo, condition_dubo_varying_T, deviance_upper_bound,  # noqa: F401
+                       deviance_upper_bound_batched, deviance_upper_bound_varying_T, elbo, elbo_batched,
+                       elbo_varying_T, spd_inverse, subject_layout, validation_dubo)
 
 __version__ = "0.1.0"

@@ -156,6 +156,12 @@ SIGNATURES = {
                                         _VP]),
     "lvae_gp_elbo_bwd_seg_f64": (_I32, [_SPEC, _SPEC, _GDIMS, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                         _VP, _VP, _VP]),
+    # the DUBO conditioned on a frozen prior: (L, Pn, T); prepare = the seg forward's arguments with (Pn, free_idx)
+    # after seg_len and state in place of dubo; eval (L, Pn, T, state, m, logv, g, dubo, dm, dlogv, stream)
+    "lvae_dubo_cond_state_size": (_SZ, [_I32, _I32, _I32]),
+    "lvae_dubo_cond_prepare_f64": (_I32, [_SPEC, _SPEC, _DDIMS, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                          _VP, _VP, _VP, _VP]),
+    "lvae_dubo_cond_eval_f64": (_I32, [_I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "lvae_relu_maxpool2_fwd_f32": (_I32, [_VP, _I64, _I32, _I32, _VP, _VP, _VP]),
     "lvae_relu_maxpool2_bwd_f32": (_I32, [_VP, _VP, _VP, _I64, _I32, _I32, _VP, _VP]),
     "lvae_relu_maxpool2_bias_workspace_size": (_SZ, [_I32, _I32]),

@@ -16,6 +16,11 @@ functions stay as they are, as their baseline and comparison.
 Subjects of varying length (an extension: the reference's two bounds reshape to [P, T]): ``subject_layout``,
 ``deviance_upper_bound_varying_T`` and ``elbo_varying_T`` lay the batch out as [P, T_max] and run the same two HIP
 calls with the padding masked out (lvae_dubo_fwd_seg_f64 ... lvae_gp_elbo_bwd_seg_f64).
+
+The latents of new subjects under a frozen prior (training.py:688-749): ``condition_dubo`` /
+``condition_dubo_varying_T`` reduce the joint DUBO of cat(new, train) to a closed form in the new rows
+(lvae_dubo_cond_prepare_f64, once) that ``cond(m_new, log_v_new)`` evaluates with one matvec per dim
+(lvae_dubo_cond_eval_f64, csrc/dubo_cond.hip).
 """
 import math
 
@@ -408,3 +413,133 @@ def elbo_varying_T(latent_dim, covar_module0, covar_module1, likelihoods, train_
         out.append(_GpElboFn.apply(params0, params1, noise, ys, x_pad, zz, spec0, spec1, dims, lay.seg_len))
     res = out[0] if len(out) == 1 else torch.cat(out, 0)
     return res[0] if single else res
+
+
+# ------------------------------------------------------------------------------------------------------
+# the DUBO conditioned on a frozen prior: the latents of new subjects (training.py:688-749)
+# ------------------------------------------------------------------------------------------------------
+class _DuboCondFn(torch.autograd.Function):
+    """dubo [L] of the conditioned bound (lvae_dubo_cond_eval_f64): the forward computes the values and the
+    unit-cotangent gradients in one call, the backward scales them."""
+
+    @staticmethod
+    def forward(ctx, m, logv, cond):
+        lib = _lib.lib()
+        m64, lv64 = _f64(m), _f64(logv)
+        dubo = torch.empty(cond.L, dtype=torch.float64, device=m64.device)
+        dm, dlv = torch.empty_like(m64), torch.empty_like(lv64)
+        rc = lib.lvae_dubo_cond_eval_f64(cond.L, cond.Pn, cond.T, _lib.ptr(cond.state), _lib.ptr(m64), _lib.ptr(lv64),
+                                         None, _lib.ptr(dubo), _lib.ptr(dm), _lib.ptr(dlv), _lib.stream_ptr())
+        _lib.check(rc, "dubo_cond_eval")
+        ctx.save_for_backward(dm, dlv)
+        ctx.dtypes = (m.dtype, logv.dtype)
+        return dubo
+
+    @staticmethod
+    def backward(ctx, gdubo):
+        dm, dlv = ctx.saved_tensors
+        g = gdubo.detach().to(torch.float64).reshape(1, -1)
+        return (dm * g).to(ctx.dtypes[0]), (dlv * g).to(ctx.dtypes[1]), None
+
+
+class DuboCondition:
+    """The joint DUBO as a function of the new subjects' latents alone (``condition_dubo``): ``cond(m_new,
+    log_v_new)`` -> [L] fp64.  ``L``, ``Pn`` (new subjects), ``T`` (rows per subject of the state: T, or the longest
+    subject) and ``Nn`` (the rows the caller passes) are ints; ``state`` is the device buffer
+    lvae_dubo_cond_prepare_f64 filled, owned by this object; ``gather`` (varying length only): the caller's row of
+    every state row."""
+
+    def __init__(self, L, Pn, T, Nn, state, gather=None):
+        self.L, self.Pn, self.T, self.Nn = int(L), int(Pn), int(T), int(Nn)
+        self.state, self.gather = state, gather
+
+    def __call__(self, m_new, log_v_new):
+        if tuple(m_new.shape) != (self.Nn, self.L) or tuple(log_v_new.shape) != (self.Nn, self.L):
+            raise ValueError(f"m_new / log_v_new must be [{self.Nn}, {self.L}]")
+        if self.gather is not None:
+            # (the padding slots repeat a row the kernel never reads; their cotangent is an exact 0)
+            m_new, log_v_new = m_new.index_select(0, self.gather), log_v_new.index_select(0, self.gather)
+        return _DuboCondFn.apply(m_new, log_v_new, self)
+
+
+def _condition(L, spec0, params0, spec1, params1, zz, noise, x, mu, logv, P, T, seg, free_idx, eps):
+    """lvae_dubo_cond_prepare_f64 on the joint [P, T] batch (everything detached); returns (state, Pn)"""
+    lib = _lib.lib()
+    p0, p1, nz, x64, z64, mu64, lv64 = (_f64(params0), _f64(params1), _f64(noise).reshape(-1), _f64(x), _f64(zz),
+                                        _f64(mu), _f64(logv))
+    dev = x64.device
+    dims = _lib.DuboDims(L, int(zz.shape[-2]), int(P), int(T), int(x.shape[-1]), float(eps))
+    Pn = int(free_idx.numel())
+    free = free_idx.to(device=dev, dtype=torch.int32).contiguous()
+    ws = torch.empty(int(lib.lvae_dubo_workspace_size(dims)), dtype=torch.uint8, device=dev)
+    state = torch.empty(int(lib.lvae_dubo_cond_state_size(L, Pn, int(T))), dtype=torch.uint8, device=dev)
+    info = torch.empty(L, dtype=torch.int32, device=dev)
+    rc = lib.lvae_dubo_cond_prepare_f64(spec0, spec1, dims, _lib.ptr(seg), Pn, _lib.ptr(free), _lib.ptr(x64),
+                                        _lib.ptr(z64), _lib.ptr(mu64), _lib.ptr(lv64), _lib.ptr(p0), _lib.ptr(p1),
+                                        _lib.ptr(nz), _lib.ptr(state), _lib.ptr(info), _lib.ptr(ws), _lib.stream_ptr())
+    _lib.check(rc, "dubo_cond_prepare")
+    _check_info(info, "condition_dubo cholesky (10000+col: K0zz, 20000+col: B_st, 30000+col: W)")
+    return state, Pn
+
+
+def _cond_joint(L, x_new, x_train, m_train, log_v_train):
+    if x_new.shape[0] < 1:
+        raise ValueError("x_new has no rows")
+    Nt = x_train.shape[0]
+    if tuple(m_train.shape) != (Nt, L) or tuple(log_v_train.shape) != (Nt, L):
+        raise ValueError(f"m_train / log_v_train must be [{Nt}, {L}]")
+    zeros = torch.zeros(x_new.shape[0], L, dtype=torch.float64, device=x_new.device)
+    x = torch.cat([x_new.detach(), x_train.detach().to(x_new.dtype)], 0)
+    return x, torch.cat([zeros, _f64(m_train)], 0), torch.cat([zeros, _f64(log_v_train)], 0)
+
+
+def condition_dubo(latent_dim, covar_module0, covar_module1, likelihoods, x_new, x_train, m_train, log_v_train, z, T,
+                   eps):
+    """The DUBO of ``cat(new, train)`` with everything but the new subjects' latents frozen (the loss of the second
+    half of variational_inference_optimization, training.py:688-749): returns ``cond`` (a ``DuboCondition``) with
+    ``cond(m_new, log_v_new)`` [L] fp64 equal to ``deviance_upper_bound_batched`` on cat(x_new, x_train),
+    cat(m_new, m_train), cat(log_v_new, log_v_train) with Pn + P subjects of T rows -- values and the gradients
+    with respect to m_new / log_v_new [Pn * T, L], in the caller's dtype.
+
+    THE PRIOR IS FROZEN: nothing flows to the kernels, the noise, z or the training latents, whatever requires
+    grad; they are read once, here.  With them fixed the joint bound is an exact quadratic-plus-exponential form in
+    the new rows (csrc/dubo_cond.hip): this call costs about one DUBO forward (lvae_dubo_cond_prepare_f64), every
+    ``cond(...)`` after it is one symmetric [Pn T, Pn T] matvec per latent dim (lvae_dubo_cond_eval_f64) whose cost
+    no longer depends on the training set or on M.  Modules, likelihoods and z in every form
+    ``deviance_upper_bound_batched`` takes; x_train may have no rows (every subject new)."""
+    L, T = int(latent_dim), int(T)
+    if x_new.shape[0] % T or x_train.shape[0] % T:
+        raise ValueError(f"x_new / x_train must hold whole subjects of T = {T} rows")
+    x, mu, logv = _cond_joint(L, x_new, x_train, m_train, log_v_train)
+    P, Pn = x.shape[0] // T, x_new.shape[0] // T
+    spec0, params0, spec1, params1, zz = _batched_kernels(L, covar_module0, covar_module1, z, x, P, T)
+    noise = _dubo_noise(likelihoods, L).to(x.device)
+    state, _ = _condition(L, spec0, params0, spec1, params1, zz, noise, x, mu, logv, P, T, None,
+                          torch.arange(Pn, dtype=torch.int32), eps)
+    return DuboCondition(L, Pn, T, Pn * T, state)
+
+
+def condition_dubo_varying_T(latent_dim, covar_module0, covar_module1, likelihoods, x_new, x_train, m_train,
+                             log_v_train, z, id_covariate, eps):
+    """``condition_dubo`` for subjects of varying length: ``cond(m_new, log_v_new)`` equals
+    ``deviance_upper_bound_varying_T`` on the joint batch, values and gradients in the caller's row order.  The
+    subjects are the distinct values of the id column; the joint ``subject_layout`` is built here.  The prior is
+    frozen as in ``condition_dubo``.  ValueError when a new id also occurs in x_train, or a subject has more than 128
+    rows."""
+    L = int(latent_dim)
+    x, mu, logv = _cond_joint(L, x_new, x_train, m_train, log_v_train)
+    n_new = x_new.shape[0]
+    ids_new = torch.unique(x_new[:, id_covariate].detach())
+    if x_train.shape[0] and bool(torch.isin(ids_new, x_train[:, id_covariate].detach().to(ids_new.dtype)).any()):
+        raise ValueError("condition_dubo_varying_T: a new subject's id also occurs in x_train")
+    spec0, params0, spec1, params1, zz = _batched_kernels(L, covar_module0, covar_module1, z, x, None, None)
+    lay = _varying_layout(x, id_covariate, None, x.shape[0], "condition_dubo_varying_T")
+    # subjects stand in torch.unique order of the ids: the new ones keep that order among themselves
+    ids_all = torch.unique(x[:, id_covariate])
+    free_idx = torch.nonzero(torch.isin(ids_all, ids_new.to(ids_all.device))).reshape(-1)
+    noise = _dubo_noise(likelihoods, L).to(x.device)
+    state, Pn = _condition(L, spec0, params0, spec1, params1, zz, noise, x.index_select(0, lay.gather),
+                           mu.index_select(0, lay.gather), logv.index_select(0, lay.gather), lay.P, lay.T_max,
+                           lay.seg_len, free_idx, eps)
+    gather = lay.gather.reshape(lay.P, lay.T_max).index_select(0, free_idx.to(lay.gather.device)).reshape(-1)
+    return DuboCondition(L, Pn, lay.T_max, n_new, state, gather.contiguous())

@@ -4,6 +4,8 @@ ClosedStep   : standard_training with type_KL='closed' (training.py:484-592)
 HensmanStep  : hensman_training batch body incl. the natural-gradient update (training.py:91-135)
 DuboStep     : standard_training with type_KL='GPapprox_closed' (training.py:499-575), full batch
 ElboStep     : standard_training with type_KL='GPapprox' (training.py:499-575), full batch, num_samples draws
+LatentInferenceStep / infer_new_subjects : the latents of new subjects under a frozen model, the second half of
+               variational_inference_optimization (training.py:688-749)
 GraphedStep  : either step replayed as HIP graphs (torch.cuda.CUDAGraph is a hipGraph on ROCm)
 
 Both steps return detached device scalars; callers read them when they choose (the reference's
@@ -405,6 +407,62 @@ class ElboStep:
         self.communicate()
         self.apply()
         return out
+
+
+class LatentInferenceStep:
+    """One iteration of the second half of variational_inference_optimization (training.py:713-746): the new
+    subjects' ``mu`` / ``log_var`` (fp64 nn.Parameters [Nn, L], the reference's dtype) are the only things
+    optimised.  sample_latent, decode and loss_function of the frozen ``vae`` (anything with these three and
+    ``encode``; the parameters are cast to the images' dtype for it), the GP term from ``cond`` (a
+    gpapprox.DuboCondition: the joint DUBO of cat(new, train) as a function of the new rows alone),
+    gp = sum_l dubo_l / L in BOTH branches as the reference does in this function (DuboStep's 'nll' does not divide):
+    recon + weight * gp ('mse') or nll + gp ('nll').  Only mu.grad and log_var.grad are assigned: the network's
+    parameters and their .grad stay exactly as they were.  ``apply`` is the optimiser step."""
+
+    def __init__(self, vae, cond, mu, log_var, optimiser, weight=0.15, loss_function="mse"):
+        if loss_function not in ("mse", "nll"):
+            raise ValueError(f"loss_function must be 'mse' or 'nll', got {loss_function!r}")
+        self.vae, self.cond, self.mu, self.log_var, self.opt = vae, cond, mu, log_var, optimiser
+        self.weight, self.loss_function = weight, loss_function
+
+    def forward_backward(self, img, mask, eps=None):
+        self.opt.zero_grad(set_to_none=True)
+        mu, log_var = self.mu, self.log_var
+        Z = self.vae.sample_latent(mu.to(img.dtype), log_var.to(img.dtype), eps)
+        mse, nll = self.vae.loss_function(self.vae.decode(Z), img, mask)
+        recon_loss, nll_loss = mse.sum(), nll.sum()
+        gp = self.cond(mu, log_var).sum() / self.cond.L
+        net = recon_loss + self.weight * gp if self.loss_function == "mse" else nll_loss + gp
+        mu.grad, log_var.grad = torch.autograd.grad(net, (mu, log_var))
+        return net.detach(), recon_loss.detach(), nll_loss.detach(), gp.detach()
+
+    def apply(self):
+        self.opt.step()
+
+    def __call__(self, img, mask, eps=None):
+        out = self.forward_backward(img, mask, eps)
+        self.apply()
+        return out
+
+
+def infer_new_subjects(vae, cond, img, mask, iters=1000, lr=1e-3, weight=0.15, loss_function="mse", eps=None):
+    """The latents of new subjects (training.py:688-749): (mu, log_var) start at ``vae.encode(img)``, Adam(lr) over
+    the two runs ``iters`` LatentInferenceSteps.  eps: optional [iters, Nn, L] draws (else drawn per iteration).
+    Returns (mu, log_var, losses): the fp64 nn.Parameters and losses [iters, 4] fp64 on the device, the columns
+    (net, recon, nll, gp) -- no host sync inside the loop."""
+    with torch.no_grad():
+        mu0, lv0 = vae.encode(img)
+    mu = torch.nn.Parameter(mu0.detach().to(torch.float64).clone())
+    log_var = torch.nn.Parameter(lv0.detach().to(torch.float64).clone())
+    if eps is not None and tuple(eps.shape) != (iters,) + tuple(mu.shape):
+        raise ValueError(f"eps must be [{iters}, {mu.shape[0]}, {mu.shape[1]}], got {tuple(eps.shape)}")
+    opt = torch.optim.Adam([{"params": mu}, {"params": log_var}], lr=lr)
+    step = LatentInferenceStep(vae, cond, mu, log_var, opt, weight, loss_function)
+    losses = torch.empty(iters, 4, dtype=torch.float64, device=mu.device)
+    for it in range(iters):
+        out = step(img, mask, None if eps is None else eps[it])
+        losses[it] = torch.stack([o.reshape(()).to(torch.float64) for o in out])
+    return mu, log_var, losses
 
 
 def _comm_capturable():
