@@ -665,6 +665,62 @@ int lvae_deconv4s2_relu_bwd_f32(const float* gy, const float* y, const float* x,
                                 int Cout, int Hi, int Wi, float* dx, float* dw, float* db, void* workspace,
                                 void* stream);
 
+/* The MLP encoder / decoder (SimpleVAE, VAE.py:165-253; selected by type_nnet='simple', LVAE.py:59-70, 141-143),
+ * fp32, each half one launch forward with its weights resident in LDS and every activation kept on chip, products
+ * on v_mfma_f32_32x32x2_f32 (exact f32).  Weights are nn.Linear's [out, in] row-major; H1 = 300 and H2 = 30 are
+ * the reference's hidden widths.  Deterministic: fixed-order sums, no float atomics.  relu: v < 0 -> 0, NaN kept;
+ * a NaN in a row of the input stays in that row.
+ * Return codes of the four compute entries, checked in this order before any launch: -1 (a required pointer NULL)
+ * -2 (B, D, H1, H2 or L < 1) -3 (H1 != 300, H2 != 30 or L > 32) -4 (D beyond the LDS bound) -5 (workspace not
+ * 256-byte aligned); 0 = ok, LVAE_ERR_LAUNCH on a HIP error.
+ * lvae_mlp_vae_lds_bytes: the largest dynamic LDS any of the kernels asks for, 0 for a shape -2 / -3 reject:
+ *   4 max(332 (D|1) + 19984 + 64 L,  302 D + 62 (L|1) + 20254) bytes (encoder / decoder forward);
+ * lvae_mlp_vae_fused_ok: 1 when that is within the 160 KiB of a CU, i.e. for L <= 32 exactly D <= 57 (and for
+ * every 1 <= D <= 48, 1 <= L <= 32).  Host only, like the two workspace sizes and lvae_mlp_wgrad_splits.
+ * More than 64 KB of dynamic LDS is asked for with hipFuncSetAttribute, per kernel and per device: each compute entry
+ * remembers (one atomic bit per device id < 64) on which devices it has asked and asks again on a new one, so any
+ * device of the process may be current; the first call per device should come before a stream capture.          */
+int lvae_mlp_vae_fused_ok(int D, int H1, int H2, int L);
+size_t lvae_mlp_vae_lds_bytes(int D, int H1, int H2, int L);
+/* encode (VAE.py:215-224): x [B, D] -> h1 = relu(fc1 x) [B, 300], h2 = relu(fc21 h1) [B, 30], mu = fc211 h2,
+ * log_var = fc221 h2 [B, L].  h1 / h2 are the backward's saved activations and may be NULL (no_grad).           */
+int lvae_mlp_enc_fwd_f32(const float* x, const float* w1, const float* b1, const float* w21, const float* b21,
+                         const float* w211, const float* b211, const float* w221, const float* b221, int B, int D,
+                         int H1, int H2, int L, float* h1, float* h2, float* mu, float* log_var, void* stream);
+/* decode (VAE.py:226-235): h3 = relu(fc3 z) [B, 30], h4 = relu(fc31 h3) [B, 300], recon = sigmoid(fc4 h4) [B, D].
+ * Either z [B, L] is given, or z is NULL and (mu, log_var, eps) are: then z = mu + eps exp(log_var / 2)
+ * (sample_latent, VAE.py:237-248) is formed in the same launch and written to z_out [B, L] (required then; not
+ * touched when z is given).  h3 / h4 may be NULL (no_grad).                                                    */
+int lvae_mlp_dec_fwd_f32(const float* z, const float* mu, const float* log_var, const float* eps, const float* w3,
+                         const float* b3, const float* w31, const float* b31, const float* w4, const float* b4, int B,
+                         int D, int H1, int H2, int L, float* z_out, float* h3, float* h4, float* recon,
+                         void* stream);
+/* The decoder's autograd backward (of VAE.py:226-248) from g_recon = dLoss/drecon and the saved recon, h4, h3, z:
+ * all weight and bias gradients and g_z [B, L].  Sampled form (log_var and eps given, as saved by the forward's
+ * sampled form): g_mu = g_z and g_log_var = g_z eps exp(log_var / 2) / 2 are written (both required; g_z may then
+ * be NULL); otherwise log_var, eps, g_mu and g_log_var are all NULL and g_z is required.  Two launches: the
+ * activation-gradient chain, then every dW = g^T h and db at once (dw3 .. db4 all NULL: a frozen decoder, the second
+ * launch is skipped; some but not all NULL is -1); rows are summed in order, and for
+ * lvae_mlp_wgrad_splits(B) >= 2 (B > 512) in that many chunks whose partial tiles are added in chunk order.
+ * workspace: lvae_mlp_dec_bwd_workspace_size(B, D, L) bytes, 256-byte aligned.                                  */
+size_t lvae_mlp_dec_bwd_workspace_size(int B, int D, int L);
+int lvae_mlp_dec_bwd_f32(const float* g_recon, const float* recon, const float* h4, const float* h3, const float* z,
+                         const float* log_var, const float* eps, const float* w3, const float* w31, const float* w4,
+                         int B, int D, int H1, int H2, int L, float* dw3, float* db3, float* dw31, float* db31,
+                         float* dw4, float* db4, float* g_z, float* g_mu, float* g_log_var, void* workspace,
+                         void* stream);
+/* The encoder's autograd backward (of VAE.py:215-224) from g_mu, g_log_var [B, L] (where the GP bound's gradient
+ * arrives) and the saved x, h1, h2: all weight and bias gradients; the input gets none.  Two launches, as above.
+ * workspace: lvae_mlp_enc_bwd_workspace_size(B, D, L) bytes, 256-byte aligned.                                  */
+size_t lvae_mlp_enc_bwd_workspace_size(int B, int D, int L);
+int lvae_mlp_enc_bwd_f32(const float* g_mu, const float* g_log_var, const float* x, const float* h1, const float* h2,
+                         const float* w21, const float* w211, const float* w221, int B, int D, int H1, int H2, int L,
+                         float* dw1, float* db1, float* dw21, float* db21, float* dw211, float* db211, float* dw221,
+                         float* db221, void* workspace, void* stream);
+/* The number of row chunks the two backward entries cut a batch of B rows into (1 up to 512 rows, then
+ * min(64, ceil(B / 512))); 0 for B < 1.                                                                         */
+int lvae_mlp_wgrad_splits(int B);
+
 /* GP posterior mean of the latents at test covariates (utils.py:115-211 batch_predict_varying_T,
  * called by MSE_test_GPapprox, model_test.py:85-143).  Prediction set laid out [P, T] by subject
  * (seg_len [P] valid rows each; padding rows of x are any finite covariates, of mu must be 0),

@@ -2,7 +2,8 @@
 
 The GP-prior ELBO term (additive-kernel Gram, blocked Cholesky / inverse, KL reductions, the
 Hensman SVI bound and its natural-gradient update) runs in hand-written HIP kernels for gfx950
-behind the C ABI of include/lvae_hip.h; the conv encoder/decoder runs on PyTorch-ROCm.
+behind the C ABI of include/lvae_hip.h; so do the conv and MLP encoder / decoder's layers (vae.py), with PyTorch-ROCm
+for the remaining GEMMs.
 """
 import os
 
@@ -23,6 +24,8 @@ from .elbo import (HensmanPrior, KL_closed, KL_closed_batched, check_pending, kl
                    set_sync_checks)
 from .predict import batch_predict_varying_T, predict_exact, sample_predictions  # noqa: F401
 from .evaluation import MSE_test, MSE_test_GPapprox  # noqa: F401
+from .vae import ConvVAE, SimpleVAE  # noqa: F401
+from .data import HealthMNISTDataset, HealthMNISTDatasetConv, PhysionetDataset  # noqa: F401
 from .gpapprox import (DuboCondition, condition_dubo, condition_dubo_varying_T, deviance_upper_bound,  # noqa: F401
                        deviance_upper_bound_batched, deviance_upper_bound_varying_T, elbo, elbo_batched,
                        elbo_varying_T, spd_inverse, subject_layout, validation_dubo)

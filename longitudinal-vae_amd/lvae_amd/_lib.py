@@ -178,6 +178,16 @@ SIGNATURES = {
     "lvae_deconv4s2_relu_bwd_workspace_size": (_SZ, [_I32, _I32, _I32]),
     "lvae_deconv4s2_relu_bwd_f32": (_I32, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP,
                                             _VP]),
+    # the MLP VAE (mlp_vae.hip): pointers, then (B, D, H1, H2, L), then outputs (, workspace), stream
+    "lvae_mlp_vae_fused_ok": (_I32, [_I32, _I32, _I32, _I32]),
+    "lvae_mlp_vae_lds_bytes": (_SZ, [_I32, _I32, _I32, _I32]),
+    "lvae_mlp_wgrad_splits": (_I32, [_I32]),
+    "lvae_mlp_enc_fwd_f32": (_I32, [_VP] * 9 + [_I32] * 5 + [_VP] * 5),
+    "lvae_mlp_dec_fwd_f32": (_I32, [_VP] * 10 + [_I32] * 5 + [_VP] * 5),
+    "lvae_mlp_dec_bwd_workspace_size": (_SZ, [_I32, _I32, _I32]),
+    "lvae_mlp_dec_bwd_f32": (_I32, [_VP] * 10 + [_I32] * 5 + [_VP] * 11),
+    "lvae_mlp_enc_bwd_workspace_size": (_SZ, [_I32, _I32, _I32]),
+    "lvae_mlp_enc_bwd_f32": (_I32, [_VP] * 8 + [_I32] * 5 + [_VP] * 10),
     "lvae_conv3x3_pool_dgrad_lds": (_SZ, [_I32, _I32, _I32]),
     "lvae_conv3x3_pool_dgrad_f32": (_I32, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP]),
     "lvae_spd_inv_chol_scratch_size": (_SZ, [_I32, _I32]),

@@ -96,6 +96,73 @@ class HealthMNISTDatasetConv:
                 "mask": self.masks.index_select(0, idx).reshape(-1, 1, 1296)}
 
 
+class HealthMNISTDataset(HealthMNISTDatasetConv):
+    """HealthMNISTDataset (dataset_def.py:133-169), the flat form the MLP VAE (type_nnet='simple') reads: the same
+    three CSVs, labels and mask as HealthMNISTDatasetConv, the image as one row of 1296 pixels.  ``ds[i]``:
+    {'digit': ToTensor-equivalent [1, 1, 1296] fp32 (the raw [1, 1296] uint8 when transform is None), 'label',
+    'idx', 'mask': [1, 1296] uint8}; ``batch(idx)``: digit [B, 1, 1, 1296] fp32 (= ToTensor + default collate)."""
+
+    def _item(self, i):
+        raw = self.pixels[i].reshape(1, 1296).cpu().numpy()
+        digit = raw if self.transform is None else self.transform(raw)
+        return {"digit": digit, "label": self.labels[i], "idx": i, "mask": self.masks[i].reshape(1, 1296)}
+
+    def batch(self, idx):
+        out = super().batch(idx)
+        out["digit"] = out["digit"].reshape(-1, 1, 1, 1296)
+        return out
+
+
+class PhysionetDataset:
+    """PhysionetDataset (dataset_def.py:8-44), preloaded once into device tensors: an ``.npz`` with data_readings
+    [.., D], outcome_attrib [.., Qa], data_mask [.., D] and outcome_mask [.., Qa], each flattened to rows.
+    ``ds[i]``: {'data': [D] fp32, 'label': [2 Qa] fp32 = cat(outcome_attrib with column 8 - 24, outcome_mask),
+    'idx': i, 'mask': [D] uint8}; ``batch(idx)``: the same keys stacked as one device gather.
+
+    The 24 is subtracted from column 8 once, at load.  The reference subtracts it from its own source array at every
+    access (``label = self.label_source[idx, :]`` is a view, dataset_def.py:34-35), so a row read twice is off by
+    another 24 each time; that defect is not reproduced: every access here returns what the reference returns on
+    its first access of the row."""
+
+    def __init__(self, data_file, root_dir, transform=None, device="cpu"):
+        import os
+        with np.load(os.path.join(root_dir, data_file)) as f:
+            flat = {k: f[k].reshape(-1, f[k].shape[-1]) for k in ("data_readings", "outcome_attrib", "data_mask",
+                                                                  "outcome_mask")}
+        data, attrib = flat["data_readings"], flat["outcome_attrib"].astype(np.float64)
+        if flat["data_mask"].shape != data.shape or flat["outcome_mask"].shape != attrib.shape \
+                or attrib.shape[0] != data.shape[0] or attrib.shape[1] < 9:
+            raise ValueError(f"Physionet arrays disagree: readings {data.shape}, mask {flat['data_mask'].shape}, "
+                             f"attributes {attrib.shape}, their mask {flat['outcome_mask'].shape}")
+        attrib[:, 8] -= 24
+        lab = np.concatenate((attrib, flat["outcome_mask"]), axis=1).astype(np.float32)
+        self.transform = transform
+        self.device = torch.device(device)
+        self.data = torch.from_numpy(data.astype(np.float32)).to(self.device)                 # [N, D] fp32
+        self.masks = torch.from_numpy(flat["data_mask"].astype(np.uint8)).to(self.device)     # [N, D] uint8
+        self.labels = torch.from_numpy(lab).to(self.device)                                   # [N, 2 Qa] fp32
+
+    def __len__(self):
+        return self.data.shape[0]
+
+    def __getitem__(self, key):
+        if isinstance(key, slice):
+            return [self._item(i) for i in range(*key.indices(len(self)))]
+        if isinstance(key, (int, np.integer)):
+            return self._item(int(key))
+        raise TypeError
+
+    def _item(self, i):
+        row = self.data[i]
+        return {"data": row if self.transform is None else self.transform(row), "label": self.labels[i], "idx": i,
+                "mask": self.masks[i]}
+
+    def batch(self, idx):
+        idx = torch.as_tensor(idx, dtype=torch.int64, device=self.device)
+        return {"data": self.data.index_select(0, idx), "label": self.labels.index_select(0, idx), "idx": idx,
+                "mask": self.masks.index_select(0, idx)}
+
+
 class DeviceBatchLoader:
     """Iterates device batches of a preloaded dataset in the order of a batch sampler (any
     iterable of index lists, e.g. BatchSampler(SubjectSampler, P_b*T) or varying_length_batches):

@@ -4,8 +4,9 @@
 ``result_error.csv`` (mean masked MSE of the autoencoder's own reconstruction, and of the decoded GP prediction).
 
 Differences from the reference, none of which changes a result it can produce:
-  * the test set is read through the project's device-resident HealthMNISTDatasetConv and evaluated as one device
-    batch (no DataLoader workers), by the project's fp32 ConvVAE (the reference casts the images to fp64);
+  * the test set is read through the project's device-resident HealthMNISTDatasetConv (type_nnet='conv') or the
+    flat HealthMNISTDataset ('simple', model_test.py:35-40) and evaluated as one device batch (no DataLoader
+    workers), by the project's fp32 ConvVAE / SimpleVAE (the reference casts the images to fp64);
   * MSE_test solves with the Cholesky factor and one refinement step instead of forming K^-1;
   * the "more than 6040 prediction rows" rule draws its 6000 rows from 40..n-1 (model_test.py:60 draws from
     0..n-1 and then adds 40, which can index past the end); an ``rng`` keyword seeds the draw, the default is
@@ -19,7 +20,7 @@ import os
 import numpy as np
 import torch
 
-from .data import HealthMNISTDatasetConv
+from .data import HealthMNISTDataset, HealthMNISTDatasetConv
 from .predict import batch_predict_varying_T, predict_exact
 
 KEEP_ROWS, SAMPLE_ROWS = 40, 6000   # model_test.py:59-61
@@ -39,26 +40,37 @@ def select_prediction_rows(n, rng=None):
     return np.concatenate((np.arange(KEEP_ROWS), r))
 
 
+def check_type_nnet(type_nnet, model):
+    """'conv' (any model, as before 'simple' existed) or 'simple' with a SimpleVAE (VAE.py:294-333); any other
+    type_nnet raises NotImplementedError"""
+    from .vae import SimpleVAE
+    if type_nnet not in ("conv", "simple"):
+        raise NotImplementedError(f"type_nnet must be 'conv' or 'simple', got {type_nnet!r}")
+    if type_nnet == "simple" and not isinstance(model, SimpleVAE):
+        raise TypeError(f"type_nnet='simple' needs a SimpleVAE, got {type(model).__name__}")
+
+
 def _whole_set(dataset, model):
-    """(images, mask [B, 1296], labels [B, 6] fp64) of a device-resident dataset as one batch in the model's dtype"""
+    """(images, mask [B, num_dim], labels [B, Q] fp64) of a device-resident dataset as one batch in the model's
+    dtype; the images are the items' 'digit' or, for PhysionetDataset, 'data'"""
     dtype = next(model.parameters()).dtype
     everything = dataset.batch(torch.arange(len(dataset)))
-    images = everything["digit"].to(dtype)
+    images = everything["digit" if "digit" in everything else "data"].to(dtype)
     return images, everything["mask"].reshape(images.shape[0], -1).to(dtype), everything["label"].to(torch.float64)
 
 
 def _mean_mse(model, recon, images, mask):
-    """The per-image masked MSE of ConvVAE.loss_function, averaged over the images"""
+    """The per-image masked MSE of the model's loss_function, averaged over the images"""
     return float(model.loss_function(recon, images, mask)[0].mean())
 
 
 def _evaluate(files, root, type_nnet, model, out_file, predict):
     """The body the two tests share: the autoencoder's own mean masked MSE over the test set and that of the
     decoded latents ``predict(labels)``, written one per line to ``out_file``."""
-    if type_nnet != "conv":
-        raise NotImplementedError("lvae_amd evaluates the convolutional VAE only (type_nnet='conv')")
+    check_type_nnet(type_nnet, model)
     data_csv, label_csv, mask_csv = files
-    dataset = HealthMNISTDatasetConv(data_csv, label_csv, mask_csv, root, device=next(model.parameters()).device)
+    dataset_cls = HealthMNISTDatasetConv if type_nnet == "conv" else HealthMNISTDataset
+    dataset = dataset_cls(data_csv, label_csv, mask_csv, root, device=next(model.parameters()).device)
     with torch.no_grad():
         images, mask, labels = _whole_set(dataset, model)
         own = _mean_mse(model, model(images)[0], images, mask)
@@ -98,7 +110,8 @@ def MSE_test_GPapprox(csv_file_test_data, csv_file_test_label, test_mask_file, d
 
 
 def VAEtest(test_dataset, nnet_model, type_nnet, id_covariate):
-    """Mean masked MSE of the autoencoder alone over a device-resident dataset (model_test.py:145-167)."""
+    """Mean masked MSE of the autoencoder alone over a device-resident dataset (model_test.py:145-167); either
+    model, ``type_nnet`` is not used."""
     with torch.no_grad():
         images, mask, _ = _whole_set(test_dataset, nnet_model)
         return _mean_mse(nnet_model, nnet_model(images)[0], images, mask)

@@ -462,6 +462,242 @@ class ConvVAE(nn.Module):
         return mse, nll.sum(1)
 
 
+# Rows above which SimpleVAE takes the layered route although the fused kernels fit (None: no gate; the timings of
+# scripts/simple_vae_timing.py, DESIGN.md "MLP VAE"): the default of a model's ``fused_max_rows``
+_MLP_FUSED_MAX_ROWS = None
+
+
+def _mlp_dims(x, w1, w21, w211):
+    return x.shape[0], w1.shape[1], w1.shape[0], w21.shape[0], w211.shape[0]
+
+
+class _MlpEncodeFn(torch.autograd.Function):
+    """(mu, log_var) of SimpleVAE.encode (VAE.py:215-224) in one HIP launch (lvae_mlp_enc_fwd_f32, mlp_vae.hip): the
+    four layers with their weights in LDS; backward: every weight and bias gradient in two launches
+    (lvae_mlp_enc_bwd_f32).  x gets no gradient.  grad_on: torch.is_grad_enabled() at the call (a Function's forward
+    cannot see it, and ctx.needs_input_grad does not: a Parameter needs grad under no_grad too); without it the
+    activations are neither written (NULL h1 / h2) nor saved."""
+
+    @staticmethod
+    def forward(ctx, grad_on, x, w1, b1, w21, b21, w211, b211, w221, b221):
+        from . import _lib
+        lib = _lib.lib()
+        ts = [t.contiguous() for t in (x, w1, b1, w21, b21, w211, b211, w221, b221)]
+        x, w1, w21, w211, w221 = ts[0], ts[1], ts[3], ts[5], ts[7]
+        B, D, H1, H2, L = _mlp_dims(x, w1, w21, w211)
+        train = grad_on and any(ctx.needs_input_grad)
+        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=x.device)
+        h1, h2 = (new(B, H1), new(B, H2)) if train else (None, None)
+        mu, log_var = new(B, L), new(B, L)
+        _lib.check(lib.lvae_mlp_enc_fwd_f32(*(_lib.ptr(t) for t in ts), B, D, H1, H2, L, _lib.ptr(h1), _lib.ptr(h2),
+                                            _lib.ptr(mu), _lib.ptr(log_var), _lib.stream_ptr()), "mlp_enc_fwd")
+        if train:
+            ctx.save_for_backward(x, h1, h2, w1, w21, w211, w221)
+        return mu, log_var
+
+    @staticmethod
+    def backward(ctx, g_mu, g_lv):
+        from . import _lib
+        lib = _lib.lib()
+        x, h1, h2, w1, w21, w211, w221 = ctx.saved_tensors
+        B, D, H1, H2, L = _mlp_dims(x, w1, w21, w211)
+        g_mu, g_lv = g_mu.contiguous(), g_lv.contiguous()
+        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=x.device)
+        dw1, db1, dw21, db21 = new(H1, D), new(H1), new(H2, H1), new(H2)
+        dw211, db211, dw221, db221 = new(L, H2), new(L), new(L, H2), new(L)
+        ws = torch.empty(lib.lvae_mlp_enc_bwd_workspace_size(B, D, L), dtype=torch.uint8, device=x.device)
+        _lib.check(lib.lvae_mlp_enc_bwd_f32(*(_lib.ptr(t) for t in (g_mu, g_lv, x, h1, h2, w21, w211, w221)), B, D, H1,
+                                            H2, L, *(_lib.ptr(t) for t in (dw1, db1, dw21, db21, dw211, db211, dw221,
+                                                                           db221, ws)), _lib.stream_ptr()),
+                   "mlp_enc_bwd")
+        return None, None, dw1, db1, dw21, db21, dw211, db211, dw221, db221
+
+
+def _mlp_dec_fwd(ctx, grad_on, z, mu, log_var, eps, params):
+    """recon of SimpleVAE.decode from z, or from (mu, log_var, eps) with the reparametrisation inside the launch;
+    grad_on as in _MlpEncodeFn (NULL h3 / h4 and nothing saved without it)"""
+    from . import _lib
+    lib = _lib.lib()
+    w3, b3, w31, b31, w4, b4 = (t.contiguous() for t in params)
+    sampled = z is None
+    lat = [t.contiguous() for t in ((mu, log_var, eps) if sampled else (z,))]
+    B, L, H2, H1, D = lat[0].shape[0], w3.shape[1], w3.shape[0], w31.shape[0], w4.shape[0]
+    train = grad_on and any(ctx.needs_input_grad)
+    ctx.wgrad = any(ctx.needs_input_grad[-6:])   # (a frozen decoder: the backward skips the weight-gradient launch)
+    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=w3.device)
+    h3, h4 = (new(B, H2), new(B, H1)) if train else (None, None)
+    z_out = new(B, L) if sampled else None
+    recon = new(B, D)
+    args = [None] + lat if sampled else lat + [None, None, None]
+    _lib.check(lib.lvae_mlp_dec_fwd_f32(*(_lib.ptr(t) for t in args), *(_lib.ptr(t) for t in (w3, b3, w31, b31, w4, b4)),
+                                        B, D, H1, H2, L, _lib.ptr(z_out), _lib.ptr(h3), _lib.ptr(h4), _lib.ptr(recon),
+                                        _lib.stream_ptr()), "mlp_dec_fwd")
+    if train:
+        ctx.save_for_backward(recon, h4, h3, z_out if sampled else lat[0], lat[1] if sampled else None,
+                              lat[2] if sampled else None, w3, w31, w4)
+    return recon
+
+
+def _mlp_dec_bwd(ctx, g_recon):
+    """(g_z or (g_mu, g_log_var), the six weight and bias gradients) in two launches (lvae_mlp_dec_bwd_f32); one, and
+    no weight gradients, when no decoder parameter needs one (LatentInferenceStep on a frozen model)"""
+    from . import _lib
+    lib = _lib.lib()
+    recon, h4, h3, z, log_var, eps, w3, w31, w4 = ctx.saved_tensors
+    sampled = eps is not None
+    B, L, H2, H1, D = z.shape[0], w3.shape[1], w3.shape[0], w31.shape[0], w4.shape[0]
+    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=z.device)
+    dws = (new(H2, L), new(H2), new(H1, H2), new(H1), new(D, H1), new(D)) if ctx.wgrad else (None,) * 6
+    g_z = None if sampled else new(B, L)
+    g_mu, g_lv = (new(B, L), new(B, L)) if sampled else (None, None)
+    ws = torch.empty(lib.lvae_mlp_dec_bwd_workspace_size(B, D, L), dtype=torch.uint8, device=z.device)
+    ins = (g_recon.contiguous(), recon, h4, h3, z, log_var, eps, w3, w31, w4)
+    outs = dws + (g_z, g_mu, g_lv, ws)
+    _lib.check(lib.lvae_mlp_dec_bwd_f32(*(_lib.ptr(t) for t in ins), B, D, H1, H2, L, *(_lib.ptr(t) for t in outs),
+                                        _lib.stream_ptr()), "mlp_dec_bwd")
+    return (None,) + ((g_mu, g_lv, None) if sampled else (g_z,)) + dws
+
+
+class _MlpDecodeFn(torch.autograd.Function):
+    """SimpleVAE.decode (VAE.py:226-235) in one HIP launch (lvae_mlp_dec_fwd_f32); backward: g_z and the weight and
+    bias gradients in two (lvae_mlp_dec_bwd_f32)."""
+
+    @staticmethod
+    def forward(ctx, grad_on, z, w3, b3, w31, b31, w4, b4):
+        return _mlp_dec_fwd(ctx, grad_on, z, None, None, None, (w3, b3, w31, b31, w4, b4))
+
+    @staticmethod
+    def backward(ctx, g_recon):
+        return _mlp_dec_bwd(ctx, g_recon)
+
+
+class _MlpSampleDecodeFn(torch.autograd.Function):
+    """decode(mu + eps exp(log_var / 2)) (VAE.py:246-253) in one HIP launch: the reparametrisation inside the
+    decoder's launch, and its adjoint inside the backward's."""
+
+    @staticmethod
+    def forward(ctx, grad_on, mu, log_var, eps, w3, b3, w31, b31, w4, b4):
+        return _mlp_dec_fwd(ctx, grad_on, None, mu, log_var, eps, (w3, b3, w31, b31, w4, b4))
+
+    @staticmethod
+    def backward(ctx, g_recon):
+        return _mlp_dec_bwd(ctx, g_recon)
+
+
+class SimpleVAE(nn.Module):
+    """The MLP encoder / decoder (VAE.py:165-273, the reference's type_nnet='simple'): the reference's parameter
+    names and shapes, so its state dicts load with strict=True, and ConvVAE's method signatures here, so every step
+    and driver takes either model.  ``x`` is [.., num_dim] (forward views it as (-1, num_dim)).
+
+    Three routes, recorded in ``last_route`` ({'encode': .., 'decode': ..}):
+      'fused'    CUDA fp32 with hidden == (300, 30), a shape lvae_mlp_vae_fused_ok accepts (num_dim <= 57) and, for
+                 the encoder, an input that needs no gradient: each half is one HIP launch with its weights in LDS
+                 (mlp_vae.hip), the backward two per half; in forward() the reparametrisation rides in the decoder's;
+                 under torch.no_grad() the activations the backward would need are not written at all;
+                 ``fused_max_rows`` (None: no gate) sends batches of more rows to the layered route;
+      'layered'  CUDA fp32 otherwise (flat Health-MNIST's 1296 inputs, other hidden widths): linear_act per layer
+                 (hipBLASLt GEMMs + the fused bias / ReLU passes) and torch.sigmoid;
+      'stock'    CPU or fp64: plain torch ops (in fp64 on the CPU, the restatement the GPU tests compare against).
+    All launches go to the caller's stream."""
+
+    def __init__(self, latent_dim, num_dim, vy_init=1.0, vy_fixed=False, hidden=(300, 30)):
+        super().__init__()
+        self.latent_dim = latent_dim
+        self.num_dim = num_dim
+        self.hidden = (int(hidden[0]), int(hidden[1]))
+        if isinstance(vy_init, (int, float)):
+            self._log_vy = nn.Parameter(torch.full((num_dim,), math.log(vy_init - math.exp(-8.0))))
+        else:
+            self._log_vy = nn.Parameter(torch.log(torch.as_tensor(vy_init, dtype=torch.float32) - math.exp(-8.0)))
+        if vy_fixed:
+            self._log_vy.requires_grad_(False)
+        h1, h2 = self.hidden
+        # encoder (VAE.py:192-195)
+        self.fc1 = nn.Linear(num_dim, h1)
+        self.fc21 = nn.Linear(h1, h2)
+        self.fc211 = nn.Linear(h2, latent_dim)
+        self.fc221 = nn.Linear(h2, latent_dim)
+        # decoder (VAE.py:198-200)
+        self.fc3 = nn.Linear(latent_dim, h2)
+        self.fc31 = nn.Linear(h2, h1)
+        self.fc4 = nn.Linear(h1, num_dim)
+        self.register_buffer("min_log_vy", torch.full((1,), -8.0))
+        self.last_route = {}
+        self.fused_max_rows = _MLP_FUSED_MAX_ROWS
+        self._fused_shape = None
+
+    @property
+    def vy(self):
+        return torch.exp(self.min_log_vy + F.softplus(self._log_vy - self.min_log_vy))
+
+    @vy.setter
+    def vy(self, vy):
+        vy = torch.as_tensor(vy, dtype=self._log_vy.dtype, device=self._log_vy.device)
+        assert torch.min(vy) >= 0.0005, "Smallest allowed value for vy is 0.0005"
+        with torch.no_grad():
+            self._log_vy.copy_(torch.log(vy - torch.exp(self.min_log_vy)))
+
+    def _route(self, half, t, layers):
+        route = "stock"
+        if _f32_cuda(t, *(p for fc in layers for p in (fc.weight, fc.bias))) and t.dim() == 2:
+            if self._fused_shape is None:
+                from . import _lib
+                self._fused_shape = bool(_lib.load().lvae_mlp_vae_fused_ok(self.num_dim, *self.hidden,
+                                                                           self.latent_dim))
+            gated = self.fused_max_rows is not None and t.shape[0] > self.fused_max_rows
+            fused = self._fused_shape and not gated and t.shape[0] > 0 and not (half == "encode" and t.requires_grad)
+            route = "fused" if fused else "layered"
+        self.last_route[half] = route
+        return route
+
+    @staticmethod
+    def _wb(layers):
+        return [p for fc in layers for p in (fc.weight, fc.bias)]
+
+    def encode(self, x):
+        layers = (self.fc1, self.fc21, self.fc211, self.fc221)
+        if x.dim() != 2:  # (a collated flat image [B, 1, 1, num_dim]: the rows, as forward() views them)
+            x = x.reshape(-1, self.num_dim)
+        route = self._route("encode", x, layers)
+        if route == "fused":
+            return _MlpEncodeFn.apply(torch.is_grad_enabled(), x, *self._wb(layers))
+        if route == "layered":
+            h2 = linear_act(self.fc21, linear_act(self.fc1, x, True), True)
+            return linear_act(self.fc211, h2, False), linear_act(self.fc221, h2, False)
+        h2 = F.relu(self.fc21(F.relu(self.fc1(x))))
+        return self.fc211(h2), self.fc221(h2)
+
+    def decode(self, z):
+        layers = (self.fc3, self.fc31, self.fc4)
+        route = self._route("decode", z, layers)
+        if route == "fused":
+            return _MlpDecodeFn.apply(torch.is_grad_enabled(), z, *self._wb(layers))
+        if route == "layered":
+            return torch.sigmoid(linear_act(self.fc4, linear_act(self.fc31, linear_act(self.fc3, z, True), True), False))
+        return torch.sigmoid(self.fc4(F.relu(self.fc31(F.relu(self.fc3(z))))))
+
+    def sample_latent(self, mu, log_var, eps=None):
+        if eps is None:
+            eps = torch.randn_like(log_var)
+        if _glue_ok(mu, log_var, eps) and mu.shape == log_var.shape == eps.shape:
+            return _ReparamFn.apply(mu, log_var, eps)  # (glue.hip: one launch each way)
+        return mu + eps * torch.exp(0.5 * log_var)
+
+    def forward(self, x, eps=None):
+        mu, log_var = self.encode(x.reshape(-1, self.num_dim))
+        layers = (self.fc3, self.fc31, self.fc4)
+        if self._route("decode", mu, layers) == "fused":
+            if eps is None:
+                eps = torch.randn_like(log_var)
+            if _glue_ok(eps) and eps.shape == mu.shape:
+                recon = _MlpSampleDecodeFn.apply(torch.is_grad_enabled(), mu, log_var, eps, *self._wb(layers))
+                return recon, mu, log_var
+        return self.decode(self.sample_latent(mu, log_var, eps)), mu, log_var
+
+    # (per-row masked MSE, per-row NLL) -- VAE.py:255-273, the formula of ConvVAE's (lvae_vae_loss_*, glue.hip)
+    loss_function = ConvVAE.loss_function
+
+
 class _VaeLossFn(torch.autograd.Function):
     """(mse [B], nll [B]) of ConvVAE.loss_function in one HIP launch (glue.hip); backward: d recon and
     d log_vy in one launch + the column sum of the d log_vy partials."""

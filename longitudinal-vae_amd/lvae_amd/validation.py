@@ -2,8 +2,9 @@
 signature and return value (the net loss as a Python float), and ``validation_dubo`` (validation.py:8-68).
 
 Differences from the reference, none of which changes a result it can produce:
-  * the dataset is the project's device-resident HealthMNISTDatasetConv, evaluated as one device batch (no
-    DataLoader workers) by the project's fp32 ConvVAE (the reference casts the images to fp64), as
+  * the dataset is one of the project's device-resident datasets (lvae_amd.data: HealthMNISTDatasetConv for
+    type_nnet='conv'; the flat HealthMNISTDataset or PhysionetDataset for 'simple'), evaluated as one device batch
+    (no DataLoader workers) by the project's fp32 ConvVAE / SimpleVAE (the reference casts the data to fp64), as
     evaluation._evaluate does;
   * ``T`` is used as passed -- the reference overwrites it with 16 (validation.py:95);
   * 'GPapprox_closed' is ONE batched call for all latent dims (deviance_upper_bound_batched), for per-dim module
@@ -17,7 +18,7 @@ lists only: with batched modules its GP term is 0 (validation.py:157-163 has no 
 """
 import torch
 
-from .evaluation import _whole_set
+from .evaluation import _whole_set, check_type_nnet
 from .gpapprox import (deviance_upper_bound_batched, deviance_upper_bound_varying_T, elbo, elbo_varying_T,  # noqa: F401
                        subject_layout, validation_dubo)
 
@@ -29,8 +30,7 @@ def validate(nnet_model, type_nnet, dataset, type_KL, num_samples, latent_dim, c
     ('GPapprox_closed') or minus the sampled ELBO ('GPapprox') summed over the latent dims.  ``train_mu``,
     ``train_x`` are accepted and not used, as in the reference, and so is ``id_covariate`` unless ``varying_T``:
     then the subjects are the distinct values of the labels' column ``id_covariate`` and ``T`` is ignored."""
-    if type_nnet != "conv":
-        raise NotImplementedError("lvae_amd validates the convolutional VAE only (type_nnet='conv')")
+    check_type_nnet(type_nnet, nnet_model)
     assert type_KL == 'GPapprox_closed' or type_KL == 'GPapprox'
     with torch.no_grad():
         images, mask, labels = _whole_set(dataset, nnet_model)
