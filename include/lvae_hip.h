@@ -810,6 +810,85 @@ int lvae_predict_var_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* 
                          const double* noise, double eps, double* out, double* out_var, int add_noise, int32_t* info,
                          void* workspace, void* stream);
 
+/* Joint predictive covariance of each group of test rows under the inducing-point predictor (and, optionally, the
+ * mean), fp64: per latent dim l and group g of n_g test rows, in lvae_predict_var_f64's model and notation (the
+ * subscript g selects the group's columns of its [rows, Nt] matrices),
+ *   Sigma_g = K0zX*_g^T Q_g + k1(x*_g, x*_g) - (Q_g^T W_g + E_g^T Q_g + C_g^T D_g) + W_g^T V_g      [n_g, n_g]
+ * = k~**_g - k~*_g^T Sigma^-1 k~*_g, the raw difference; add_noise = 1 adds noise_l to its diagonal.  Its diagonal
+ * is lvae_predict_var_f64's formula; for a group of an absent subject C, D and E are zero and the k1 term stays.
+ * The covariance between rows of different groups is not zero (the shared components couple subjects) and is not
+ * returned.  Arguments as lvae_predict_var_f64 with, in place of out_var: n_max, the rows of the largest group
+ * (1 .. 128 when n_groups > 0), and out_cov [L, n_groups, n_max, n_max], block (l, g) at
+ * out_cov[(l*n_groups + g)*n_max*n_max], row i of a block the group's i-th row (test_x's row group_start[g] + i);
+ * rows of a group beyond n_max are left out.  Padding rows and columns (i or j >= n_g) carry the identity, and a
+ * block is symmetric bit for bit ([i][j] and [j][i] are one computed value).  Route: lvae_predict_var_f64's
+ * launches up to V (the same buffers, no second pass over the prediction set), one kernel that fills the blocks
+ * with the identity, and one fp64 matrix-core kernel with a workgroup per (dim, group, 16 x 16 tile on or below the
+ * diagonal) that accumulates the five products over M and T in index order and adds k1(x*_i, x*_j) through the
+ * spec.  O((M + T) n_g^2) flops per dim and group on top of the variance's.  out, info, Nt == 0 as
+ * lvae_predict_var_f64; with Nt == 0 or n_groups == 0 out_cov is untouched.  workspace:
+ * lvae_predict_cov_workspace_size(L, M, P, T, Nt) bytes (= lvae_predict_var_workspace_size's).
+ * Return codes (before any launch): -1 -6 -8 -9 -10 -11 -12 -13 -15 -17 -20 as lvae_predict_var_f64; -3: also
+ * L > 65535; -14: n_groups outside 0 .. 65535; -16: n_groups > 0 and out_cov NULL; -18: n_groups > 0 and n_max
+ * outside 1 .. 128 (a group above the cap).  0 = ok.                                                          */
+size_t lvae_predict_cov_workspace_size(int L, int M, int P, int T, int Nt);
+int lvae_predict_cov_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, int L, int M, int Q, int P,
+                         int T, const int32_t* seg_len, const int32_t* include, const double* x, const double* mu,
+                         const double* z, int Nt, const double* test_x, int n_groups, const int32_t* group_subject,
+                         const int32_t* group_start, int n_max, const double* params0, const double* params1,
+                         const double* noise, double eps, double* out, double* out_cov, int add_noise, int32_t* info,
+                         void* workspace, void* stream);
+
+/* Joint predictive covariance of each group of test rows under the exact-GP predictor (and, optionally, the mean),
+ * fp64.  With K_l = k_l(x, x) + noise_l I = L_l L_l^T and V = L_l^-1 k_l(x, tx_g):
+ *   Sigma_g = k_l(tx_g, tx_g) - V^T V   (+ noise_l on the diagonal when add_noise = 1)              [n_g, n_g]
+ * The covariance between rows of different groups is not returned.  Arguments as lvae_predict_exact_var_f64 with,
+ * in place of out_var / ld_var: the groups, group g = the test rows [group_start[g], group_start[g + 1]) -- n_groups
+ * + 1 entries in HOST memory (the chunks are cut at group boundaries on the host), group_start[0] = 0,
+ * group_start[n_groups] = nt, every group of 1 .. n_max rows, n_max in 1 .. 128; and out_cov [L, n_groups, n_max,
+ * n_max] laid out, padded and symmetric as lvae_predict_cov_f64's.  Route: the factor (and mean) as
+ * lvae_predict_exact_f64; then per chunk of whole groups with at most c = min(chunk, nt) test rows the panel
+ * k(x, tx_chunk) [L, n, c] and lvae_trsm_f64 in place as lvae_predict_exact_var_f64; V^T V on the fp64 matrix cores
+ * with the n prediction rows cut into slabs of 512 whose partial 16 x 16 tiles go to the workspace and are added in
+ * slab order (no atomics): the bits depend on neither the grid nor the chunk.  n^2 nt + n sum n_g^2 flops per dim.
+ * nt == 0 (then n_groups == 0): the factor runs (info is written), nothing else is touched.  workspace:
+ * lvae_predict_exact_cov_workspace_size(n, nt, L, chunk) bytes (lvae_predict_exact_var_f64's
+ * + 2048 L c ceil(n / 512); 0 as there), 256-B aligned.
+ * Returns 0, LVAE_ERR_LAUNCH, or before any launch, in this order: -1 .. -16 as lvae_predict_exact_var_f64 (-5 also
+ * for L > 65535); -17 (n_groups outside 0 .. 65535, or n_groups == 0 with nt > 0 or the reverse); with nt > 0: -18
+ * (n_max outside 1 .. 128: a group above the cap); -19 (add_noise not 0 / 1); with nt > 0: -20 (chunk < n_max) -21
+ * (group_start NULL) -22 (group_start does not cut 0 .. nt into groups of 1 .. n_max rows) -23 (out_cov NULL). */
+size_t lvae_predict_exact_cov_workspace_size(int n, int nt, int L, int chunk);
+int lvae_predict_exact_cov_f64(const lvae_kernel_spec* spec, const double* x, int64_t ldx, int n, int L,
+                               const double* params, const double* noise, const double* mu, int64_t ld_mu,
+                               const double* tx, int64_t ldt, int nt, int n_groups, const int32_t* group_start,
+                               int n_max, double* out_mean, int64_t ld_out, double* out_cov, int add_noise, int chunk,
+                               int32_t* info, void* workspace, void* stream);
+
+/* S joint draws of every group's rows from N(mean, Sigma_g + jitter I), fp64, groups and latent dims drawn
+ * independently of each other:
+ *   out[s, r_i, l] = mean[r_i, l] + sum_{j <= i} Lc[l, g, i, j] eps[s, r_j, l],   Lc Lc^T = cov[l, g] + jitter I
+ * cov [L, n_groups, n_max, n_max] as lvae_predict_cov_f64 / lvae_predict_exact_cov_f64 write it (the padding
+ * identity keeps a padded block positive definite); index [n_groups, n_max] int32 (device): r_i = index[g, i], the
+ * row of mean / eps / out that holds the group's i-th row, or -1 on padding (a group's rows first, then its
+ * padding); mean [Nt, L], eps [S, Nt, L] standard normal draws, out [S, Nt, L].  Every row 0 .. Nt - 1 must appear
+ * in exactly one group: rows in no group are not written, and of that only Nt > n_groups n_max can be seen here (-4)
+ * -- the caller checks the rest (lvae_amd.sample_trajectories does, before the call).  Route: one kernel copies cov
+ * with the jitter on the diagonals into the workspace, lvae_potrf_f64 factors the L n_groups blocks in place
+ * (info[l*n_groups + g] LAPACK-style: > 0 for a block that is not positive definite, whose draws are then
+ * meaningless; the others are unaffected), one kernel forms the draws, each sum in the order of j.  n_groups == 0
+ * (then Nt == 0): returns 0, nothing is touched; S == 0 or Nt == 0: the factors run (info is written), out is
+ * untouched.  workspace: lvae_predict_sample_workspace_size(L, n_groups, n_max) bytes (8 (L G n_max^2 + L G), each
+ * array rounded up to 256 B, G = max(n_groups, 1); 0 for L < 1, n_groups < 0 or n_max < 1), 256-B aligned.
+ * Returns 0, LVAE_ERR_LAUNCH, or before any launch, in this order: -1 (L < 1) -2 (n_groups < 0 or L n_groups >
+ * 65535) -3 (n_max outside 1 .. 128) -4 (Nt < 0 or Nt > n_groups n_max) -5 (S < 0); with n_groups > 0: -6 (cov NULL)
+ * -7 (index NULL); with Nt > 0 and S > 0: -8 (mean NULL) -9 (eps NULL); -10 (jitter negative or NaN); with Nt > 0
+ * and S > 0: -11 (out NULL); with n_groups > 0: -12 (info NULL); -13 (workspace NULL or misaligned).        */
+size_t lvae_predict_sample_workspace_size(int L, int n_groups, int n_max);
+int lvae_predict_sample_f64(int L, int n_groups, int n_max, int Nt, int S, const double* cov, const int32_t* index,
+                            const double* mean, const double* eps, double jitter, double* out, int32_t* info,
+                            void* workspace, void* stream);
+
 /* ---------------------------------------------------------------------------------------- */
 /* The early stream (per device; optional).  The blocked Cholesky inverse (lvae_spd_inv_chol_f32,   */
 /* lvae_kl_closed_factor_f32) can start the part of its triangular inverse that needs only the      */

@@ -16,9 +16,12 @@
 //
 // Both predictors also give the predictive variance of the latent functions, which the reference does not:
 // lvae_predict_exact_var_f64 and lvae_predict_var_f64 below, their kernels and formulas in predict_var.hpp.
+// lvae_predict_cov_f64 and lvae_predict_exact_cov_f64 form the joint covariance of each group of test rows from the
+// same buffers, and lvae_predict_sample_f64 draws whole trajectories from it (kernels in predict_cov.hpp).
 #include "small.hpp"
 #include "prof.hpp"
 #include "predict_var.hpp"
+#include "predict_cov.hpp"
 
 namespace lvae {
 namespace {
@@ -207,6 +210,26 @@ inline size_t exact_var_panel_bytes(int n, int nt, int L, int chunk) {
   return align256((size_t)L * n * (c > 0 ? c : 0) * sizeof(double));
 }
 
+// workspace of lvae_predict_exact_cov_f64 behind EWs and the panel: the slabs' partial tiles [L, c, nslab, 16, 16]
+// (a chunk of c columns in whole groups of <= 128 rows holds at most c tiles on and below the diagonals)
+inline int exact_cov_slabs(int n) { return cdiv(n, kCovSlab); }
+inline size_t exact_cov_part_bytes(int n, int nt, int L, int chunk) {
+  const int c = chunk < nt ? chunk : nt;
+  return align256((size_t)L * (c > 0 ? c : 0) * exact_cov_slabs(n) * 256 * sizeof(double));
+}
+
+// workspace of lvae_predict_sample_f64: the factors Lc [L, G, n_max, n_max] and their log-determinants [L G]
+struct SWs {
+  double *Lc, *logdet;
+  size_t bytes;
+  SWs(char* base, int L, int G, int n_max) {
+    WsCarve c(base);
+    Lc = c.take((size_t)L * G * n_max * n_max);
+    logdet = c.take((size_t)L * G);
+    bytes = c.off;
+  }
+};
+
 }  // namespace
 
 int gram_matvec_f64(const lvae_kernel_spec* spec, const double* x1, int64_t ld1, int n1, const double* x2, int64_t ld2,
@@ -313,6 +336,55 @@ static int exact_core(const lvae_kernel_spec* spec, const double* x, int64_t ldx
   pe_add_kernel<<<nblk((int64_t)L * n), 256, 0, st>>>((int64_t)L * n, w.a, w.r);
   // Zpred = k(X*, x) a
   LVAE_TRY(gram_matvec_f64(spec, tx, ldt, nt, x, ldx, n, L, params, nullptr, w.a, n, 1, out, ld_out, 0, w.mv, st));
+  LVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+// The launches of lvae_predict_var_f64 up to its last kernel, on the carved workspaces w and v (arguments checked by
+// the caller): lvae_predict_f64's own (and the mean when out is given), then C, D, E, K0zX*, Q, W and V [rows, Nt].
+static int var_pipeline(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, int L, int M, int Q, int P, int T,
+                        const int32_t* seg_len, const int32_t* include, const double* x, const double* mu,
+                        const double* z, int Nt, const double* test_x, int n_groups, const int32_t* group_subject,
+                        const int32_t* group_start, const double* params0, const double* params1,
+                        const double* noise, double eps, double* out, int32_t* info, PWs& w, VWs& v, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  // the Grams, iB, K0zz^-1, H^-1 (and the mean) by lvae_predict_f64's own launches; G kept aside
+  LVAE_TRY(predict_core(spec0, spec1, L, M, Q, P, T, seg_len, include, x, mu, z, Nt, test_x, params0, params1, noise,
+                        eps, out, out != nullptr, v.Gm, info, w, stream));
+  if (Nt == 0) return 0;
+  const int64_t MM = (int64_t)M * M, MN = (int64_t)M * Nt;
+  const size_t mn_bytes = (size_t)L * MN * sizeof(double);
+  const int b1 = spec_bucket(spec1);
+  const DevSpec d1 = to_dev(spec1);
+  // c_i, d_i = iB_s c_i, e_i = K0zx_s d_i per subject group (rows of no group, or of an absent subject: 0)
+  pv_rowsubj_kernel<<<nblk(Nt), 256, 0, st>>>(Nt, P, n_groups, group_subject, group_start, v.rs);
+  if (b1 == 1)
+    pv_c_kernel<8, 2><<<nblk((int64_t)L * T * Nt), 256, 0, st>>>(d1, L, T, Nt, Q, seg_len, v.rs, x, test_x, params1, v.C);
+  else
+    pv_c_kernel<16, 4><<<nblk((int64_t)L * T * Nt), 256, 0, st>>>(d1, L, T, Nt, Q, seg_len, v.rs, x, test_x, params1, v.C);
+  LVAE_TRY(zero_async(v.D, (size_t)L * T * Nt * sizeof(double), st));
+  LVAE_TRY(zero_async(v.E, mn_bytes, st));
+  if (n_groups > 0)
+    pv_group_kernel<<<dim3(Nt / kPvC + n_groups, L), 256, 0, st>>>(M, P, T, Nt, n_groups, group_subject, group_start,
+                                                                  v.C, w.iB, w.K0xz, v.D, v.E);
+  // Q = K0zz^-1 K0zX* with one refinement step Q += K0zz^-1 (K0zX* - K0zz Q), as the mean refines its two products
+  // with explicit inverses: the bare product is cond(K0zz) ulps off, and q enters the variance three times in
+  // terms that cancel.  With this step and the one for V below, an fp64 emulation of the route against the dense
+  // oracle gives 5e-15 of the largest prior variance at M = 128, eps = 1e-3 (cond K0zz 5e5) where the bare
+  // products give 1.5e-10; the tests' bound is 2e-12.  K0zX* [L, M, Nt] is its own Gram (test rows as columns).
+  const lvae_xview zv{z, 0, (int64_t)M * Q, Q}, tv{test_x, 0, 0, Q};
+  LVAE_TRY(lvae_gram_f64(spec0, zv, tv, 1, L, M, Nt, params0, nullptr, v.KzX, 0, MN, Nt, stream));
+  LVAE_TRY(gemm_small_f64(0, 0, M, Nt, M, 1.0, w.iK, M, MM, 0, v.KzX, Nt, MN, 0, 0.0, v.Qm, Nt, MN, 0, L, 1, st));
+  LVAE_TRY(copy_words_async(v.R, v.KzX, mn_bytes, st));
+  LVAE_TRY(gemm_small_f64(0, 0, M, Nt, M, -1.0, w.K0zz, M, MM, 0, v.Qm, Nt, MN, 0, 1.0, v.R, Nt, MN, 0, L, 1, st));
+  LVAE_TRY(gemm_small_f64(0, 0, M, Nt, M, 1.0, w.iK, M, MM, 0, v.R, Nt, MN, 0, 1.0, v.Qm, Nt, MN, 0, L, 1, st));
+  // W = G Q + E;  V = H^-1 W with the same refinement step, V += H^-1 (W - H V) (cond(H) ulps otherwise)
+  LVAE_TRY(copy_words_async(v.W, v.E, mn_bytes, st));
+  LVAE_TRY(gemm_small_f64(0, 0, M, Nt, M, 1.0, v.Gm, M, MM, 0, v.Qm, Nt, MN, 0, 1.0, v.W, Nt, MN, 0, L, 1, st));
+  LVAE_TRY(gemm_small_f64(0, 0, M, Nt, M, 1.0, w.iH, M, MM, 0, v.W, Nt, MN, 0, 0.0, v.V, Nt, MN, 0, L, 1, st));
+  LVAE_TRY(copy_words_async(v.R, v.W, mn_bytes, st));
+  LVAE_TRY(gemm_small_f64(0, 0, M, Nt, M, -1.0, w.Hm, M, MM, 0, v.V, Nt, MN, 0, 1.0, v.R, Nt, MN, 0, L, 1, st));
+  LVAE_TRY(gemm_small_f64(0, 0, M, Nt, M, 1.0, w.iH, M, MM, 0, v.R, Nt, MN, 0, 1.0, v.V, Nt, MN, 0, L, 1, st));
   LVAE_CHECK_LAUNCH();
   return 0;
 }
@@ -457,49 +529,186 @@ int lvae_predict_var_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* 
   const int nt1 = Nt > 0 ? Nt : 1;
   PWs w((char*)workspace, L, M, P, T, nt1);
   VWs v((char*)workspace, w.bytes, L, M, T, nt1);
-  // the Grams, iB, K0zz^-1, H^-1 (and the mean) by lvae_predict_f64's own launches; G kept aside
-  LVAE_TRY(predict_core(spec0, spec1, L, M, Q, P, T, seg_len, include, x, mu, z, Nt, test_x, params0, params1, noise,
-                        eps, out, out != nullptr, v.Gm, info, w, stream));
+  LVAE_TRY(var_pipeline(spec0, spec1, L, M, Q, P, T, seg_len, include, x, mu, z, Nt, test_x, n_groups, group_subject,
+                        group_start, params0, params1, noise, eps, out, info, w, v, stream));
   if (Nt == 0) return 0;
-  const int64_t MM = (int64_t)M * M, MN = (int64_t)M * Nt;
-  const size_t mn_bytes = (size_t)L * MN * sizeof(double);
   const int b1 = spec_bucket(spec1);
   const DevSpec d1 = to_dev(spec1);
-  // c_i, d_i = iB_s c_i, e_i = K0zx_s d_i per subject group (rows of no group, or of an absent subject: 0)
-  pv_rowsubj_kernel<<<nblk(Nt), 256, 0, st>>>(Nt, P, n_groups, group_subject, group_start, v.rs);
-  if (b1 == 1)
-    pv_c_kernel<8, 2><<<nblk((int64_t)L * T * Nt), 256, 0, st>>>(d1, L, T, Nt, Q, seg_len, v.rs, x, test_x, params1, v.C);
-  else
-    pv_c_kernel<16, 4><<<nblk((int64_t)L * T * Nt), 256, 0, st>>>(d1, L, T, Nt, Q, seg_len, v.rs, x, test_x, params1, v.C);
-  LVAE_TRY(zero_async(v.D, (size_t)L * T * Nt * sizeof(double), st));
-  LVAE_TRY(zero_async(v.E, mn_bytes, st));
-  if (n_groups > 0)
-    pv_group_kernel<<<dim3(Nt / kPvC + n_groups, L), 256, 0, st>>>(M, P, T, Nt, n_groups, group_subject, group_start,
-                                                                  v.C, w.iB, w.K0xz, v.D, v.E);
-  // Q = K0zz^-1 K0zX* with one refinement step Q += K0zz^-1 (K0zX* - K0zz Q), as the mean refines its two products
-  // with explicit inverses: the bare product is cond(K0zz) ulps off, and q enters the variance three times in
-  // terms that cancel.  With this step and the one for V below, an fp64 emulation of the route against the dense
-  // oracle gives 5e-15 of the largest prior variance at M = 128, eps = 1e-3 (cond K0zz 5e5) where the bare
-  // products give 1.5e-10; the tests' bound is 2e-12.  K0zX* [L, M, Nt] is its own Gram (test rows as columns).
-  const lvae_xview zv{z, 0, (int64_t)M * Q, Q}, tv{test_x, 0, 0, Q};
-  LVAE_TRY(lvae_gram_f64(spec0, zv, tv, 1, L, M, Nt, params0, nullptr, v.KzX, 0, MN, Nt, stream));
-  LVAE_TRY(gemm_small_f64(0, 0, M, Nt, M, 1.0, w.iK, M, MM, 0, v.KzX, Nt, MN, 0, 0.0, v.Qm, Nt, MN, 0, L, 1, st));
-  LVAE_TRY(copy_words_async(v.R, v.KzX, mn_bytes, st));
-  LVAE_TRY(gemm_small_f64(0, 0, M, Nt, M, -1.0, w.K0zz, M, MM, 0, v.Qm, Nt, MN, 0, 1.0, v.R, Nt, MN, 0, L, 1, st));
-  LVAE_TRY(gemm_small_f64(0, 0, M, Nt, M, 1.0, w.iK, M, MM, 0, v.R, Nt, MN, 0, 1.0, v.Qm, Nt, MN, 0, L, 1, st));
-  // W = G Q + E;  V = H^-1 W with the same refinement step, V += H^-1 (W - H V) (cond(H) ulps otherwise)
-  LVAE_TRY(copy_words_async(v.W, v.E, mn_bytes, st));
-  LVAE_TRY(gemm_small_f64(0, 0, M, Nt, M, 1.0, v.Gm, M, MM, 0, v.Qm, Nt, MN, 0, 1.0, v.W, Nt, MN, 0, L, 1, st));
-  LVAE_TRY(gemm_small_f64(0, 0, M, Nt, M, 1.0, w.iH, M, MM, 0, v.W, Nt, MN, 0, 0.0, v.V, Nt, MN, 0, L, 1, st));
-  LVAE_TRY(copy_words_async(v.R, v.W, mn_bytes, st));
-  LVAE_TRY(gemm_small_f64(0, 0, M, Nt, M, -1.0, w.Hm, M, MM, 0, v.V, Nt, MN, 0, 1.0, v.R, Nt, MN, 0, L, 1, st));
-  LVAE_TRY(gemm_small_f64(0, 0, M, Nt, M, 1.0, w.iH, M, MM, 0, v.R, Nt, MN, 0, 1.0, v.V, Nt, MN, 0, L, 1, st));
   if (b1 == 1)
     pv_var_kernel<8, 2><<<nblk((int64_t)L * Nt), 256, 0, st>>>(d1, L, M, T, Nt, Q, v.KzX, v.Qm, v.W, v.E, v.V, v.C, v.D,
                                                                test_x, params1, noise, add_noise, out_var);
   else
     pv_var_kernel<16, 4><<<nblk((int64_t)L * Nt), 256, 0, st>>>(d1, L, M, T, Nt, Q, v.KzX, v.Qm, v.W, v.E, v.V, v.C, v.D,
                                                                 test_x, params1, noise, add_noise, out_var);
+  LVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+size_t lvae_predict_cov_workspace_size(int L, int M, int P, int T, int Nt) {
+  return lvae_predict_var_workspace_size(L, M, P, T, Nt);
+}
+
+int lvae_predict_cov_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, int L, int M, int Q, int P,
+                         int T, const int32_t* seg_len, const int32_t* include, const double* x, const double* mu,
+                         const double* z, int Nt, const double* test_x, int n_groups, const int32_t* group_subject,
+                         const int32_t* group_start, int n_max, const double* params0, const double* params1,
+                         const double* noise, double eps, double* out, double* out_cov, int add_noise, int32_t* info,
+                         void* workspace, void* stream) {
+  if (!spec0 || !spec1 || !spec_bucket(spec0) || !spec_bucket(spec1)) return -1;  // (before any launch)
+  if (L < 1 || L > 65535 || M < 1 || M > 128) return -3;
+  if (P < 1 || T < 1 || T > 128 || Q < 1) return -6;
+  if (!seg_len || !include) return -8;
+  if (out && !mu) return -9;
+  if (!x || !z) return -10;
+  if (!params0 || !params1 || !noise) return -11;
+  if (Nt < 0) return -13;
+  if (Nt > 0 && !test_x) return -12;
+  if (n_groups < 0 || n_groups > 65535) return -14;
+  if (n_groups > 0 && (!group_subject || !group_start)) return -15;
+  if (n_groups > 0 && !out_cov) return -16;
+  if (add_noise != 0 && add_noise != 1) return -17;
+  if (n_groups > 0 && (n_max < 1 || n_max > kPvT)) return -18;
+  if (!workspace || ((uintptr_t)workspace & 255)) return -20;
+  hipStream_t st = (hipStream_t)stream;
+  const int nt1 = Nt > 0 ? Nt : 1;
+  PWs w((char*)workspace, L, M, P, T, nt1);
+  VWs v((char*)workspace, w.bytes, L, M, T, nt1);
+  LVAE_TRY(var_pipeline(spec0, spec1, L, M, Q, P, T, seg_len, include, x, mu, z, Nt, test_x, n_groups, group_subject,
+                        group_start, params0, params1, noise, eps, out, info, w, v, stream));
+  if (Nt == 0 || n_groups == 0) return 0;
+  const int64_t nb = (int64_t)L * n_groups;
+  pc_eye_kernel<<<nblk(nb * n_max * n_max), 256, 0, st>>>(nb, n_max, out_cov);
+  const DevSpec d1 = to_dev(spec1);
+  const dim3 grid(cov_tiles(n_max), n_groups, L);
+  if (spec_bucket(spec1) == 1)
+    pc_cov_kernel<8, 2><<<grid, 64, 0, st>>>(d1, M, T, Nt, Q, n_max, group_start, v.KzX, v.Qm, v.W, v.E, v.V, v.C, v.D,
+                                             test_x, params1, noise, add_noise, out_cov);
+  else
+    pc_cov_kernel<16, 4><<<grid, 64, 0, st>>>(d1, M, T, Nt, Q, n_max, group_start, v.KzX, v.Qm, v.W, v.E, v.V, v.C, v.D,
+                                              test_x, params1, noise, add_noise, out_cov);
+  LVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+size_t lvae_predict_exact_cov_workspace_size(int n, int nt, int L, int chunk) {
+  if (n < 1 || nt < 0 || L < 1 || (nt > 0 && chunk < 1)) return 0;
+  return EWs(nullptr, n, nt, L).bytes + exact_var_panel_bytes(n, nt, L, chunk) + exact_cov_part_bytes(n, nt, L, chunk);
+}
+
+int lvae_predict_exact_cov_f64(const lvae_kernel_spec* spec, const double* x, int64_t ldx, int n, int L,
+                               const double* params, const double* noise, const double* mu, int64_t ld_mu,
+                               const double* tx, int64_t ldt, int nt, int n_groups, const int32_t* group_start,
+                               int n_max, double* out_mean, int64_t ld_out, double* out_cov, int add_noise, int chunk,
+                               int32_t* info, void* workspace, void* stream) {
+  const int ld_min = spec ? gram_matvec_spec_ld(spec) : 0;
+  if (ld_min < 1 || ld_min > 32) return -1;  // (before any launch)
+  if (!x) return -2;
+  if (ldx < ld_min) return -3;
+  if (n < 1) return -4;
+  if (L < 1 || L > 65535) return -5;
+  if (!params) return -6;
+  if (!noise) return -7;
+  if (out_mean && !mu) return -8;
+  if (out_mean && ld_mu < L) return -9;
+  if (nt < 0) return -12;
+  if (nt > 0 && !tx) return -10;
+  if (nt > 0 && ldt < ld_min) return -11;
+  if (out_mean && ld_out < L) return -14;
+  if (!info) return -15;
+  if (!workspace || ((uintptr_t)workspace & 255)) return -16;
+  if (n_groups < 0 || n_groups > 65535 || (n_groups == 0) != (nt == 0)) return -17;
+  if (nt > 0 && (n_max < 1 || n_max > kPvT)) return -18;
+  if (add_noise != 0 && add_noise != 1) return -19;
+  if (nt > 0 && chunk < n_max) return -20;
+  if (nt > 0 && !group_start) return -21;
+  if (nt > 0) {
+    if (group_start[0] != 0 || group_start[n_groups] != nt) return -22;
+    for (int g = 0; g < n_groups; ++g) {
+      const int64_t len = (int64_t)group_start[g + 1] - group_start[g];
+      if (len < 1 || len > n_max) return -22;
+    }
+  }
+  if (nt > 0 && !out_cov) return -23;
+  hipStream_t st = (hipStream_t)stream;
+  EWs w((char*)workspace, n, nt, L);
+  double* panel = (double*)((char*)workspace + w.bytes);
+  double* part = (double*)((char*)panel + exact_var_panel_bytes(n, nt, L, chunk));
+  // the factor of K (and the mean, by lvae_predict_exact_f64's own launches)
+  LVAE_TRY(exact_core(spec, x, ldx, n, L, params, noise, mu, ld_mu, tx, ldt, nt, out_mean, ld_out, info, w, stream));
+  if (nt == 0) return 0;
+  const int64_t nb = (int64_t)L * n_groups;
+  pc_eye_kernel<<<nblk(nb * n_max * n_max), 256, 0, st>>>(nb, n_max, out_cov);
+  // whole groups at a time, as many as fit c panel columns: the panel k(X, X*_chunk) [L, n, c] and one triangular
+  // solve in place as lvae_predict_exact_var_f64, then per launch of <= kCovBatch groups the slabs' partial tiles
+  // and their sum in slab order.  A column's solve does not depend on its neighbours and a tile's slabs depend on n
+  // alone, so the bits do not depend on the chunk.
+  const int c = chunk < nt ? chunk : nt, nslab = exact_cov_slabs(n), bucket = spec_bucket(spec);
+  const DevSpec ds = to_dev(spec);
+  const lvae_xview xv{x, 0, 0, ldx};
+  for (int g0 = 0; g0 < n_groups;) {
+    int g1 = g0;
+    while (g1 < n_groups && group_start[g1 + 1] - group_start[g0] <= c) ++g1;
+    const int c0 = group_start[g0], nr = group_start[g1] - c0;
+    const double* tc = tx + (int64_t)c0 * ldt;
+    const lvae_xview tv{tc, 0, 0, ldt};
+    LVAE_TRY(lvae_gram_f64(spec, xv, tv, 1, L, n, nr, params, nullptr, panel, 0, (int64_t)n * c, c, stream));
+    LVAE_TRY(lvae_trsm_f64(0, n, nr, L, w.K, n, (int64_t)n * n, panel, c, (int64_t)n * c, w.trsm, stream));
+    int tile0 = 0;
+    for (int b0 = g0; b0 < g1; b0 += kCovBatch) {
+      CovBatch cb;
+      cb.n = g1 - b0 < kCovBatch ? g1 - b0 : kCovBatch;
+      cb.tile[0] = 0;
+      for (int b = 0; b <= cb.n; ++b) {
+        cb.col[b] = group_start[b0 + b] - c0;
+        if (b > 0) cb.tile[b] = cb.tile[b - 1] + cov_tiles(cb.col[b] - cb.col[b - 1]);
+      }
+      for (int b = cb.n + 1; b <= kCovBatch; ++b) cb.col[b] = cb.col[cb.n], cb.tile[b] = cb.tile[cb.n];
+      const int nt_b = cb.tile[cb.n];
+      pcx_partial_kernel<<<dim3(nt_b, nslab, L), 64, 0, st>>>(cb, n, panel, c, tile0, c, part);
+      if (bucket == 1)
+        pcx_reduce_kernel<8, 2><<<dim3(nt_b, L), 256, 0, st>>>(ds, cb, nslab, tile0, c, part, tc, ldt, params, noise,
+                                                               add_noise, b0, n_groups, n_max, out_cov);
+      else
+        pcx_reduce_kernel<16, 4><<<dim3(nt_b, L), 256, 0, st>>>(ds, cb, nslab, tile0, c, part, tc, ldt, params, noise,
+                                                                add_noise, b0, n_groups, n_max, out_cov);
+      tile0 += nt_b;
+    }
+    g0 = g1;
+  }
+  LVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+size_t lvae_predict_sample_workspace_size(int L, int n_groups, int n_max) {
+  if (L < 1 || n_groups < 0 || n_max < 1) return 0;
+  return SWs(nullptr, L, n_groups > 0 ? n_groups : 1, n_max).bytes;
+}
+
+int lvae_predict_sample_f64(int L, int n_groups, int n_max, int Nt, int S, const double* cov, const int32_t* index,
+                            const double* mean, const double* eps, double jitter, double* out, int32_t* info,
+                            void* workspace, void* stream) {
+  if (L < 1) return -1;  // (before any launch)
+  if (n_groups < 0 || (int64_t)L * n_groups > 65535) return -2;
+  if (n_max < 1 || n_max > kPvT) return -3;
+  if (Nt < 0 || (int64_t)Nt > (int64_t)n_groups * n_max) return -4;  // (some row is in no group)
+  if (S < 0) return -5;
+  if (n_groups > 0 && !cov) return -6;
+  if (n_groups > 0 && !index) return -7;
+  if (Nt > 0 && S > 0 && !mean) return -8;
+  if (Nt > 0 && S > 0 && !eps) return -9;
+  if (!(jitter >= 0.0)) return -10;
+  if (Nt > 0 && S > 0 && !out) return -11;
+  if (n_groups > 0 && !info) return -12;
+  if (!workspace || ((uintptr_t)workspace & 255)) return -13;
+  if (n_groups == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  SWs w((char*)workspace, L, n_groups, n_max);
+  const int64_t nb = (int64_t)L * n_groups, nn = (int64_t)n_max * n_max;
+  pcs_jitter_kernel<<<nblk(nb * nn), 256, 0, st>>>(nb, n_max, jitter, cov, w.Lc);
+  LVAE_TRY(lvae_potrf_f64(n_max, (int)nb, w.Lc, n_max, nn, w.Lc, n_max, nn, w.logdet, info, stream));
+  if (Nt > 0 && S > 0)
+    pcs_draw_kernel<<<nblk((int64_t)S * nb * n_max), 256, 0, st>>>(L, n_groups, n_max, Nt, S, w.Lc, index, mean, eps,
+                                                                   out);
   LVAE_CHECK_LAUNCH();
   return 0;
 }

@@ -10,7 +10,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from lvae_amd import samplers as _s  # noqa: E402
 from lvae_amd.data import DeviceBatchLoader  # noqa: E402
-from lvae_amd.predict import batch_predict_varying_T, sample_predictions  # noqa: E402,F401
+from lvae_amd.predict import batch_predict_varying_T, sample_predictions, sample_trajectories  # noqa: E402,F401
 
 
 class SubjectSampler:
@@ -70,4 +70,4 @@ class HensmanDataLoader(DeviceBatchLoader):
 
 
 __all__ = ["SubjectSampler", "VaryingLengthSubjectSampler", "VaryingLengthBatchSampler", "HensmanDataLoader",
-           "batch_predict_varying_T", "sample_predictions"]
+           "batch_predict_varying_T", "sample_predictions", "sample_trajectories"]

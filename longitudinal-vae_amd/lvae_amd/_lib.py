@@ -215,6 +215,17 @@ SIGNATURES = {
     "lvae_predict_var_workspace_size": (_SZ, [_I32, _I32, _I32, _I32, _I32]),
     "lvae_predict_var_f64": (_I32, [_SPEC, _SPEC, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _I32, _VP,
                                     _I32, _VP, _VP, _VP, _VP, _VP, _D, _VP, _VP, _I32, _VP, _VP, _VP]),
+    # the groups' joint covariance: lvae_predict_var_f64's arguments with n_max after group_start and out_cov for
+    # out_var; lvae_predict_exact_var_f64's with (n_groups, host group_start, n_max) after nt and out_cov for
+    # (out_var, ld_var); the draws (L, G, n_max, Nt, S, cov, index, mean, eps, jitter, out, info, workspace, stream)
+    "lvae_predict_cov_workspace_size": (_SZ, [_I32, _I32, _I32, _I32, _I32]),
+    "lvae_predict_cov_f64": (_I32, [_SPEC, _SPEC, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _I32, _VP,
+                                    _I32, _VP, _VP, _I32, _VP, _VP, _VP, _D, _VP, _VP, _I32, _VP, _VP, _VP]),
+    "lvae_predict_exact_cov_workspace_size": (_SZ, [_I32, _I32, _I32, _I32]),
+    "lvae_predict_exact_cov_f64": (_I32, [_SPEC, _VP, _I64, _I32, _I32, _VP, _VP, _VP, _I64, _VP, _I64, _I32, _I32,
+                                          _VP, _I32, _VP, _I64, _VP, _I32, _I32, _VP, _VP, _VP]),
+    "lvae_predict_sample_workspace_size": (_SZ, [_I32, _I32, _I32]),
+    "lvae_predict_sample_f64": (_I32, [_I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _D, _VP, _VP, _VP, _VP]),
     "lvae_prof_enable": (_I32, [_I32]),
     "lvae_set_early_stream": (_I32, [_VP]),
     "lvae_prof_collect": (_I32, [_VP, _VP, _I32]),

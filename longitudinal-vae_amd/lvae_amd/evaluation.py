@@ -109,6 +109,40 @@ def MSE_test_GPapprox(csv_file_test_data, csv_file_test_label, test_mask_file, d
                                                      labels, pm, zt_list, id_covariate, eps=1e-6))
 
 
+def generate_trajectories(nnet_model, mean, cov=None, num_samples=0, eps=None, generator=None, jitter=1e-8,
+                          chunk_rows=4096):
+    """Decoded image sequences at the predicted latents: ``(decode(mean), draws)``, the computational half of
+    recon_complete_gen / variational_complete_gen (predict_HealthMNIST.py:131-138, 165-170; their plots are out of
+    scope).  ``mean`` [Nt, L] is a predictor's Z_pred (batch_predict_varying_T or predict_exact at the generation
+    set's labels).  With ``cov`` (the PredictiveCovariance of the same call with ``return_cov=True``) and
+    ``num_samples`` > 0 or ``eps`` [S, Nt, L], ``draws`` [S, Nt, ...] holds the decoded trajectory draws of
+    ``sample_trajectories(mean, cov, num_samples, eps, generator, jitter)``: each subject's frames are drawn
+    jointly, so a drawn sequence is coherent over time, while different subjects are drawn independently of each
+    other.  Otherwise ``draws`` is None.  Either model (ConvVAE, SimpleVAE), in the mode the caller left it in
+    (``eval()`` for dropout-free images, as the reference's callers do); no gradients are recorded.  The decoder
+    runs one draw at a time, over at most ``chunk_rows`` of its rows per call, exactly as it runs over ``mean``: the
+    S * Nt images never need one set of activations, and a draw with ``eps = 0`` is ``decode(mean)`` bit for bit.
+    A decoder call's bits do not depend on the other rows' values, so ``chunk_rows`` changes no bit as long as the
+    decoder's GEMM library picks the same kernel for the shorter calls (the ConvVAE's fc layers run on hipBLASLt,
+    which chooses by shape: 15 rows in calls of 4 gave the bits of one call on an MI355X, 30 rows did not)."""
+    from .predict import sample_trajectories
+    chunk_rows = max(int(chunk_rows), 1)
+    dtype = next(nnet_model.parameters()).dtype
+
+    def decode(z):
+        parts = [nnet_model.decode(z[r0:r0 + chunk_rows].to(dtype)) for r0 in range(0, z.shape[0], chunk_rows)]
+        return torch.cat(parts) if parts else nnet_model.decode(z.to(dtype))
+
+    with torch.no_grad():
+        images = decode(mean)
+        if cov is None or (eps is None and int(num_samples) < 1):
+            return images, None
+        z = sample_trajectories(mean, cov, num_samples=num_samples, eps=eps, generator=generator, jitter=jitter)
+        if z.shape[0] == 0:
+            return images, images.new_empty((0,) + tuple(images.shape))
+        return images, torch.stack([decode(zs) for zs in z])
+
+
 def VAEtest(test_dataset, nnet_model, type_nnet, id_covariate):
     """Mean masked MSE of the autoencoder alone over a device-resident dataset (model_test.py:145-167); either
     model, ``type_nnet`` is not used."""

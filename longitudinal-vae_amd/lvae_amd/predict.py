@@ -6,7 +6,11 @@ Python loops and its removed ``torch.solve``.  ``predict_exact`` is the exact-GP
 
 Both predictors also return the predictive variance of the latent functions (``return_var=True``:
 lvae_predict_var_f64, lvae_predict_exact_var_f64), which the reference does not compute; ``sample_predictions``
-draws from the resulting marginals.
+draws from the resulting marginals.  ``return_cov=True`` returns the joint covariance of each group of test rows
+(a subject's, for the inducing-point route) as a ``PredictiveCovariance`` (lvae_predict_cov_f64,
+lvae_predict_exact_cov_f64), and ``sample_trajectories`` draws each group's rows jointly from it
+(lvae_predict_sample_f64).  Groups are independent of each other: the covariance between rows of different groups
+is not zero in the model, and is neither returned nor drawn from.
 """
 import ctypes
 
@@ -15,9 +19,70 @@ import torch
 from . import _lib
 from .elbo import _check_info, _noise_vector, _stack_modules, _subject_layout
 
+MAX_GROUP_ROWS = 128   # the largest group of test rows a joint covariance is formed for (kPvT)
+
+
+class PredictiveCovariance:
+    """The joint predictive covariance of the latent functions at each group of test rows, per latent dim.
+
+    ``blocks`` [L, G, n_max, n_max] fp64: block (l, g) is the covariance of group g's rows, row i of a block the
+    group's i-th test row in order of appearance; padding rows and columns carry the identity and a block is
+    symmetric bit for bit.  ``index`` [G, n_max] int32: the caller's row index of each block row, -1 on padding.
+    ``counts`` [G] (CPU): the groups' rows.  Covariance between rows of different groups (or latent dims) is not
+    held: groups are treated as independent of each other."""
+
+    def __init__(self, blocks, index, counts):
+        self.blocks, self.index, self.counts = blocks, index, counts
+
+    @property
+    def num_rows(self):
+        return int(self.counts.sum())
+
+    def diagonal(self):
+        """[Nt, L]: the predictive variances in the caller's row order"""
+        L, G, n_max = self.blocks.shape[:3]
+        d = torch.diagonal(self.blocks, dim1=2, dim2=3).reshape(L, G * n_max)
+        ix = self.index.reshape(-1).long()
+        keep = ix >= 0
+        out = torch.empty(self.num_rows, L, dtype=self.blocks.dtype, device=self.blocks.device)
+        out[ix[keep]] = d[:, keep].T
+        return out
+
+    def block(self, g):
+        """[L, n_g, n_g]: group g's covariance without padding"""
+        n = int(self.counts[g])
+        return self.blocks[:, g, :n, :n]
+
+
+def _row_groups(labels, what):
+    """Test rows grouped by label, stable (a group's rows keep their order of appearance): (order [Nt], the
+    groups' labels [G], counts [G], start [G + 1] int32, n_max), all on the CPU; a group above MAX_GROUP_ROWS
+    raises ValueError"""
+    lab = labels.detach().to("cpu", torch.float64).reshape(-1)
+    order = torch.argsort(lab, stable=True)
+    ids, counts = torch.unique_consecutive(lab[order], return_counts=True)
+    start = torch.zeros(ids.numel() + 1, dtype=torch.int32)
+    start[1:] = torch.cumsum(counts, 0)
+    n_max = int(counts.max()) if counts.numel() else 1
+    if n_max > MAX_GROUP_ROWS:
+        g = int(counts.argmax())
+        raise ValueError(f"{what}: group {g} (label {float(ids[g]):g}) has {n_max} test rows; a joint covariance "
+                         f"is formed for groups of at most {MAX_GROUP_ROWS}")
+    return order, ids, counts, start, n_max
+
+
+def _group_index(order, counts, start, n_max, dev):
+    """index [G, n_max] int32 on dev: the caller's row of each block row, -1 on padding"""
+    G = int(counts.numel())
+    index = torch.full((G, n_max), -1, dtype=torch.int32)
+    if order.numel():
+        g_of = torch.repeat_interleave(torch.arange(G), counts)
+        index[g_of, torch.arange(order.numel()) - start[:-1].long()[g_of]] = order.to(torch.int32)
+    return index.to(dev)
+
 
 def batch_predict_varying_T(latent_dim, covar_module0, covar_module1, likelihoods, prediction_x, test_x, mu,
-                            zt_list, id_covariate, eps, return_var=False, add_noise=False):
+                            zt_list, id_covariate, eps, return_var=False, add_noise=False, return_cov=False):
     """Z_pred [N_test, L]: posterior mean of the L latent GPs at ``test_x`` given the encoder means
     ``mu`` [N_pred, L] at ``prediction_x`` (subjects of any length).  ``covar_module0/1`` are
     batched modules or per-dim lists, ``zt_list`` the inducing points [L, M, Q] (or a per-dim
@@ -26,7 +91,16 @@ def batch_predict_varying_T(latent_dim, covar_module0, covar_module1, likelihood
     ``return_var=True`` returns ``(Z_pred, Z_var)``: Z_var [N_test, L] fp64 is the predictive variance of the
     latent functions in the same structured model (lvae_predict_var_f64; K0xz K0zz^-1 K0zx + blockdiag k1 as
     the prior), clamped at 0, in the caller's row order; ``add_noise=True`` adds the likelihood noise of each
-    dim.  The id kernel ``covar_module1`` must vanish between subjects (generate_kernel_batched's does)."""
+    dim.  The id kernel ``covar_module1`` must vanish between subjects (generate_kernel_batched's does).
+
+    ``return_cov=True`` returns ``(Z_pred, cov)`` instead: ``cov`` is a PredictiveCovariance with one group per test
+    subject (the rows sharing ``test_x[:, id_covariate]``), its blocks the joint covariance of the subject's rows
+    in the same model (lvae_predict_cov_f64), not clamped; ``add_noise=True`` adds the noise to the diagonals.  A
+    subject with more than 128 test rows raises ValueError.  The covariance between different subjects' rows is
+    not zero (the shared components couple subjects) and is deliberately not returned: sample_trajectories draws
+    the groups independently of each other."""
+    if return_var and return_cov:
+        raise ValueError("return_var and return_cov are exclusive: cov.diagonal() holds the variances")
     lib = _lib.lib()
     L = int(latent_dim)
     spec0, params0 = _stack_modules(covar_module0)
@@ -63,6 +137,26 @@ def batch_predict_varying_T(latent_dim, covar_module0, covar_module1, likelihood
     p0, p1 = f64(params0), f64(params1)
     out = torch.empty(Nt, L, dtype=torch.float64, device=dev)
     info = torch.empty(L, dtype=torch.int32, device=dev)
+    if return_cov:
+        order, ids, counts, start, n_max = _row_groups(test_x[:, id_covariate], "batch_predict_varying_T")
+        G = int(ids.numel())
+        where = torch.searchsorted(pred_ids, ids).clamp(max=P - 1)
+        subj = torch.where(pred_ids[where] == ids, where, torch.full_like(where, -1)).to(torch.int32)
+        order_d = order.to(dev)
+        txg = tx[order_d].contiguous()
+        outg = torch.empty_like(out)
+        blocks = torch.empty(L, G, n_max, n_max, dtype=torch.float64, device=dev)
+        subj_d, start_d = subj.to(dev), start.to(dev)
+        ws = torch.empty(int(lib.lvae_predict_cov_workspace_size(L, M, P, T, Nt)), dtype=torch.uint8, device=dev)
+        rc = lib.lvae_predict_cov_f64(spec0, spec1, L, M, Q, P, T, _lib.ptr(seg_d), _lib.ptr(inc_d), _lib.ptr(x_pad),
+                                      _lib.ptr(mu_pad), _lib.ptr(z), Nt, _lib.ptr(txg), G, _lib.ptr(subj_d),
+                                      _lib.ptr(start_d), n_max, _lib.ptr(p0), _lib.ptr(p1), _lib.ptr(noise),
+                                      float(eps), _lib.ptr(outg), _lib.ptr(blocks), 1 if add_noise else 0,
+                                      _lib.ptr(info), _lib.ptr(ws), _lib.stream_ptr())
+        _lib.check(rc, "predict_cov")
+        _check_info(info, "batch_predict_varying_T cholesky (10000+col: K0zz, 20000+col: B_st, 30000+col: H)")
+        out[order_d] = outg
+        return out, PredictiveCovariance(blocks, _group_index(order, counts, start, n_max, dev), counts)
     if return_var:
         # test rows grouped by subject (stable: a subject's rows keep their order), each group with its
         # subject's index in the prediction layout or -1; the grouping is undone on the way out
@@ -101,7 +195,7 @@ def batch_predict_varying_T(latent_dim, covar_module0, covar_module1, likelihood
 
 
 def predict_exact(covar_module, likelihoods, prediction_x, test_x, prediction_mu, max_workspace_bytes=4 << 30,
-                  return_var=False, add_noise=False):
+                  return_var=False, add_noise=False, return_cov=False, groups=None):
     """Z_pred [N_test, L] fp64: the exact-GP posterior mean k(X*, X) (k(X, X) + noise I)^-1 mu per latent dim
     (model_test.py:11-17 predict_gp as MSE_test calls it, model_test.py:65-76), one HIP pass per group of dims
     (lvae_predict_exact_f64) instead of the reference's per-dim explicit inverse and dense [N_test, N] Gram.
@@ -113,7 +207,18 @@ def predict_exact(covar_module, likelihoods, prediction_x, test_x, prediction_mu
     ``return_var=True`` returns ``(Z_pred, Z_var)``: Z_var [N_test, L] fp64 is the latent functions' predictive
     variance k(x*, x*) - |L^-1 k(X, x*)|^2 (lvae_predict_exact_var_f64), clamped at 0; ``add_noise=True`` adds
     each dim's likelihood noise.  The test rows are then solved in chunks (8 N bytes a row and dim) sized, after
-    the dim groups, to keep the workspace under ``max_workspace_bytes``; neither choice changes the bits."""
+    the dim groups, to keep the workspace under ``max_workspace_bytes``; neither choice changes the bits.
+
+    ``return_cov=True`` returns ``(Z_pred, cov)`` instead: ``cov`` is a PredictiveCovariance whose groups are the
+    test rows sharing a label in ``groups`` [N_test] (for example ``test_x[:, id_covariate]``; None: all test rows
+    form one group), its blocks k(x*_g, x*_g) - V^T V with V = L^-1 k(X, x*_g) (lvae_predict_exact_cov_f64), not
+    clamped; ``add_noise=True`` adds the noise to the diagonals.  A group of more than 128 rows raises ValueError.
+    The test rows are solved in chunks of whole groups under ``max_workspace_bytes`` as above (a chunk holds at
+    least the largest group); the bits depend on neither the dim groups nor the chunks.  The covariance between
+    rows of different groups is not zero and is deliberately not returned: sample_trajectories draws the groups
+    independently of each other."""
+    if return_var and return_cov:
+        raise ValueError("return_var and return_cov are exclusive: cov.diagonal() holds the variances")
     lib = _lib.lib()
     spec, params = _stack_modules(covar_module)
     L = int(prediction_mu.shape[1])
@@ -133,6 +238,41 @@ def predict_exact(covar_module, likelihoods, prediction_x, test_x, prediction_mu
     if n < 1 or mu.shape[0] != n:
         raise ValueError(f"prediction_mu rows {mu.shape[0]} != prediction_x rows {n} (>= 1)")
     chunk = 1   # (the smallest panel decides the dim groups; the chunk then takes what is left)
+    if return_cov:
+        labels = torch.zeros(nt) if groups is None else groups
+        if labels.numel() != nt:
+            raise ValueError(f"groups has {labels.numel()} labels for {nt} test rows")
+        order, ids, counts, start, n_max = _row_groups(labels, "predict_exact")
+        G = int(ids.numel())
+        txg = tx[order.to(dev)].contiguous()
+        size = lambda g, c: int(lib.lvae_predict_exact_cov_workspace_size(n, nt, g, c))
+        group = L
+        while group > 1 and size(group, n_max) > max_workspace_bytes:
+            group -= 1
+        chunk = max(nt, 1)
+        while chunk > n_max and size(group, chunk) > max_workspace_bytes:
+            chunk = max((chunk + 1) // 2, n_max)
+        outg = torch.empty(nt, L, dtype=torch.float64, device=dev)
+        blocks = torch.empty(L, G, n_max, n_max, dtype=torch.float64, device=dev)
+        info = torch.empty(L, dtype=torch.int32, device=dev)
+        ws = torch.empty(size(group, chunk), dtype=torch.uint8, device=dev)
+        start_h = (ctypes.c_int32 * (G + 1))(*start.tolist())   # host memory: the chunks are cut on the host
+        at = lambda t, off: ctypes.c_void_p(t.data_ptr() + 8 * off)
+        for l0 in range(0, L, group):
+            g = min(group, L - l0)
+            rc = lib.lvae_predict_exact_cov_f64(spec, _lib.ptr(x), x.stride(0), n, g, at(p, l0 * n_params),
+                                                at(noise, l0), at(mu, l0), L, _lib.ptr(txg) if nt else None,
+                                                txg.stride(0), nt, G, ctypes.cast(start_h, ctypes.c_void_p), n_max,
+                                                at(outg, l0) if nt else None, L,
+                                                at(blocks, l0 * G * n_max * n_max) if nt else None,
+                                                1 if add_noise else 0, chunk,
+                                                ctypes.c_void_p(info.data_ptr() + 4 * l0), _lib.ptr(ws),
+                                                _lib.stream_ptr())
+            _lib.check(rc, "predict_exact_cov")
+        _check_info(info, "predict_exact cholesky of k(X, X) + noise I")
+        out = torch.empty_like(outg)
+        out[order.to(dev)] = outg
+        return out, PredictiveCovariance(blocks, _group_index(order, counts, start, n_max, dev), counts)
     if return_var:
         size = lambda g: int(lib.lvae_predict_exact_var_workspace_size(n, nt, g, chunk))
     else:
@@ -173,8 +313,56 @@ def predict_exact(covar_module, likelihoods, prediction_x, test_x, prediction_mu
 
 def sample_predictions(mean, var, eps=None, generator=None):
     """mean + sqrt(var) * eps, eps ~ N(0, 1) elementwise (drawn with ``generator`` unless given): independent draws
-    from each test row's own marginal N(mean, var).  The rows are NOT drawn jointly: no covariance between test
-    rows (or latent dims) is modelled, so a drawn trajectory is rougher than a joint posterior sample would be."""
+    from each test row's own marginal N(mean, var).  The rows are NOT drawn jointly, so a drawn trajectory is rougher
+    than a joint posterior sample: for coherent trajectories take ``return_cov=True`` and ``sample_trajectories``,
+    which draws each group's rows (a subject's) jointly from their covariance."""
     if eps is None:
         eps = torch.randn(mean.shape, dtype=mean.dtype, device=mean.device, generator=generator)
     return mean + torch.sqrt(var.clamp(min=0.0)) * eps
+
+
+def sample_trajectories(mean, cov, num_samples=1, eps=None, generator=None, jitter=1e-8):
+    """[S, Nt, L] fp64: S draws in which each group's rows are drawn jointly from N(mean_g, Sigma_g + jitter I),
+    ``mean`` [Nt, L] and ``cov`` the PredictiveCovariance a ``return_cov=True`` call returned beside it
+    (lvae_predict_sample_f64: the blocks are factored by lvae_potrf_f64, then out[s, r_i, l] = mean[r_i, l] +
+    sum_{j <= i} Lc[l, g, i, j] eps[s, r_j, l]).  ``eps`` [S, Nt, L] in the caller's row order holds the standard
+    normal draws (drawn with ``generator`` unless given; S is then ``num_samples``).  Groups, like latent dims, are
+    drawn independently of each other: the covariance between different groups' rows is not modelled.  ``jitter``
+    is added to the blocks' diagonals before the factorisation (rows observed without noise, or duplicated, make a
+    block singular); a block that still fails raises torch.linalg.LinAlgError naming its dim and group.  Every test
+    row must belong to exactly one group (ValueError otherwise).  With one-row groups and ``jitter=0`` this is
+    ``sample_predictions`` to a few ulps."""
+    lib = _lib.lib()
+    dev = mean.device
+    m = mean.detach().to(dev, torch.float64).contiguous()
+    Nt, L = int(m.shape[0]), int(m.shape[1])
+    blocks = cov.blocks.detach().to(dev, torch.float64).contiguous()
+    index = cov.index.to(dev, torch.int32).contiguous()
+    G, n_max = int(index.shape[0]), int(blocks.shape[2])
+    if blocks.shape != (L, G, n_max, n_max) or index.shape != (G, n_max):
+        raise ValueError(f"cov blocks {tuple(blocks.shape)} / index {tuple(index.shape)} do not fit L = {L}")
+    rows = index[index >= 0].long()
+    if rows.numel() != Nt or (Nt and (int(rows.max()) >= Nt or torch.unique(rows).numel() != Nt)):
+        raise ValueError(f"sample_trajectories: cov's groups hold {rows.numel()} rows, not each of the {Nt} test "
+                         "rows exactly once")
+    if eps is None:
+        eps = torch.randn(int(num_samples), Nt, L, dtype=torch.float64, device=dev, generator=generator)
+    e = eps.detach().to(dev, torch.float64).contiguous()
+    if e.dim() != 3 or e.shape[1:] != (Nt, L):
+        raise ValueError(f"eps must be [S, {Nt}, {L}], got {tuple(e.shape)}")
+    S = int(e.shape[0])
+    out = torch.empty(S, Nt, L, dtype=torch.float64, device=dev)
+    if G == 0:
+        return out
+    info = torch.empty(L * G, dtype=torch.int32, device=dev)
+    ws = torch.empty(int(lib.lvae_predict_sample_workspace_size(L, G, n_max)), dtype=torch.uint8, device=dev)
+    rc = lib.lvae_predict_sample_f64(L, G, n_max, Nt, S, _lib.ptr(blocks), _lib.ptr(index), _lib.ptr(m), _lib.ptr(e),
+                                     float(jitter), _lib.ptr(out), _lib.ptr(info), _lib.ptr(ws), _lib.stream_ptr())
+    _lib.check(rc, "predict_sample")
+    bad = info.nonzero()
+    if bad.numel():
+        b = int(bad[0, 0])
+        raise torch.linalg.LinAlgError(
+            f"sample_trajectories: latent dim {b // G}, group {b % G}: the leading minor of order {int(info[b])} of "
+            f"the covariance + {jitter:g} I is not positive-definite")
+    return out
