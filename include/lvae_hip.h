@@ -152,6 +152,31 @@ int lvae_gram_matvec_f64(const lvae_kernel_spec* spec, const double* x1, int64_t
                          int64_t ld2, int n2, int L, const double* params, const double* diag, const double* v,
                          int64_t ld_v, double* out, int64_t ld_out, void* workspace, void* stream);
 
+/* The same product resolved by additive component of the spec (R = spec->n_comp), fp64, no Gram written:
+ *   out[r, i, l] = sum_{j < n2} s_{l,r} prod_f phi_{r,f}(x1_i, x2_j) v[j, l]           r < R, i < n1, l < L
+ * so that sum_r out[r] is lvae_gram_matvec_f64's out (diag = NULL) up to rounding.  Arguments as there, except:
+ * x2 may differ per latent dim, element (l, j, q) at x2[l*x2_stride_l + j*ld2 + q] (x2_stride_l = 0: one x2 for
+ * every dim; M*Q for inducing inputs [L, M, Q]); out element (r, i, l) at out[r*ostride_r + i*ld_out + l] (nothing
+ * else of out is written); there is no diag.  Kernel family, limits, tiling and the slabs S are
+ * lvae_gram_matvec_f64's; the per-(component, row) sums are kept in LDS, each with one owning lane, tiles added in
+ * column order and slabs in slab order: no atomics, the same bits on every run.  A component whose cross-Gram is
+ * zero everywhere (an id component between disjoint subject sets) gives exact zeros.  workspace:
+ * lvae_gram_matvec_comp_workspace_size(n1, n2, L, R) bytes (partials [L, S, R, n1]; 0 when S == 1, then it may be
+ * NULL), 256-B aligned.
+ * Returns 0, LVAE_ERR_LAUNCH, or before any launch, checked in this order (lvae_gram_matvec_f64's codes where the
+ * two share a fault):
+ *   -1 (spec NULL, outside every template bucket, or a factor dim outside 0 .. 31)
+ *   -4 (n1 < 0) -7 (n2 < 0) -8 (L < 1); then n1 == 0 returns 0 and writes nothing;
+ *   -2 (x1 NULL) -3 (ld1 < 1 + the largest column the spec reads) -5 (x2 NULL) -6 (ld2, as ld1) -9 (params NULL)
+ *   -11 (v NULL) -12 (ld_v < L) -13 (out NULL) -14 (ld_out < L) -16 (x2_stride_l < 0)
+ *   -17 (R > 1 and ostride_r < n1*ld_out) -15 (workspace NULL or misaligned when S > 1).  x2, ld2, x2_stride_l, v
+ *   and ld_v are not checked when n2 == 0: the call then writes zeros to all R blocks [n1, L] and returns 0.   */
+size_t lvae_gram_matvec_comp_workspace_size(int n1, int n2, int L, int n_comp);
+int lvae_gram_matvec_comp_f64(const lvae_kernel_spec* spec, const double* x1, int64_t ld1, int n1, const double* x2,
+                              int64_t ld2, int64_t x2_stride_l, int n2, int L, const double* params, const double* v,
+                              int64_t ld_v, double* out, int64_t ld_out, int64_t ostride_r, void* workspace,
+                              void* stream);
+
 /* ---------------------------------------------------------------------------------------- */
 /* Regime B: exact KL over the full N x N covariance (elbo_functions.py:8-34), batched over L */
 /* latent dims.  Arithmetic: fp32 storage; every GEMM on the f16 matrix cores with the       */
@@ -760,6 +785,41 @@ int lvae_predict_exact_f64(const lvae_kernel_spec* spec, const double* x, int64_
                            const double* params, const double* noise, const double* mu, int64_t ld_mu,
                            const double* tx, int64_t ldt, int nt, double* out, int64_t ld_out, int32_t* info,
                            void* workspace, void* stream);
+
+/* Both posterior means split by additive component of the kernel (each is linear in the kernel, so the split is
+ * exact): what each covariate effect contributes to the predicted latents.
+ *
+ * lvae_predict_exact_comp_f64: lvae_predict_exact_f64's arguments and launches (out and info receive its bits), then
+ *   out_comp[r, t, l] = k_{l,r}(tx_t, x) a_l,   a_l = (k_l(x, x) + noise_l I)^-1 mu[:, l] as refined there,
+ * by lvae_gram_matvec_comp_f64's kernel, element (r, t, l) at out_comp[r*cstride_r + t*ld_comp + l], r < R =
+ * spec->n_comp; sum_r out_comp[r] = out up to rounding.  nt == 0: the factor runs, out and out_comp are untouched.
+ * workspace: lvae_predict_exact_comp_workspace_size(n, nt, L, R) bytes (lvae_predict_exact_f64's + the component
+ * product's slab partials; 0 for n < 1, nt < 0, L < 1 or R < 1), 256-B aligned.
+ * Returns 0, LVAE_ERR_LAUNCH, or before any launch, in this order: -1 .. -16 as lvae_predict_exact_f64; with nt > 0:
+ * -17 (out_comp NULL) -18 (ld_comp < L) -19 (R > 1 and cstride_r < nt*ld_comp).
+ *
+ * lvae_predict_comp_f64: lvae_predict_f64's arguments and launches (out and info receive its bits; the dense
+ * chunked k1 route of the summed mean included), then, with b_l = K0zz^-1 K0zx mu~_l and mu~m_l (mu~_l on the valid
+ * rows of the subjects in the test set, 0 elsewhere) as they are left in the workspace,
+ *   out_comp[r, i, l]      = k0_{l,r}(X*_i, z_l) b_l        r < R0 = spec0->n_comp
+ *   out_comp[R0 + r, i, l] = k1_{l,r}(X*_i, x) mu~m_l       r < R1 = spec1->n_comp
+ * two launches of lvae_gram_matvec_comp_f64's kernel (z per latent dim, x shared), element (r, i, l) at
+ * out_comp[r*cstride_r + i*ld_comp + l]; sum_r out_comp[r] = out up to rounding.  Nt == 0: info is written, out and
+ * out_comp are untouched.  workspace: lvae_predict_comp_workspace_size(L, M, P, T, Nt, R0, R1) bytes, 256-B aligned.
+ * Return codes (before any launch): -1 -3 -6 -8 -13 -20 as lvae_predict_f64, and also -1: a factor dim of either
+ * spec outside 0 .. 31; -6: Q < 1 + the largest column either spec reads; with Nt > 0: -21 (out_comp NULL)
+ * -22 (ld_comp < L) -23 (R0 + R1 > 1 and cstride_r < Nt*ld_comp).  0 = ok.                                  */
+size_t lvae_predict_exact_comp_workspace_size(int n, int nt, int L, int n_comp);
+int lvae_predict_exact_comp_f64(const lvae_kernel_spec* spec, const double* x, int64_t ldx, int n, int L,
+                                const double* params, const double* noise, const double* mu, int64_t ld_mu,
+                                const double* tx, int64_t ldt, int nt, double* out, int64_t ld_out, double* out_comp,
+                                int64_t ld_comp, int64_t cstride_r, int32_t* info, void* workspace, void* stream);
+size_t lvae_predict_comp_workspace_size(int L, int M, int P, int T, int Nt, int n_comp0, int n_comp1);
+int lvae_predict_comp_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, int L, int M, int Q, int P,
+                          int T, const int32_t* seg_len, const int32_t* include, const double* x, const double* mu,
+                          const double* z, int Nt, const double* test_x, const double* params0,
+                          const double* params1, const double* noise, double eps, double* out, double* out_comp,
+                          int64_t ld_comp, int64_t cstride_r, int32_t* info, void* workspace, void* stream);
 
 /* Exact-GP predictive variance (and, optionally, the mean) of the latent functions at test covariates, fp64.  With
  * K_l = k_l(x, x) + noise_l I = L_l L_l^T:

@@ -1558,6 +1558,128 @@ __global__ __launch_bounds__(256) void gram_matvec_sum(const double* __restrict_
   out[(int64_t)i * o_rs + (int64_t)l * o_ls] = acc;
 }
 
+// The same product resolved by additive component (the per-component view of the predictors' means, predict.hip):
+//   out[r][i][l] = sum_j s_{l,r} prod_f phi_{r,f}(x1_i, x2_j) v[j][l],  sum_r out[r] = gram_matvec_tiles' out
+// up to rounding.  gram_matvec_tiles' tiling, staging, tables, gates and masks; its own text of kernel_half64's
+// component loop, because each component's micro-tile is contracted with the staged v at once and never summed
+// into k.  The per-(component, row) sums live in LDS (racc: a register array indexed by the runtime component
+// index would go to scratch): per tile half and component the row's 16 tc lanes reduce by shuffles and the lane
+// tc == 0 adds into its own slot, so every slot has one owner, tiles are added in ascending J, and no barrier or
+// atomic guards racc.  A component whose gates zero the whole wave adds nothing; one whose cross-Gram is zero
+// everywhere leaves its 0.0.  x2 may differ per latent dim (x2_ls: elements between dims, 0: shared): the
+// inducing inputs [L, M, Q].  S == 1 writes out element (r, i, l) at [r o_cs + i o_rs + l o_ls]; S > 1 writes
+// part[l][sl][r][i], summed in slab order by gram_matvec_comp_sum.
+template <int MC, int MF, int QMAX, int NTAB>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void gram_matvec_comp_tiles(
+    DevSpec s, MvCols qc, const double* __restrict__ x1, int64_t ld1, int n1, const double* __restrict__ x2,
+    int64_t ld2, int64_t x2_ls, int n2, const double* __restrict__ params, const double* __restrict__ v, int64_t v_rs,
+    int64_t v_ls, double* __restrict__ out, int64_t o_rs, int64_t o_ls, int64_t o_cs, double* __restrict__ part, int S,
+    int tps) {
+  __shared__ double sx1[kGT * QMAX];
+  __shared__ double sx2[kGT * QMAX];
+  __shared__ double sp[64];
+  __shared__ double sv[kGT];
+  __shared__ double tab[64];
+  __shared__ double itab[MC * MF * NTAB];  // integer-distance tables (distances < NTAB), slot r * MF + f
+  __shared__ double racc[MC][kGT];         // racc[r][row of the tile]: owned by the lane tc == 0 of the row's group
+  const int l = blockIdx.y, I = blockIdx.x / S, sl = blockIdx.x % S, tid = threadIdx.x, tr = tid >> 4, tc = tid & 15;
+  if (tid < 64) tab[tid] = exp2((double)tid / 64.0);
+  if (tid < s.n_params) sp[tid] = params[(int64_t)l * s.n_params + tid];
+  __syncthreads();
+  build_itab64<MC, MF, NTAB>(s, sp, tab, itab);
+  const int i0 = I * kGT, ntc = (n2 + kGT - 1) / kGT;
+  const int J0 = sl * tps, J1 = min(J0 + tps, ntc);
+  for (int e = tid; e < kGT * qc.nq; e += 256) {
+    const int r = e / qc.nq, q = e % qc.nq;
+    sx1[q * kGT + cov_slot(r)] = (i0 + r < n1) ? x1[(int64_t)(i0 + r) * ld1 + qc.col[q]] : 0.0;
+  }
+  if (tc == 0) {
+    for (int r = 0; r < s.n_comp; ++r)
+#pragma unroll
+      for (int a = 0; a < 4; ++a) racc[r][4 * tr + a] = 0.0;
+  }
+  const double* x2l = x2 + (int64_t)l * x2_ls;
+  const double* vl = v + (int64_t)l * v_ls;
+  for (int J = J0; J < J1; ++J) {
+    const int j0 = J * kGT;
+    __syncthreads();  // the previous tile's LDS readers are done (first pass: sx1, sp, itab are written)
+    for (int e = tid; e < kGT * qc.nq; e += 256) {
+      const int r = e / qc.nq, q = e % qc.nq;
+      sx2[q * kGT + cov_slot(r)] = (j0 + r < n2) ? x2l[(int64_t)(j0 + r) * ld2 + qc.col[q]] : 0.0;
+    }
+    if (tid < kGT) sv[tid] = (j0 + tid < n2) ? vl[(int64_t)(j0 + tid) * v_rs] : 0.0;
+    __syncthreads();
+#pragma unroll 1
+    for (int hf = 0; hf < 2; ++hf) {
+#pragma unroll 1
+      for (int r = 0; r < s.n_comp; ++r) {
+        double k[2][4];
+        const double sc = sp[s.scale_idx[r]];
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int c = 0; c < 4; ++c) k[a][c] = sc;
+        // gates first (cheap, exact), then the transcendental factors unless the gates zeroed the wave
+#pragma unroll 1
+        for (int f = 0; f < s.n_fac[r]; ++f) {
+          const int kind = s.kind[r][f];
+          if (kind != LVAE_CAT && kind != LVAE_BIN) continue;
+          apply_factor64<NTAB>(kind, s.dim[r][f], sp, sx1, sx2, tr, tc, hf, k, tab, itab);
+        }
+        bool any = false;
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int c = 0; c < 4; ++c) any |= k[a][c] != 0.0;
+        if (!__any(any)) continue;
+#pragma unroll 1
+        for (int f = 0; f < s.n_fac[r]; ++f) {
+          const int kind = s.kind[r][f];
+          if (kind == LVAE_CAT || kind == LVAE_BIN) continue;
+          const int pi = s.param_idx[r][f];
+          apply_factor64<NTAB>(kind, s.dim[r][f], sp + (pi < 0 ? 0 : pi), sx1, sx2, tr, tc, hf, k, tab,
+                               itab + (r * MF + f) * NTAB);
+        }
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+          const int i = i0 + 4 * tr + 2 * hf + a;
+          double t = 0.0;
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            const int j = j0 + 4 * tc + c;
+            t += ((i >= n1 || j >= n2) ? 0.0 : k[a][c]) * sv[4 * tc + c];
+          }
+#pragma unroll
+          for (int o = 1; o < 16; o <<= 1) t += __shfl_xor(t, o, 64);
+          if (tc == 0) racc[r][4 * tr + 2 * hf + a] += t;
+        }
+      }
+    }
+  }
+  if (tc != 0) return;
+  for (int r = 0; r < s.n_comp; ++r)
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      const int i = i0 + 4 * tr + a;
+      if (i >= n1) continue;
+      const double t = racc[r][4 * tr + a];
+      if (S == 1) out[(int64_t)r * o_cs + (int64_t)i * o_rs + (int64_t)l * o_ls] = t;
+      else part[(((int64_t)l * S + sl) * s.n_comp + r) * n1 + i] = t;
+    }
+}
+
+// out[r][i][l] = sum_s part[l][s][r][i] in slab order (S == 0: zeros, the product over no columns).  Grid
+// (n1 / 256, L, R).
+__global__ __launch_bounds__(256) void gram_matvec_comp_sum(const double* __restrict__ part, int S, int R, int n1,
+                                                            double* __restrict__ out, int64_t o_rs, int64_t o_ls,
+                                                            int64_t o_cs) {
+  const int i = blockIdx.x * 256 + threadIdx.x, l = blockIdx.y, r = blockIdx.z;
+  if (i >= n1) return;
+  double acc = 0.0;
+  for (int s = 0; s < S; ++s) acc += part[(((int64_t)l * S + s) * R + r) * n1 + i];
+  out[(int64_t)r * o_cs + (int64_t)i * o_rs + (int64_t)l * o_ls] = acc;
+}
+
 // per-parameter derivative constants of kl_gram_bwd_tiles' raw sums (host-built from the spec):
 // type 0 scale (1), 1 RBF lengthscale (1 / l^3), 2 PER lengthscale (4 / l^3), 3 PER period
 // (2 pi / (l^2 p^2), l at index ell[p])
@@ -1827,6 +1949,63 @@ int gram_matvec_f64(const lvae_kernel_spec* spec, const double* x1, int64_t ld1,
   return 0;
 }
 
+size_t gram_matvec_comp_ws_bytes(int n1, int n2, int L, int n_comp) {
+  if (n1 <= 0 || n2 <= 0 || L <= 0 || n_comp <= 0) return 0;
+  const int S = matvec_slabs(n1, n2, L, nullptr);
+  return S > 1 ? (size_t)L * S * n_comp * n1 * sizeof(double) : 0;
+}
+
+// The component-resolved fused product (gram_matvec_comp_tiles); v and out in gram_matvec_f64's two layouts, the
+// R = spec->n_comp blocks of out ostride_r elements apart, x2 of latent dim l at x2 + l x2_stride_l.  The slabs are
+// gram_matvec_f64's.  Argument codes are lvae_gram_matvec_comp_f64's.
+int gram_matvec_comp_f64(const lvae_kernel_spec* spec, const double* x1, int64_t ld1, int n1, const double* x2,
+                         int64_t ld2, int64_t x2_stride_l, int n2, int L, const double* params, const double* v,
+                         int64_t ld_v, int v_t, double* out, int64_t ld_out, int o_t, int64_t ostride_r,
+                         void* workspace, hipStream_t st) {
+  if (!spec) return -1;
+  const int bucket = spec_bucket(spec);
+  DevSpec ds;
+  MvCols qc;
+  int ld_min = 1;
+  if (!bucket || !matvec_cols(spec, ds, qc, &ld_min)) return -1;
+  if (n1 < 0) return -4;
+  if (n2 < 0) return -7;
+  if (L < 1) return -8;
+  if (n1 == 0) return 0;
+  if (!x1) return -2;
+  if (ld1 < ld_min) return -3;
+  if (n2 > 0 && !x2) return -5;
+  if (n2 > 0 && ld2 < ld_min) return -6;
+  if (!params) return -9;
+  if (n2 > 0 && !v) return -11;
+  if (n2 > 0 && ld_v < (v_t ? n2 : L)) return -12;
+  if (!out) return -13;
+  if (ld_out < (o_t ? n1 : L)) return -14;
+  if (n2 > 0 && x2_stride_l < 0) return -16;
+  const int R = spec->n_comp;
+  if (R > 1 && ostride_r < (int64_t)(o_t ? L : n1) * ld_out) return -17;
+  const int64_t v_rs = v_t ? 1 : ld_v, v_ls = v_t ? ld_v : 1, o_rs = o_t ? 1 : ld_out, o_ls = o_t ? ld_out : 1;
+  int tps = 1;
+  const int S = n2 > 0 ? matvec_slabs(n1, n2, L, &tps) : 0;
+  if (S > 1 && (!workspace || ((uintptr_t)workspace & 255))) return -15;
+  double* part = (double*)workspace;
+  if (S >= 1) {
+    const dim3 grid(cdiv(n1, kGT) * S, L);
+    // gram_matvec_f64's three LDS images, each with racc on top (4 KiB for 8 components, 8 KiB for 16)
+#define LVAE_MVC_LAUNCH(MC, MF, Q, NT)                                                                              \
+  gram_matvec_comp_tiles<MC, MF, Q, NT><<<grid, 256, 0, st>>>(ds, qc, x1, ld1, n1, x2, ld2, x2_stride_l, n2, params, \
+                                                              v, v_rs, v_ls, out, o_rs, o_ls, ostride_r, part, S, tps)
+    if (bucket == 1) LVAE_MVC_LAUNCH(8, 2, kMaxQB, kIntTab);
+    else if (qc.nq <= kMaxQB) LVAE_MVC_LAUNCH(16, 4, kMaxQB, kIntTab);
+    else LVAE_MVC_LAUNCH(16, 4, kMaxQ, 16);
+#undef LVAE_MVC_LAUNCH
+  }
+  if (S != 1)
+    gram_matvec_comp_sum<<<dim3(cdiv(n1, 256), L, R), 256, 0, st>>>(part, S, R, n1, out, o_rs, o_ls, ostride_r);
+  LVAE_CHECK_LAUNCH();
+  return 0;
+}
+
 // workgroups per latent dim of the adjoint: ~1536 in all, each looping over ~ntiles / G tiles
 static int kl_gram_bwd_groups(int np_, int L) {
   const int nt = np_ / kGT, ntiles = nt * (nt + 1) / 2;
@@ -2004,6 +2183,18 @@ int lvae_gram_matvec_f64(const lvae_kernel_spec* spec, const double* x1, int64_t
                          int64_t ld_v, double* out, int64_t ld_out, void* workspace, void* stream) {
   return lvae::gram_matvec_f64(spec, x1, ld1, n1, x2, ld2, n2, L, params, diag, v, ld_v, 0, out, ld_out, 0, workspace,
                                (hipStream_t)stream);
+}
+
+size_t lvae_gram_matvec_comp_workspace_size(int n1, int n2, int L, int n_comp) {
+  return lvae::gram_matvec_comp_ws_bytes(n1, n2, L, n_comp);
+}
+
+int lvae_gram_matvec_comp_f64(const lvae_kernel_spec* spec, const double* x1, int64_t ld1, int n1, const double* x2,
+                              int64_t ld2, int64_t x2_stride_l, int n2, int L, const double* params, const double* v,
+                              int64_t ld_v, double* out, int64_t ld_out, int64_t ostride_r, void* workspace,
+                              void* stream) {
+  return lvae::gram_matvec_comp_f64(spec, x1, ld1, n1, x2, ld2, x2_stride_l, n2, L, params, v, ld_v, 0, out, ld_out, 0,
+                                    ostride_r, workspace, (hipStream_t)stream);
 }
 
 size_t lvae_gram_bwd_workspace_size(int nb, int L, int n1, int n2) {

@@ -18,6 +18,8 @@
 // lvae_predict_exact_var_f64 and lvae_predict_var_f64 below, their kernels and formulas in predict_var.hpp.
 // lvae_predict_cov_f64 and lvae_predict_exact_cov_f64 form the joint covariance of each group of test rows from the
 // same buffers, and lvae_predict_sample_f64 draws whole trajectories from it (kernels in predict_cov.hpp).
+// lvae_predict_exact_comp_f64 and lvae_predict_comp_f64 split the two means by additive component of the kernel
+// (both are linear in it): the same launches, then gram.hip's component-resolved cross-Gram x vector.
 #include "small.hpp"
 #include "prof.hpp"
 #include "predict_var.hpp"
@@ -236,6 +238,10 @@ int gram_matvec_f64(const lvae_kernel_spec* spec, const double* x1, int64_t ld1,
                     int n2, int L, const double* params, const double* diag, const double* v, int64_t ld_v, int v_t,
                     double* out, int64_t ld_out, int o_t, void* workspace, hipStream_t st);
 int gram_matvec_spec_ld(const lvae_kernel_spec* spec);
+int gram_matvec_comp_f64(const lvae_kernel_spec* spec, const double* x1, int64_t ld1, int n1, const double* x2,
+                         int64_t ld2, int64_t x2_stride_l, int n2, int L, const double* params, const double* v,
+                         int64_t ld_v, int v_t, double* out, int64_t ld_out, int o_t, int64_t ostride_r,
+                         void* workspace, hipStream_t st);
 }  // namespace lvae
 
 using namespace lvae;
@@ -410,6 +416,47 @@ int lvae_predict_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec
                       eps, out, true, nullptr, info, w, stream);
 }
 
+static size_t predict_comp_mv_bytes(int L, int M, int P, int T, int Nt, int n_comp0, int n_comp1) {
+  const size_t m0 = lvae_gram_matvec_comp_workspace_size(Nt, M, L, n_comp0);
+  const size_t m1 = lvae_gram_matvec_comp_workspace_size(Nt, P * T, L, n_comp1);
+  return align256(m0 > m1 ? m0 : m1);
+}
+
+size_t lvae_predict_comp_workspace_size(int L, int M, int P, int T, int Nt, int n_comp0, int n_comp1) {
+  return lvae_predict_workspace_size(L, M, P, T, Nt) + predict_comp_mv_bytes(L, M, P, T, Nt, n_comp0, n_comp1);
+}
+
+int lvae_predict_comp_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, int L, int M, int Q, int P,
+                          int T, const int32_t* seg_len, const int32_t* include, const double* x, const double* mu,
+                          const double* z, int Nt, const double* test_x, const double* params0, const double* params1,
+                          const double* noise, double eps, double* out, double* out_comp, int64_t ld_comp,
+                          int64_t cstride_r, int32_t* info, void* workspace, void* stream) {
+  if (!spec0 || !spec1 || !spec_bucket(spec0) || !spec_bucket(spec1)) return -1;  // (before any launch)
+  const int ld0 = gram_matvec_spec_ld(spec0), ld1 = gram_matvec_spec_ld(spec1);
+  if (ld0 < 1 || ld1 < 1) return -1;  // (a factor dim outside 0 .. 31: the fused product does not take it)
+  if (L < 1 || M < 1 || M > 128) return -3;
+  if (P < 1 || T < 1 || T > 128 || Q < 1 || Q < ld0 || Q < ld1) return -6;
+  if (!seg_len || !include) return -8;
+  if (Nt < 0) return -13;
+  if (!workspace || ((uintptr_t)workspace & 255)) return -20;
+  if (Nt > 0 && !out_comp) return -21;
+  if (Nt > 0 && ld_comp < L) return -22;
+  if (Nt > 0 && spec0->n_comp + spec1->n_comp > 1 && cstride_r < (int64_t)Nt * ld_comp) return -23;
+  PWs w((char*)workspace, L, M, P, T, Nt > 0 ? Nt : 1);
+  // the mean by lvae_predict_f64's own launches (its dense chunked K1 route included), then per component
+  // k0_r(X*, z_l) b_l (blocks 0 .. R0 - 1) and k1_r(X*, x) mu~m_l (blocks R0 .. R0 + R1 - 1) on the b and mu~m they
+  // leave in the workspace; mu~m is 0 on padding rows and on subjects outside the test set
+  LVAE_TRY(predict_core(spec0, spec1, L, M, Q, P, T, seg_len, include, x, mu, z, Nt, test_x, params0, params1, noise,
+                        eps, out, true, nullptr, info, w, stream));
+  if (Nt == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  void* mv = (char*)workspace + align256(w.bytes);
+  LVAE_TRY(gram_matvec_comp_f64(spec0, test_x, Q, Nt, z, Q, (int64_t)M * Q, M, L, params0, w.b, M, 1, out_comp, ld_comp,
+                                0, cstride_r, mv, st));
+  return gram_matvec_comp_f64(spec1, test_x, Q, Nt, x, Q, 0, P * T, L, params1, w.muTm, (int64_t)P * T, 1,
+                              out_comp + (int64_t)spec0->n_comp * cstride_r, ld_comp, 0, cstride_r, mv, st);
+}
+
 size_t lvae_predict_exact_workspace_size(int n, int nt, int L) {
   if (n < 1 || nt < 0 || L < 1) return 0;
   return EWs(nullptr, n, nt, L).bytes;
@@ -438,6 +485,44 @@ int lvae_predict_exact_f64(const lvae_kernel_spec* spec, const double* x, int64_
   if (!workspace || ((uintptr_t)workspace & 255)) return -16;
   EWs w((char*)workspace, n, nt, L);
   return exact_core(spec, x, ldx, n, L, params, noise, mu, ld_mu, tx, ldt, nt, out, ld_out, info, w, stream);
+}
+
+size_t lvae_predict_exact_comp_workspace_size(int n, int nt, int L, int n_comp) {
+  if (n < 1 || nt < 0 || L < 1 || n_comp < 1) return 0;
+  return EWs(nullptr, n, nt, L).bytes + align256(lvae_gram_matvec_comp_workspace_size(nt, n, L, n_comp));
+}
+
+int lvae_predict_exact_comp_f64(const lvae_kernel_spec* spec, const double* x, int64_t ldx, int n, int L,
+                                const double* params, const double* noise, const double* mu, int64_t ld_mu,
+                                const double* tx, int64_t ldt, int nt, double* out, int64_t ld_out, double* out_comp,
+                                int64_t ld_comp, int64_t cstride_r, int32_t* info, void* workspace, void* stream) {
+  const int ld_min = spec ? gram_matvec_spec_ld(spec) : 0;
+  if (ld_min < 1 || ld_min > 32) return -1;  // (before any launch)
+  if (!x) return -2;
+  if (ldx < ld_min) return -3;
+  if (n < 1) return -4;
+  if (L < 1) return -5;
+  if (!params) return -6;
+  if (!noise) return -7;
+  if (!mu) return -8;
+  if (ld_mu < L) return -9;
+  if (nt < 0) return -12;
+  if (nt > 0 && !tx) return -10;
+  if (nt > 0 && ldt < ld_min) return -11;
+  if (nt > 0 && !out) return -13;
+  if (nt > 0 && ld_out < L) return -14;
+  if (!info) return -15;
+  if (!workspace || ((uintptr_t)workspace & 255)) return -16;
+  if (nt > 0 && !out_comp) return -17;
+  if (nt > 0 && ld_comp < L) return -18;
+  if (nt > 0 && spec->n_comp > 1 && cstride_r < (int64_t)nt * ld_comp) return -19;
+  EWs w((char*)workspace, n, nt, L);
+  // the factor and the mean by lvae_predict_exact_f64's own launches, then k_r(X*, x) a per component r on the
+  // refined a they leave in the workspace
+  LVAE_TRY(exact_core(spec, x, ldx, n, L, params, noise, mu, ld_mu, tx, ldt, nt, out, ld_out, info, w, stream));
+  if (nt == 0) return 0;
+  return gram_matvec_comp_f64(spec, tx, ldt, nt, x, ldx, 0, n, L, params, w.a, n, 1, out_comp, ld_comp, 0, cstride_r,
+                              (char*)workspace + w.bytes, (hipStream_t)stream);
 }
 
 size_t lvae_predict_exact_var_workspace_size(int n, int nt, int L, int chunk) {

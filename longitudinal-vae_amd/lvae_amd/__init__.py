@@ -22,9 +22,11 @@ from .likelihoods import GaussianLikelihood  # noqa: F401
 from .elbo import (HensmanPrior, KL_closed, KL_closed_batched, check_pending, kl_closed_prefactor,  # noqa: F401
                    minibatch_KLD_upper_bound, minibatch_KLD_upper_bound_iter, natural_gradient_update,
                    set_sync_checks)
-from .predict import (PredictiveCovariance, batch_predict_varying_T, predict_exact, sample_predictions,  # noqa: F401
+from .predict import (LatentComponents, PredictiveCovariance, batch_predict_components,  # noqa: F401
+                      batch_predict_varying_T, predict_exact, predict_exact_components, sample_predictions,
                       sample_trajectories)
-from .evaluation import MSE_test, MSE_test_GPapprox, generate_trajectories  # noqa: F401
+from .evaluation import (MSE_test, MSE_test_GPapprox, generate_component_sequences,  # noqa: F401
+                         generate_trajectories)
 from .vae import ConvVAE, SimpleVAE  # noqa: F401
 from .data import HealthMNISTDataset, HealthMNISTDatasetConv, PhysionetDataset  # noqa: F401
 from .gpapprox import (DuboCondition, condition_dubo, condition_dubo_varying_T, deviance_upper_bound,  # noqa: F401

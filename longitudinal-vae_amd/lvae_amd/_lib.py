@@ -209,6 +209,15 @@ SIGNATURES = {
     "lvae_predict_exact_workspace_size": (_SZ, [_I32, _I32, _I32]),
     "lvae_predict_exact_f64": (_I32, [_SPEC, _VP, _I64, _I32, _I32, _VP, _VP, _VP, _I64, _VP, _I64, _I32, _VP, _I64,
                                       _VP, _VP, _VP]),
+    "lvae_gram_matvec_comp_workspace_size": (_SZ, [_I32, _I32, _I32, _I32]),
+    "lvae_gram_matvec_comp_f64": (_I32, [_SPEC, _VP, _I64, _I32, _VP, _I64, _I64, _I32, _I32, _VP, _VP, _I64, _VP,
+                                         _I64, _I64, _VP, _VP]),
+    "lvae_predict_exact_comp_workspace_size": (_SZ, [_I32, _I32, _I32, _I32]),
+    "lvae_predict_exact_comp_f64": (_I32, [_SPEC, _VP, _I64, _I32, _I32, _VP, _VP, _VP, _I64, _VP, _I64, _I32, _VP,
+                                           _I64, _VP, _I64, _I64, _VP, _VP, _VP]),
+    "lvae_predict_comp_workspace_size": (_SZ, [_I32, _I32, _I32, _I32, _I32, _I32, _I32]),
+    "lvae_predict_comp_f64": (_I32, [_SPEC, _SPEC, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _I32, _VP,
+                                     _VP, _VP, _VP, _D, _VP, _VP, _I64, _I64, _VP, _VP, _VP]),
     "lvae_predict_exact_var_workspace_size": (_SZ, [_I32, _I32, _I32, _I32]),
     "lvae_predict_exact_var_f64": (_I32, [_SPEC, _VP, _I64, _I32, _I32, _VP, _VP, _VP, _I64, _VP, _I64, _I32, _VP,
                                           _I64, _VP, _I64, _I32, _I32, _VP, _VP, _VP]),

@@ -27,7 +27,10 @@ KEEP_ROWS, SAMPLE_ROWS = 40, 6000   # model_test.py:59-61
 
 
 def predict_gp(kernel_component, full_kernel_inverse, z):
-    """Predictive mean kernel_component @ full_kernel_inverse @ z (model_test.py:11-17)."""
+    """Predictive mean kernel_component @ full_kernel_inverse @ z (model_test.py:11-17).  With one additive
+    component's cross-Gram as ``kernel_component`` this is that component's share of the predicted latents;
+    predict_exact_components and batch_predict_components return all the shares at once without the dense Gram or
+    the explicit inverse."""
     return torch.matmul(torch.matmul(kernel_component, full_kernel_inverse), z)
 
 
@@ -141,6 +144,25 @@ def generate_trajectories(nnet_model, mean, cov=None, num_samples=0, eps=None, g
         if z.shape[0] == 0:
             return images, images.new_empty((0,) + tuple(images.shape))
         return images, torch.stack([decode(zs) for zs in z])
+
+
+def generate_component_sequences(nnet_model, comps, order=None):
+    """Decoded images as the covariate effects are added one by one: ``[R', Nt, ...]``, entry r the decoder's output
+    at the partial sum ``comps.values[order[:r + 1]].sum(0)`` of a LatentComponents (``predict_exact_components``,
+    ``batch_predict_components``).  ``order`` lists the components to add, in that order (default: all R, as
+    stored); with every component in it the last entry is ``decode(comps.total())``.  The split is additive in the
+    latent space only: the decoder is not linear, so the images are NOT additive in image space, an entry is the
+    reconstruction with the effects so far, and the difference of two entries is not "the image of" a component
+    (it depends on the order).  Uses ``nnet_model.decode`` (ConvVAE or SimpleVAE, in the mode the caller left it
+    in); no gradients are recorded."""
+    R = int(comps.values.shape[0])
+    order = list(range(R)) if order is None else [int(r) for r in order]
+    if not order or any(r < 0 or r >= R for r in order):
+        raise ValueError(f"order {order} must name at least one component, each in 0 .. {R - 1}")
+    dtype = next(nnet_model.parameters()).dtype
+    idx = torch.tensor(order, dtype=torch.long, device=comps.values.device)
+    with torch.no_grad():
+        return torch.stack([nnet_model.decode(comps.values[idx[:r + 1]].sum(0).to(dtype)) for r in range(len(order))])
 
 
 def VAEtest(test_dataset, nnet_model, type_nnet, id_covariate):

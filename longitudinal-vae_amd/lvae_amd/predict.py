@@ -81,27 +81,10 @@ def _group_index(order, counts, start, n_max, dev):
     return index.to(dev)
 
 
-def batch_predict_varying_T(latent_dim, covar_module0, covar_module1, likelihoods, prediction_x, test_x, mu,
-                            zt_list, id_covariate, eps, return_var=False, add_noise=False, return_cov=False):
-    """Z_pred [N_test, L]: posterior mean of the L latent GPs at ``test_x`` given the encoder means
-    ``mu`` [N_pred, L] at ``prediction_x`` (subjects of any length).  ``covar_module0/1`` are
-    batched modules or per-dim lists, ``zt_list`` the inducing points [L, M, Q] (or a per-dim
-    list of [M, Q]).
-
-    ``return_var=True`` returns ``(Z_pred, Z_var)``: Z_var [N_test, L] fp64 is the predictive variance of the
-    latent functions in the same structured model (lvae_predict_var_f64; K0xz K0zz^-1 K0zx + blockdiag k1 as
-    the prior), clamped at 0, in the caller's row order; ``add_noise=True`` adds the likelihood noise of each
-    dim.  The id kernel ``covar_module1`` must vanish between subjects (generate_kernel_batched's does).
-
-    ``return_cov=True`` returns ``(Z_pred, cov)`` instead: ``cov`` is a PredictiveCovariance with one group per test
-    subject (the rows sharing ``test_x[:, id_covariate]``), its blocks the joint covariance of the subject's rows
-    in the same model (lvae_predict_cov_f64), not clamped; ``add_noise=True`` adds the noise to the diagonals.  A
-    subject with more than 128 test rows raises ValueError.  The covariance between different subjects' rows is
-    not zero (the shared components couple subjects) and is deliberately not returned: sample_trajectories draws
-    the groups independently of each other."""
-    if return_var and return_cov:
-        raise ValueError("return_var and return_cov are exclusive: cov.diagonal() holds the variances")
-    lib = _lib.lib()
+def _inducing_inputs(latent_dim, covar_module0, covar_module1, likelihoods, prediction_x, test_x, mu, zt_list,
+                     id_covariate):
+    """The arguments of batch_predict_varying_T as lvae_predict_f64 and its siblings take them: the modules in eval
+    mode, everything fp64 on mu's device, the prediction set gathered into the padded [P, T] subject layout"""
     L = int(latent_dim)
     spec0, params0 = _stack_modules(covar_module0)
     spec1, params1 = _stack_modules(covar_module1)
@@ -132,9 +115,34 @@ def batch_predict_varying_T(latent_dim, covar_module0, covar_module1, likelihood
     x_pad = f64(prediction_x)[g].contiguous()
     mu_pad = (f64(mu)[g] * valid.to(dev, torch.float64).unsqueeze(1)).contiguous()
     tx = f64(test_x)
-    Nt = int(tx.shape[0])
-    seg_d, inc_d = seg.to(dev), include.to(dev)
-    p0, p1 = f64(params0), f64(params1)
+    return (L, spec0, spec1, f64(params0), f64(params1), dev, z, M, Q, noise, seg.to(dev), include.to(dev), T, P,
+            pred_ids, x_pad, mu_pad, tx, int(tx.shape[0]))
+
+
+def batch_predict_varying_T(latent_dim, covar_module0, covar_module1, likelihoods, prediction_x, test_x, mu,
+                            zt_list, id_covariate, eps, return_var=False, add_noise=False, return_cov=False):
+    """Z_pred [N_test, L]: posterior mean of the L latent GPs at ``test_x`` given the encoder means
+    ``mu`` [N_pred, L] at ``prediction_x`` (subjects of any length).  ``covar_module0/1`` are
+    batched modules or per-dim lists, ``zt_list`` the inducing points [L, M, Q] (or a per-dim
+    list of [M, Q]).
+
+    ``return_var=True`` returns ``(Z_pred, Z_var)``: Z_var [N_test, L] fp64 is the predictive variance of the
+    latent functions in the same structured model (lvae_predict_var_f64; K0xz K0zz^-1 K0zx + blockdiag k1 as
+    the prior), clamped at 0, in the caller's row order; ``add_noise=True`` adds the likelihood noise of each
+    dim.  The id kernel ``covar_module1`` must vanish between subjects (generate_kernel_batched's does).
+
+    ``return_cov=True`` returns ``(Z_pred, cov)`` instead: ``cov`` is a PredictiveCovariance with one group per test
+    subject (the rows sharing ``test_x[:, id_covariate]``), its blocks the joint covariance of the subject's rows
+    in the same model (lvae_predict_cov_f64), not clamped; ``add_noise=True`` adds the noise to the diagonals.  A
+    subject with more than 128 test rows raises ValueError.  The covariance between different subjects' rows is
+    not zero (the shared components couple subjects) and is deliberately not returned: sample_trajectories draws
+    the groups independently of each other."""
+    if return_var and return_cov:
+        raise ValueError("return_var and return_cov are exclusive: cov.diagonal() holds the variances")
+    lib = _lib.lib()
+    (L, spec0, spec1, p0, p1, dev, z, M, Q, noise, seg_d, inc_d, T, P, pred_ids, x_pad, mu_pad, tx,
+     Nt) = _inducing_inputs(latent_dim, covar_module0, covar_module1, likelihoods, prediction_x, test_x, mu, zt_list,
+                            id_covariate)
     out = torch.empty(Nt, L, dtype=torch.float64, device=dev)
     info = torch.empty(L, dtype=torch.int32, device=dev)
     if return_cov:
@@ -194,6 +202,29 @@ def batch_predict_varying_T(latent_dim, covar_module0, covar_module1, likelihood
     return out
 
 
+def _exact_inputs(covar_module, likelihoods, prediction_x, test_x, prediction_mu):
+    """The arguments of predict_exact as lvae_predict_exact_f64 and its siblings take them: the modules in eval
+    mode, everything fp64 on prediction_mu's device"""
+    spec, params = _stack_modules(covar_module)
+    L = int(prediction_mu.shape[1])
+    if params.shape[0] == 1 and L > 1:
+        params = params.expand(L, -1)
+    if params.shape[0] != L:
+        raise ValueError(f"kernel batch {params.shape[0]} != latent dims {L}")
+    for mod in (covar_module, likelihoods):
+        for m_ in (mod if isinstance(mod, (list, tuple, torch.nn.ModuleList)) else [mod]):
+            if hasattr(m_, "eval"):
+                m_.eval()
+    dev = prediction_mu.device
+    f64 = lambda t: t.detach().to(dev, torch.float64).contiguous()
+    x, tx, mu, p = f64(prediction_x), f64(test_x), f64(prediction_mu), f64(params)
+    noise = f64(_noise_vector(likelihoods, L)).reshape(L)
+    n, nt, n_params = int(x.shape[0]), int(tx.shape[0]), int(p.shape[1])
+    if n < 1 or mu.shape[0] != n:
+        raise ValueError(f"prediction_mu rows {mu.shape[0]} != prediction_x rows {n} (>= 1)")
+    return spec, L, dev, x, tx, mu, p, noise, n, nt, n_params
+
+
 def predict_exact(covar_module, likelihoods, prediction_x, test_x, prediction_mu, max_workspace_bytes=4 << 30,
                   return_var=False, add_noise=False, return_cov=False, groups=None):
     """Z_pred [N_test, L] fp64: the exact-GP posterior mean k(X*, X) (k(X, X) + noise I)^-1 mu per latent dim
@@ -220,23 +251,8 @@ def predict_exact(covar_module, likelihoods, prediction_x, test_x, prediction_mu
     if return_var and return_cov:
         raise ValueError("return_var and return_cov are exclusive: cov.diagonal() holds the variances")
     lib = _lib.lib()
-    spec, params = _stack_modules(covar_module)
-    L = int(prediction_mu.shape[1])
-    if params.shape[0] == 1 and L > 1:
-        params = params.expand(L, -1)
-    if params.shape[0] != L:
-        raise ValueError(f"kernel batch {params.shape[0]} != latent dims {L}")
-    for mod in (covar_module, likelihoods):
-        for m_ in (mod if isinstance(mod, (list, tuple, torch.nn.ModuleList)) else [mod]):
-            if hasattr(m_, "eval"):
-                m_.eval()
-    dev = prediction_mu.device
-    f64 = lambda t: t.detach().to(dev, torch.float64).contiguous()
-    x, tx, mu, p = f64(prediction_x), f64(test_x), f64(prediction_mu), f64(params)
-    noise = f64(_noise_vector(likelihoods, L)).reshape(L)
-    n, nt, n_params = int(x.shape[0]), int(tx.shape[0]), int(p.shape[1])
-    if n < 1 or mu.shape[0] != n:
-        raise ValueError(f"prediction_mu rows {mu.shape[0]} != prediction_x rows {n} (>= 1)")
+    spec, L, dev, x, tx, mu, p, noise, n, nt, n_params = _exact_inputs(covar_module, likelihoods, prediction_x, test_x,
+                                                                       prediction_mu)
     chunk = 1   # (the smallest panel decides the dim groups; the chunk then takes what is left)
     if return_cov:
         labels = torch.zeros(nt) if groups is None else groups
@@ -309,6 +325,99 @@ def predict_exact(covar_module, likelihoods, prediction_x, test_x, prediction_mu
     if return_var:
         return out, var.clamp_(min=0.0)
     return out
+
+
+class LatentComponents:
+    """A posterior mean of the latents split by additive component of the kernel: what each covariate effect
+    contributes (both predictors are linear in the kernel, so the split is exact).
+
+    ``values`` [R, Nt, L] fp64: component r's share of Z_pred, in the caller's row order.  ``labels`` [R]: the
+    component's factors, e.g. ``"rbf(0)"`` or ``"cat(3)*rbf(0)"`` (kind(covariate column); a masked factor carries
+    its ``*bin(d)``).  ``module`` [R]: 0 for a component of ``covar_module0`` (or of the exact route's one kernel),
+    1 for one of ``covar_module1``; the components of module 0 come first."""
+
+    def __init__(self, values, labels, module):
+        self.values, self.labels, self.module = values, list(labels), list(module)
+
+    def total(self):
+        """[Nt, L]: the sum over components, Z_pred up to rounding"""
+        return self.values.sum(0)
+
+    def explained_variance(self):
+        """[R, L]: the population variance over the test rows of each component, divided by the sum of those
+        variances over the components (0 where that sum is 0: every component constant over the rows).  The
+        covariances between components are ignored, so the shares describe the components one at a time and do
+        not decompose the variance of ``total()``."""
+        var = self.values.var(dim=1, unbiased=False) if self.values.shape[1] else self.values.new_zeros(
+            self.values.shape[0], self.values.shape[2])
+        den = var.sum(0, keepdim=True)
+        return torch.where(den > 0, var / torch.where(den > 0, den, torch.ones_like(den)), torch.zeros_like(var))
+
+
+def component_labels(covar_module):
+    """The labels of a kernel's additive components, from ``kernel.components()`` (a per-dim list: its first
+    module's): the factors as kind(column) joined by ``*``."""
+    mod = covar_module[0] if isinstance(covar_module, (list, tuple, torch.nn.ModuleList)) else covar_module
+    names = {v: k for k, v in _lib.KIND_CODE.items()}
+    return ["*".join(f"{names.get(k, k)}({int(d)})" for k, d in facs) for facs, _ in mod.components()]
+
+
+def predict_exact_components(covar_module, likelihoods, prediction_x, test_x, prediction_mu,
+                             max_workspace_bytes=4 << 30):
+    """``(Z_pred, comps)``: ``predict_exact``'s Z_pred [N_test, L] (the same launches, the same bits) and its split
+    by additive component of ``covar_module`` as a LatentComponents, ``comps.values[r] = k_r(X*, X) alpha`` with
+    alpha = (k(X, X) + noise I)^-1 mu as the mean uses it (lvae_predict_exact_comp_f64: one fused pass over the
+    cross-Gram for all components, no [N_test, N] Gram formed).  Arguments, the dim groups under
+    ``max_workspace_bytes`` and the errors are ``predict_exact``'s; the groups do not change the bits."""
+    lib = _lib.lib()
+    spec, L, dev, x, tx, mu, p, noise, n, nt, n_params = _exact_inputs(covar_module, likelihoods, prediction_x, test_x,
+                                                                       prediction_mu)
+    R = int(spec.n_comp)
+    size = lambda g: int(lib.lvae_predict_exact_comp_workspace_size(n, nt, g, R))
+    group = L
+    while group > 1 and size(group) > max_workspace_bytes:
+        group -= 1
+    out = torch.empty(nt, L, dtype=torch.float64, device=dev)
+    vals = torch.empty(R, nt, L, dtype=torch.float64, device=dev)
+    info = torch.empty(L, dtype=torch.int32, device=dev)
+    ws = torch.empty(size(group), dtype=torch.uint8, device=dev)
+    at = lambda t, off: ctypes.c_void_p(t.data_ptr() + 8 * off)
+    for l0 in range(0, L, group):
+        g = min(group, L - l0)
+        rc = lib.lvae_predict_exact_comp_f64(spec, _lib.ptr(x), x.stride(0), n, g, at(p, l0 * n_params),
+                                             at(noise, l0), at(mu, l0), L, _lib.ptr(tx) if nt else None,
+                                             tx.stride(0), nt, at(out, l0) if nt else None, L,
+                                             at(vals, l0) if nt else None, L, nt * L,
+                                             ctypes.c_void_p(info.data_ptr() + 4 * l0), _lib.ptr(ws),
+                                             _lib.stream_ptr())
+        _lib.check(rc, "predict_exact_comp")
+    _check_info(info, "predict_exact cholesky of k(X, X) + noise I")
+    return out, LatentComponents(vals, component_labels(covar_module), [0] * R)
+
+
+def batch_predict_components(latent_dim, covar_module0, covar_module1, likelihoods, prediction_x, test_x, mu,
+                             zt_list, id_covariate, eps):
+    """``(Z_pred, comps)``: ``batch_predict_varying_T``'s Z_pred [N_test, L] (the same launches, the same bits) and
+    its split by additive component as a LatentComponents: the components of ``covar_module0`` first,
+    ``k0_r(X*, z) K0zz^-1 K0zx mu~``, then those of ``covar_module1``, ``k1_r(X*, x) mu~`` over the prediction rows
+    of the test subjects (lvae_predict_comp_f64).  Arguments and errors are ``batch_predict_varying_T``'s."""
+    lib = _lib.lib()
+    (L, spec0, spec1, p0, p1, dev, z, M, Q, noise, seg_d, inc_d, T, P, pred_ids, x_pad, mu_pad, tx,
+     Nt) = _inducing_inputs(latent_dim, covar_module0, covar_module1, likelihoods, prediction_x, test_x, mu, zt_list,
+                            id_covariate)
+    R0, R1 = int(spec0.n_comp), int(spec1.n_comp)
+    out = torch.empty(Nt, L, dtype=torch.float64, device=dev)
+    vals = torch.empty(R0 + R1, Nt, L, dtype=torch.float64, device=dev)
+    info = torch.empty(L, dtype=torch.int32, device=dev)
+    ws = torch.empty(int(lib.lvae_predict_comp_workspace_size(L, M, P, T, Nt, R0, R1)), dtype=torch.uint8, device=dev)
+    rc = lib.lvae_predict_comp_f64(spec0, spec1, L, M, Q, P, T, _lib.ptr(seg_d), _lib.ptr(inc_d), _lib.ptr(x_pad),
+                                   _lib.ptr(mu_pad), _lib.ptr(z), Nt, _lib.ptr(tx), _lib.ptr(p0), _lib.ptr(p1),
+                                   _lib.ptr(noise), float(eps), _lib.ptr(out), _lib.ptr(vals) if Nt else None, L,
+                                   Nt * L, _lib.ptr(info), _lib.ptr(ws), _lib.stream_ptr())
+    _lib.check(rc, "predict_comp")
+    _check_info(info, "batch_predict_varying_T cholesky (10000+col: K0zz, 20000+col: B_st, 30000+col: H)")
+    labels = component_labels(covar_module0) + component_labels(covar_module1)
+    return out, LatentComponents(vals, labels, [0] * R0 + [1] * R1)
 
 
 def sample_predictions(mean, var, eps=None, generator=None):
