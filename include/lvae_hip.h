@@ -45,7 +45,8 @@ extern "C" {
 #define LVAE_MAX_FAC 4     /* product factors per component                   */
 #define LVAE_ERR_LAUNCH (-1000)
 
-/* factor kinds (GP_model.py:31-85; periodic/linear are extensions, parity unpinned) */
+/* factor kinds (GP_model.py:31-85).  Periodic and linear are extensions: parity with the reference is undefined
+ * (it has no such kernel); agreement with the fp64 oracle is pinned for every entry point that takes a spec. */
 enum lvae_factor_kind {
   LVAE_CAT = 0,   /* 1[x1_d == x2_d]                                  GP_model.py:52-53 */
   LVAE_BIN = 1,   /* 1[x1_d + x2_d == 2]                              GP_model.py:40-41 */
@@ -600,10 +601,12 @@ int lvae_dubo_cond_eval_f64(int L, int Pn, int T, const void* state, const doubl
  * (the last as d/dx2 against dKz[l]^T; the jitter does not depend on z).  dz [L, M, Q] is OVERWRITTEN; columns of
  * categorical / binary factors and unread columns get exact zeros.  No atomics: the same bits on every call.
  * The DUBO's and the ELBO's calls first re-form dKz in zworkspace with its terms iK Q iK and iW R iW built from
- * N x M factors ((X iK)^T (iBK iK), (iBK iW)^T B_p (F iW)): with inducing rows that coincide for k0, the backward's
- * (iK Q) iK carries rounding times 1 / eps in directions the hyper-parameter adjoint is blind to and dz is not
- * (gp_bound.hpp).  The Hensman call reads dK0zz as the backward left it.  None of this writes the bound's own
- * workspace: the backward may run again on it, and so may these calls.
+ * N x M factors ((X iK)^T (iBK iK), (iBK iW)^T B_p (F iW)): with inducing rows that coincide for k0, a product
+ * like (iK Q) iK carries rounding times 1 / eps in directions the hyper-parameter adjoint is blind to and dz is not
+ * (gp_bound.hpp; the backwards themselves form both terms from such factors too, for the period derivatives' sake,
+ * so they are re-formed to the same values).  The Hensman call reads dK0zz as the backward left it, formed term by
+ * term from B x M factors.  None of this writes the bound's own workspace: the backward may run again on it, and so
+ * may these calls.
  * PRECONDITION: the matching lvae_*_bwd_f64 has run on `workspace` since the last forward on it; the cotangent
  * scaling (gdubo[l], gelbo[s][l], *gkld) is then already inside dX / dKz.  x, z, params0 and d as that call's.
  * zworkspace: lvae_bound_dz_workspace_size(L, M, N, Q) bytes, N = P T rows (a multiple of 256; 0 for L, M, N or

@@ -342,12 +342,16 @@ int lvae_dubo_bwd_seg_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec*
   LVAE_TRY(gemm_small_f64(0, 0, N, M, M, 1.0, w.iBK, M, NM, 0, w.iK, M, MM, 0, 0.0, w.Z, M, NM, 0, L, 1, st));
   dubo_sum3_kernel<<<blocks((int64_t)L * NM), 256, 0, st>>>((int64_t)L * NM, w.iBK, w.UR, w.F, w.tNM);
   LVAE_TRY(gemm_small_f64(0, 0, N, M, M, 1.0, w.tNM, M, NM, 0, w.iW, M, MM, 0, 0.0, w.dX, M, NM, 0, L, 1, st));
+  // dKz's two sandwiches from their N x M factors (tNM is free again, Z still iBK iK): iK Q iK = (X iK)^T Z and
+  // iW R iW = U^T (D U).  As (iK Q) iK and (iW R) iW they carry the rounding of the inner product times |iK| ~ 1 / eps
+  // (|iW| less so), which a derivative of Kz that oscillates over the inducing points (a period's) does not average
+  // out -- ten times the oracle's own error in dparams0 at cond(Kz) ~ 5e4
+  LVAE_TRY(gemm_small_f64(0, 0, N, M, M, 1.0, w.X, M, NM, 0, w.iK, M, MM, 0, 0.0, w.tNM, M, NM, 0, L, 1, st));
+  LVAE_TRY(gemm_small_f64(1, 0, M, M, N, 1.0, w.tNM, M, NM, 0, w.Z, M, NM, 0, 0.0, w.iKQiK, M, MM, 0, L, 1, st));
+  dubo_rowscale_nm_kernel<<<blocks((int64_t)L * NM), 256, 0, st>>>(N, M, L, T, seg, logv, w.U, w.tNM);
+  LVAE_TRY(gemm_small_f64(1, 0, M, M, N, 1.0, w.U, M, NM, 0, w.tNM, M, NM, 0, 0.0, w.iWRiW, M, MM, 0, L, 1, st));
   dubo_dx_kernel<<<blocks((int64_t)L * NM), 256, 0, st>>>(N, M, L, gdubo, w.a, w.w, w.U, w.F, w.Z, w.UR, w.dX);
   // dKz
-  LVAE_TRY(gemm_small_f64(0, 0, M, M, M, 1.0, w.iW, M, MM, 0, w.R, M, MM, 0, 0.0, w.iWR, M, MM, 0, L, 1, st));
-  LVAE_TRY(gemm_small_f64(0, 0, M, M, M, 1.0, w.iWR, M, MM, 0, w.iW, M, MM, 0, 0.0, w.iWRiW, M, MM, 0, L, 1, st));
-  LVAE_TRY(gemm_small_f64(0, 0, M, M, M, 1.0, w.iK, M, MM, 0, w.Q, M, MM, 0, 0.0, w.iKQ, M, MM, 0, L, 1, st));
-  LVAE_TRY(gemm_small_f64(0, 0, M, M, M, 1.0, w.iKQ, M, MM, 0, w.iK, M, MM, 0, 0.0, w.iKQiK, M, MM, 0, L, 1, st));
   dubo_dkz_kernel<<<blocks(L * MM), 256, 0, st>>>(L, M, gdubo, w.iK, w.iW, w.iWRiW, w.w, w.iKQiK, w.dKz);
   // dB_p, dK0_p (Z now holds U - Z, UR holds UR - 2 F)
   dubo_rowscale_tt_kernel<<<blocks(LTT), 256, 0, st>>>(P, T, L, seg, logv, w.iB, w.VB);

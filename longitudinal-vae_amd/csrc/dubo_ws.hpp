@@ -15,6 +15,8 @@ inline BoundDims dubo_dims(const lvae_dubo_dims* d) {
   return d ? BoundDims{d->L, d->M, d->P, d->T, d->Q} : BoundDims{};
 }
 
+// (iWR and iKQ are unused since the backward forms iW R iW and iK Q iK from N x M factors; they keep their places
+// so that lvae_dubo_workspace_size stays what it was)
 struct DWs {
   double *X, *iBK, *U, *UR, *F, *Z, *tNM, *dX;                                    // [L,N,M]
   double *Kz, *iK, *Q, *R, *W, *iW0, *E, *iW, *iWR, *iWRiW, *iKQ, *iKQiK, *dKz;  // [L,M,M]

@@ -39,6 +39,7 @@ inline BoundDims ge_dims(const lvae_gp_elbo_dims* d) {
   return d ? BoundDims{d->L, d->M, d->P, d->T, d->Q} : BoundDims{};
 }
 
+// (iKQ: unused, as in dubo_ws.hpp's DWs; lvae_gp_elbo_workspace_size stays what it was)
 struct GWs {
   double *X, *iBK, *U, *Z, *dX;                                   // [L,N,M]
   double *Kz, *iK, *Q, *W, *iW0, *E, *iW, *iKQ, *iKQiK, *dKz;     // [L,M,M]
@@ -344,12 +345,13 @@ int lvae_gp_elbo_bwd_seg_f64(const lvae_kernel_spec* spec0, const lvae_kernel_sp
   LVAE_TRY(gemm_small_f64(0, 0, N, kGeS, M, 1.0, w.U, M, NM, 0, w.Pm, kGeS, MS, 0, 0.0, w.A, kGeS, NS, 0, L, 1, st));
   gp_elbo_g_kernel<<<blocks((int64_t)L * MS), 256, 0, st>>>(L, M, S, gelbo, w.Wm, w.WG, w.Gs);
   gp_elbo_a_kernel<<<blocks((int64_t)L * NS), 256, 0, st>>>(N, L, S, T, seg, gelbo, w.s, w.A, w.AG, dy);
+  // iK Q iK = (X iK)^T Z from the N x M factors, X iK in dX's place (why not (iK Q) iK: dubo.hip's backward)
+  LVAE_TRY(gemm_small_f64(0, 0, N, M, M, 1.0, w.X, M, NM, 0, w.iK, M, MM, 0, 0.0, w.dX, M, NM, 0, L, 1, st));
+  LVAE_TRY(gemm_small_f64(1, 0, M, M, N, 1.0, w.dX, M, NM, 0, w.Z, M, NM, 0, 0.0, w.iKQiK, M, MM, 0, L, 1, st));
   // dX = (A Gam) Wm^T - G (U - Z)   (one [N,16] x [16,M] product for all samples)
   LVAE_TRY(gemm_small_f64(0, 1, N, M, kGeS, 1.0, w.AG, kGeS, NS, 0, w.Wm, kGeS, MS, 0, 0.0, w.dX, M, NM, 0, L, 1, st));
   gp_elbo_dx_kernel<<<blocks((int64_t)L * NM), 256, 0, st>>>(NM, L, w.Gs, w.U, w.Z, w.dX);
   // dKz
-  LVAE_TRY(gemm_small_f64(0, 0, M, M, M, 1.0, w.iK, M, MM, 0, w.Q, M, MM, 0, 0.0, w.iKQ, M, MM, 0, L, 1, st));
-  LVAE_TRY(gemm_small_f64(0, 0, M, M, M, 1.0, w.iKQ, M, MM, 0, w.iK, M, MM, 0, 0.0, w.iKQiK, M, MM, 0, L, 1, st));
   LVAE_TRY(gemm_small_f64(0, 1, M, M, kGeS, 1.0, w.WG, kGeS, MS, 0, w.Wm, kGeS, MS, 0, 0.0, w.dKz, M, MM, 0, L, 1, st));
   gp_elbo_dkz_kernel<<<blocks(L * MM), 256, 0, st>>>(L, MM, w.Gs, w.iK, w.iW, w.iKQiK, w.dKz);
   // dB_p, dK0_p (Z now holds U - Z)

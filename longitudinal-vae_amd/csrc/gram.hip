@@ -230,10 +230,12 @@ __global__ __launch_bounds__(256) void gram_bwd_part_kernel(GramBwdJobs J, int L
       const int r = e / (MF * kGTab), f = (e / kGTab) % MF, m = e % kGTab;
       double phi = 0.0, sn = 0.0, s2 = 0.0;
       if (r < s.n_comp && f < s.n_fac[r]) {
-        const double ell = sp[s.param_idx[r][f]], ad = (double)m;
+        const double ad = (double)m;   // (the parameters are read per kind: a gate or a linear factor has index -1)
         if (s.kind[r][f] == LVAE_RBF) {
+          const double ell = sp[s.param_idx[r][f]];
           phi = exp(-(ad * ad) / (2.0 * ell * ell));
         } else if (s.kind[r][f] == LVAE_PER) {
+          const double ell = sp[s.param_idx[r][f]];
           const double per = sp[s.param_idx[r][f] + 1], u = M_PI * ad / per;
           sn = sin(u);
           phi = exp(-2.0 * sn * sn / (ell * ell));

@@ -5,7 +5,7 @@
 // Per latent dim (B = P_b T rows, subject blocks p of T rows):
 //   K0xz = k0(x, z) [B,M]  K0zz = k0(z, z) + eps I  K0_p = k0(x_p, x_p)  B_p = k1(x_p, x_p) + noise I
 //   iK = K0zz^-1, iB_p = B_p^-1, iH = H^-1 (+ log-dets)         spd_inv_small
-//   t = iK m, r = K0xz t - mu, s = iB r, iBK = iB K0xz, Q = K0xz^T iBK, Y = iK H iK
+//   t = iK m (+ one refinement step), r = K0xz t - mu, s = iB r, iBK = iB K0xz, Q = K0xz^T iBK, Y = iK H iK
 //   A = r.s, Bt = sum diag(iB) v, C = sum log|B_p|, D = sum iB.K0 - sum Q.iK, E = sum Y.Q, F = sum logv
 //   kl_u = 1/2 (sum iK.H + m.t - M + log|K0zz| - log|H|)
 //   kld = sum_l [P_tot/P_b 1/2 (A+Bt+C+D+E-F) + kl_u] - L P_tot T / 2
@@ -14,10 +14,13 @@
 //   dmu = -2c s, dlogv = c (diag(iB) v - 1), Xq = c (Y - iK)
 //   dK0xz = 2c s t^T + 2 iBK Xq
 //   G_iK = c (2 (K0xz^T s) m^T - Q + Z + Z^T) + h (H + m m^T),  Z = Q iK H
-//   dK0zz = -iK G_iK iK + h iK
+//   dK0zz = -iK G_iK iK + h iK, term by term from N x M factors, never as (iK G_iK) iK (that product's rounding
+//   times |iK| ~ 1 / eps is what a period's derivative of K0zz does not average out: dubo.hip's backward):
+//     S = iK Q iK = (K0xz iK)^T (iBK iK),  iK Z iK = S (iK H)^T,  iK (K0xz^T s) m^T iK = (iK K0xz^T s) t^T,
+//     iK H iK = Y,  iK m m^T iK = t t^T
 //   dK0_p = c iB_p
 //   dB_p = c (iB - s s^T - iB V iB - iB K0 iB)_p - iBK_p Xq iBK_p^T
-//   (Adam path) dm = 2c iK K0xz^T s + g t,  dH = c iK Q iK + h (iK - iH)
+//   (Adam path) dm = 2c iK K0xz^T s + g t,  dH = c S + h (iK - iH)
 // (the four Grams and their adjoints, the argument check and the info merge are the DUBO's and the sampled ELBO's
 // too: gp_bound.hpp / gp_bound.hip)
 #include "gp_bound.hpp"
@@ -200,6 +203,40 @@ __global__ void lincomb_kernel(int64_t n, double ax, const double* x, double ay,
   z[e] = cx * x[e] + (y ? cy * y[e] : 0.0);
 }
 
+// t += iK (m - K0zz t), one step of refinement with the residual's dot products in double-double (two-product by
+// fma, two-sum; gp_bound.hip's bound_resid_kernel).  t = iK m carries iK's forward error, cond(K0zz) u, into y, the
+// residual r and s: 5.6e-12 of the id kernel's scale gradient at cond 5e4 where the oracle moves by 1.3e-13.  One
+// workgroup of 128 threads per latent dim (M <= 128: bound_check).
+__global__ __launch_bounds__(128) void hn_t_refine_kernel(int M, const double* __restrict__ K,
+                                                          const double* __restrict__ iK,
+                                                          const double* __restrict__ m, double* __restrict__ t) {
+#pragma clang fp contract(off)  // the error-free transforms below need every product and sum rounded on its own
+  __shared__ double ts[128], rs[128];
+  const int l = blockIdx.x, i = threadIdx.x;
+  const int64_t b = (int64_t)l * M * M;
+  if (i < M) ts[i] = t[(int64_t)l * M + i];
+  __syncthreads();
+  if (i < M) {
+    const double* kr = K + b + (int64_t)i * M;
+    double hi = m[(int64_t)l * M + i], lo = 0.0;
+    for (int k = 0; k < M; ++k) {
+      const double a = -kr[k], y = ts[k];
+      const double ph = a * y, pl = fma(a, y, -ph);  // a y = ph + pl exactly
+      const double s = hi + ph, bb = s - hi;
+      lo += ((hi - (s - bb)) + (ph - bb)) + pl;      // two-sum's error term + the product's
+      hi = s;
+    }
+    rs[i] = hi + lo;
+  }
+  __syncthreads();
+  if (i < M) {
+    const double* ir = iK + b + (int64_t)i * M;
+    double sum = 0.0;
+    for (int k = 0; k < M; ++k) sum += ir[k] * rs[k];
+    t[(int64_t)l * M + i] = ts[i] + sum;
+  }
+}
+
 // dmu[i][l] = -2c s[l][i];  dlogv[i][l] = c (iB_ii v_i - 1)
 __global__ void hn_bwd_vec_kernel(int P_b, int T, int L, double k, const double* __restrict__ g,
                                   const double* __restrict__ s, const double* __restrict__ iB,
@@ -227,21 +264,22 @@ __global__ void outer_add_kernel(int L, int n1, int n2, double a, const double* 
   X[e] += a * g[0] * u[(int64_t)l * n1 + i] * v[(int64_t)l * n2 + j];
 }
 
-// G_iK = c (2 v1 m^T - Q + Z + Z^T) + h (H + m m^T)
-__global__ void giK_kernel(int L, int M, double kc, double kh, const double* __restrict__ g,
-                           const double* __restrict__ v1, const double* __restrict__ m,
-                           const double* __restrict__ Q, const double* __restrict__ Z,
-                           const double* __restrict__ H, double* __restrict__ G) {
+// dK0zz = -(c (2 tv t^T - S + SH + SH^T) + h (Y + t t^T)) + h iK   (tv = iK K0xz^T s at tv[l M M ..), SH = S (iK H)^T)
+__global__ void hn_dkzz_kernel(int L, int M, double kc, double kh, const double* __restrict__ g,
+                               const double* __restrict__ tv, const double* __restrict__ t,
+                               const double* __restrict__ S, const double* __restrict__ SH,
+                               const double* __restrict__ Y, const double* __restrict__ iK,
+                               double* __restrict__ dK0zz) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t MM = (int64_t)M * M;
   if (e >= L * MM) return;
   const int l = (int)(e / MM);
   const int i = (int)((e % MM) / M), j = (int)(e % M);
   const double c = kc * g[0], h = kh * g[0];
-  const double* mm = m + (int64_t)l * M;
+  const double* tl = t + (int64_t)l * M;
   const int64_t b = l * MM;
-  G[e] = c * (2.0 * v1[(int64_t)l * M + i] * mm[j] - Q[e] + Z[e] + Z[b + (int64_t)j * M + i]) +
-         h * (H[e] + mm[i] * mm[j]);
+  dK0zz[e] = h * iK[e] - c * (2.0 * tv[b + i] * tl[j] - S[e] + SH[e] + SH[b + (int64_t)j * M + i]) -
+             h * (Y[e] + tl[i] * tl[j]);
 }
 
 // VB[l,p][i][j] = v_{l,p,i} iB[l,p][i][j]
@@ -321,6 +359,7 @@ int lvae_hensman_fwd_part_f64(int part, const lvae_kernel_spec* spec0, const lva
     LVAE_TRY(spd_inv_small_f64(T, L * P_b, w.Bst, TT, w.iB, TT, w.ldB, w.info + L, st));
     // t = iK m ; y = K0xz t ; iBK = iB K0xz ; Q = K0xz^T iBK ; Y = iK H iK
     LVAE_TRY(gemm_small_f64(0, 0, M, 1, M, 1.0, w.iK, M, MM, 0, m, 1, M, 0, 0.0, w.t, 1, M, 0, L, 1, st));
+    hn_t_refine_kernel<<<L, 128, 0, st>>>(M, w.K0zz, w.iK, m, w.t);
     LVAE_TRY(gemm_small_f64(0, 0, B, 1, M, 1.0, w.K0xz, M, BM, 0, w.t, 1, M, 0, 0.0, w.y, 1, B, 0, L, 1, st));
     LVAE_TRY(gemm_small_f64(0, 0, T, M, T, 1.0, w.iB, T, P_b * TT, TT, w.K0xz, M, BM, (int64_t)T * M, 0.0, w.iBK,
                             M, BM, (int64_t)T * M, L, P_b, st));
@@ -394,16 +433,18 @@ int lvae_hensman_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* 
                                                             dlogv);
   // Xq = c (Y - iK)
   lincomb_kernel<<<blocks(L * MM), 256, 0, st>>>(L * MM, kc, w.Y, -kc, w.iK, w.Xq, gkld, 1, 1);
+  // S = iK Q iK = (K0xz iK)^T (iBK iK) -> T1   (the factors in tBM and in dK0xz, which is formed next)
+  LVAE_TRY(gemm_small_f64(0, 0, B, M, M, 1.0, w.K0xz, M, BM, 0, w.iK, M, MM, 0, 0.0, w.tBM, M, BM, 0, L, 1, st));
+  LVAE_TRY(gemm_small_f64(0, 0, B, M, M, 1.0, w.iBK, M, BM, 0, w.iK, M, MM, 0, 0.0, w.dK0xz, M, BM, 0, L, 1, st));
+  LVAE_TRY(gemm_small_f64(1, 0, M, M, B, 1.0, w.tBM, M, BM, 0, w.dK0xz, M, BM, 0, 0.0, w.T1, M, MM, 0, L, 1, st));
   // dK0xz = 2 iBK Xq + 2c s t^T
   LVAE_TRY(gemm_small_f64(0, 0, B, M, M, 2.0, w.iBK, M, BM, 0, w.Xq, M, MM, 0, 0.0, w.dK0xz, M, BM, 0, L, 1, st));
   outer_add_kernel<<<blocks((int64_t)L * BM), 256, 0, st>>>(L, B, M, 2.0 * kc, gkld, w.s, w.t, w.dK0xz);
-  // v1 = K0xz^T s ; Z = Q iK H ; G_iK ; dK0zz = -iK G_iK iK + h iK
+  // v1 = K0xz^T s ; tv = iK v1 (in GiK's place) ; SH = S (iK H)^T -> Z ; dK0zz
   LVAE_TRY(gemm_small_f64(1, 0, M, 1, B, 1.0, w.K0xz, M, BM, 0, w.s, 1, B, 0, 0.0, w.v1, 1, M, 0, L, 1, st));
-  LVAE_TRY(gemm_small_f64(0, 0, M, M, M, 1.0, w.Q, M, MM, 0, w.iKH, M, MM, 0, 0.0, w.Z, M, MM, 0, L, 1, st));
-  giK_kernel<<<blocks(L * MM), 256, 0, st>>>(L, M, kc, kh, gkld, w.v1, m, w.Q, w.Z, H, w.GiK);
-  LVAE_TRY(gemm_small_f64(0, 0, M, M, M, 1.0, w.iK, M, MM, 0, w.GiK, M, MM, 0, 0.0, w.T1, M, MM, 0, L, 1, st));
-  lincomb_kernel<<<blocks(L * MM), 256, 0, st>>>(L * MM, kh, w.iK, 0.0, nullptr, w.dK0zz, gkld, 1, 0);
-  LVAE_TRY(gemm_small_f64(0, 0, M, M, M, -1.0, w.T1, M, MM, 0, w.iK, M, MM, 0, 1.0, w.dK0zz, M, MM, 0, L, 1, st));
+  LVAE_TRY(gemm_small_f64(0, 0, M, 1, M, 1.0, w.iK, M, MM, 0, w.v1, 1, M, 0, 0.0, w.GiK, 1, MM, 0, L, 1, st));
+  LVAE_TRY(gemm_small_f64(0, 1, M, M, M, 1.0, w.T1, M, MM, 0, w.iKH, M, MM, 0, 0.0, w.Z, M, MM, 0, L, 1, st));
+  hn_dkzz_kernel<<<blocks(L * MM), 256, 0, st>>>(L, M, kc, kh, gkld, w.GiK, w.t, w.T1, w.Z, w.Y, w.iK, w.dK0zz);
   // dB_p and dK0_p
   rowscale_v_kernel<<<blocks(LTT), 256, 0, st>>>(P_b, T, L, logv, w.iB, d.seg_len, w.VB);
   LVAE_TRY(gemm_small_f64(0, 0, T, T, T, 1.0, w.iB, T, P_b * TT, TT, w.VB, T, P_b * TT, TT, 0.0, w.iBVB, T,
@@ -425,10 +466,8 @@ int lvae_hensman_bwd_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* 
   if (!d.natural_gradient && dm && dH) {
     LVAE_TRY(gemm_small_f64(0, 0, M, 1, M, 1.0, w.iK, M, MM, 0, w.v1, 1, M, 0, 0.0, w.tM, 1, M, 0, L, 1, st));
     lincomb_kernel<<<blocks((int64_t)L * M), 256, 0, st>>>((int64_t)L * M, 2.0 * kc, w.tM, 1.0, w.t, dm, gkld, 1, 1);
-    LVAE_TRY(gemm_small_f64(0, 0, M, M, M, 1.0, w.iK, M, MM, 0, w.Q, M, MM, 0, 0.0, w.iKQ, M, MM, 0, L, 1, st));
     lincomb_kernel<<<blocks(L * MM), 256, 0, st>>>(L * MM, kh, w.iK, -kh, w.iH, dH, gkld, 1, 1);
-    LVAE_TRY(gemm_small_f64(0, 0, M, M, M, 1.0, w.iKQ, M, MM, 0, w.iK, M, MM, 0, 0.0, w.tMM, M, MM, 0, L, 1, st));
-    axpby_kernel<<<blocks(L * MM), 256, 0, st>>>(L * MM, kc, w.tMM, 1.0, dH, gkld, nullptr);
+    axpby_kernel<<<blocks(L * MM), 256, 0, st>>>(L * MM, kc, w.T1, 1.0, dH, gkld, nullptr);
   }
   LVAE_CHECK_LAUNCH();
   return 0;

@@ -98,8 +98,9 @@ class RbfKernel(_Factor):
 
 
 class PeriodicKernel(_Factor):
-    """exp(-2 sin^2(pi |x1_d - x2_d| / p) / l^2).  EXTENSION (BASELINE config 5): not in the
-    reference; parity unpinned."""
+    """exp(-2 sin^2(pi |x1_d - x2_d| / p) / l^2).  EXTENSION (BASELINE config 5): not in the reference, so parity
+    with it is undefined; agreement with the fp64 oracle is pinned for every entry point that takes a spec
+    (factor_params order: lengthscale, then period)."""
     kind = "per"
 
     def __init__(self, dim, latent_dim=1, lengthscale=1.0, period=4.0):
@@ -126,7 +127,8 @@ class PeriodicKernel(_Factor):
 
 
 class LinearKernel(_Factor):
-    """x1_d * x2_d (its variance is the enclosing ScaleKernel).  EXTENSION, parity unpinned."""
+    """x1_d * x2_d (its variance is the enclosing ScaleKernel).  EXTENSION: not in the reference, so parity with it
+    is undefined; agreement with the fp64 oracle is pinned for every entry point that takes a spec."""
     kind = "lin"
 
     def __init__(self, dim):

@@ -98,7 +98,7 @@ def point(cid, name):
 
 
 def hypers(c):
-    return O.constrain(torch.tensor(c["raw0"])), O.constrain(torch.tensor(c["raw1"])), torch.tensor(c["noise"])
+    return D.positive(c)[:3]
 
 
 def oracle_at(c, m, lv, cot, x=None, mu=None, logv=None, rows=None, dubo_fn=None):
@@ -179,14 +179,14 @@ def bound_for(cid, name):
 def abi_inputs(cid, noise=None):
     """dubo_util.abi_inputs for every case of this module + the free set as a device int32 array"""
     from lvae_amd import _lib as P
-    c = problem(cid)
+    c = problem(cid) if isinstance(cid, str) else cid   # (or a problem given whole, with free / rows / Pn / Nn)
     s0, s1 = P.make_spec(c["s0"]), P.make_spec(c["s1"])
     p0, p1, nz = hypers(c)
     t = dict(x=c["X"], z=c["Z"], mu=c["mu"], lv=c["lv"], p0=p0, p1=p1,
              noise=nz if noise is None else torch.tensor(noise, dtype=torch.float64))
     d = {k: v.to(DEV).contiguous() for k, v in t.items()}
     d["free"] = torch.tensor(c["free"], dtype=torch.int32, device=DEV)
-    dims = P.DuboDims(L, c["M"], c["P"], c["T"], c["X"].shape[1], EPS)
+    dims = P.DuboDims(L, c["M"], c["P"], c["T"], c["X"].shape[1], c.get("eps", EPS))
     return c, s0, s1, dims, d
 
 

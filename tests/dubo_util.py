@@ -173,15 +173,30 @@ def noise_stub(values, dev=DEV):
 TAIL = 7
 
 
+def as_problem(cid):
+    """a case id of this module, or a problem given whole: problem()'s keys with any specs and covariates, the
+    positive hyper-parameters as p0 / p1 [L, n] in place of raw0 / raw1, and its own jitter as eps (ext_util)"""
+    return problem(cid) if isinstance(cid, str) else cid
+
+
+def positive(c):
+    """(p0, p1, noise) [L, .] fp64 of a problem, and its jitter"""
+    if "p0" in c:
+        p0, p1 = c["p0"], c["p1"]
+    else:
+        p0, p1 = O.constrain(torch.tensor(c["raw0"])), O.constrain(torch.tensor(c["raw1"]))
+    return p0, p1, torch.as_tensor(c["noise"], dtype=torch.float64), c.get("eps", EPS)
+
+
 def abi_inputs(cid, noise=None):
     from lvae_amd import _lib as P
-    c = problem(cid)
+    c = as_problem(cid)
     s0, s1 = P.make_spec(c["s0"]), P.make_spec(c["s1"])
-    t = dict(x=c["X"], z=c["Z"], mu=c["mu"], lv=c["lv"], p0=O.constrain(torch.tensor(c["raw0"])),
-             p1=O.constrain(torch.tensor(c["raw1"])),
-             noise=torch.tensor(c["noise"] if noise is None else noise, dtype=torch.float64))
+    p0, p1, nz, eps = positive(c)
+    t = dict(x=c["X"], z=c["Z"], mu=c["mu"], lv=c["lv"], p0=p0, p1=p1,
+             noise=nz if noise is None else torch.tensor(noise, dtype=torch.float64))
     d = {k: v.to(DEV).contiguous() for k, v in t.items()}
-    dims = P.DuboDims(L, c["M"], c["P"], c["T"], c["X"].shape[1], EPS)
+    dims = P.DuboDims(L, c["M"], c["P"], c["T"], c["X"].shape[1], eps)
     return c, s0, s1, dims, d
 
 

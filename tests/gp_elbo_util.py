@@ -25,9 +25,17 @@ BOUND = dict(elbo=D.BOUND["dubo"], dy=D.BOUND["dmu"], draw0=D.BOUND["draw0"], dr
 rel = D.rel
 
 
-@functools.lru_cache(maxsize=None)
 def samples(cid, S):
-    """y [S, N, L] = mu + 0.3 randn and the cotangents g [S, L], both seeded by (case, S)"""
+    """y [S, N, L] = mu + 0.3 randn and the cotangents g [S, L], both seeded by (case, S); a problem given whole
+    (dubo_util.as_problem) brings its own as ys / g"""
+    if not isinstance(cid, str):
+        assert cid["ys"].shape[0] == S
+        return cid["ys"], cid["g"]
+    return _samples(cid, S)
+
+
+@functools.lru_cache(maxsize=None)
+def _samples(cid, S):
     c = D.problem(cid)
     gen = torch.Generator().manual_seed(7000 + 100 * D.CASE_IDS.index(cid) + S)
     y = c["mu"][None] + 0.3 * torch.randn(S, c["N"], L, generator=gen, dtype=torch.float64)
@@ -113,16 +121,16 @@ def make_dims(c, S, **kw):
     from lvae_amd import _lib as P
     f = dict(L=L, M=c["M"], P=c["P"], T=c["T"], Q=c["X"].shape[1], S=S)
     f.update(kw)
-    return P.GpElboDims(f["L"], f["M"], f["P"], f["T"], f["Q"], f["S"], EPS)
+    return P.GpElboDims(f["L"], f["M"], f["P"], f["T"], f["Q"], f["S"], c.get("eps", EPS))
 
 
 def abi_inputs(cid, S, noise=None):
     from lvae_amd import _lib as P
-    c = D.problem(cid)
+    c = D.as_problem(cid)
     s0, s1 = P.make_spec(c["s0"]), P.make_spec(c["s1"])
-    t = dict(x=c["X"], z=c["Z"], y=samples(cid, S)[0], p0=O.constrain(torch.tensor(c["raw0"])),
-             p1=O.constrain(torch.tensor(c["raw1"])),
-             noise=torch.tensor(c["noise"] if noise is None else noise, dtype=torch.float64))
+    p0, p1, nz, _ = D.positive(c)
+    t = dict(x=c["X"], z=c["Z"], y=samples(cid, S)[0], p0=p0, p1=p1,
+             noise=nz if noise is None else torch.tensor(noise, dtype=torch.float64))
     d = {k: v.to(DEV).contiguous() for k, v in t.items()}
     return c, s0, s1, make_dims(c, S), d
 

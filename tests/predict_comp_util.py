@@ -15,10 +15,11 @@ import numpy as np
 import torch
 
 import abi_util as U
+import ext_util
 from oracle import lvae_oracle as O
 
 EPS = 1e-3
-PAIRS = U.spec_pairs()
+PAIRS = ext_util.all_spec_pairs()
 
 
 def offsets(spec):
@@ -98,6 +99,9 @@ IND_CASES = {
     "no-test-rows": ("ref", 2, 3, 5, 16, 0, (16, 1, 7, 12, 16), ()),
     "none-included": ("mix1", 2, 3, 5, 16, 7, (16, 1, 7, 12, 16), (9, 11)),        # the k1 components vanish
     "ref-ragged": ("ref", 3, 17, 4, 17, 30, (17, 1, 9, 16), (2, 0, 7)),            # (the Python tests' problem)
+    # periodic and linear factors (ext_util): both buckets for spec0; Nt not a multiple of 64, subject 7 / 5 absent
+    "ext-a": ("ext-a", 3, 9, 4, 7, 70, (7, 1, 4, 6), (2, 0, 7)),
+    "ext-c": ("ext-c", 2, 17, 3, 9, 67, (9, 1, 5), (1, 0, 5)),
 }
 IND_IDS = list(IND_CASES)
 
@@ -146,7 +150,7 @@ def ind_ref(cid):
 
 
 # ---- exact-route problems: test_gpu_predict_exact_abi.problem()'s ----
-EXACT_IDS = ["smallest", "tile-edge", "mix1", "ext", "few-rows", "no-test-rows"]
+EXACT_IDS = ["smallest", "tile-edge", "mix1", "ext", "few-rows", "no-test-rows", "ext-a"]
 
 
 def exact_oracle(cid, dev="cpu", perturb=False):
@@ -175,12 +179,15 @@ def bound(yard):
 
 # ---- the fused component product alone (test_gpu_gram_matvec_comp_abi.py) ----
 R1_SPEC = [[("cat", 3), ("rbf", 0)]]
+# a bare lin on a signed real column, cat x lin, bin x lin, per, per x rbf and the reference kinds; bucket (8, 2)
+XLIN = [[("lin", 1)], [("cat", 3), ("lin", 6)], [("bin", 5), ("lin", 6)], [("per", 0)], [("per", 0), ("rbf", 1)],
+        [("cat", 2)], [("cat", 2), ("rbf", 0)], [("rbf", 0)]]
 MIX1_0 = PAIRS["mix1"][0]
 
 
 def mv_specs():
     import test_gpu_predict_exact_abi as E
-    return {**E.SPECS, "r1": R1_SPEC, "mix1-0": MIX1_0}
+    return {**E.SPECS, "r1": R1_SPEC, "mix1-0": MIX1_0, "xlin": XLIN}
 
 
 def slabs(n1, n2, L, R):
@@ -214,7 +221,23 @@ MV_CASES = {
     "z128": ("mix1-0", 3, 70, 128, True, False),
     "r1": ("r1", 2, 70, 67, False, False),
     "zero-id": ("ref", 2, 70, 130, False, True),
+    # XLIN (linear factors bare and gated, periodic ones): shared and per-dim x2, real and integer-coded times ("-int")
+    "xl-1x1": ("xlin", 2, 1, 1, False, False),
+    "xl-65x130": ("xlin", 3, 65, 130, False, False),
+    "xl-65x130-int": ("xlin", 3, 65, 130, False, False),
+    "xl-z65x130": ("xlin", 3, 65, 130, True, False),
+    "xl-z65x130-int": ("xlin", 3, 65, 130, True, False),
+    "xl-slab": ("xlin", 2, 3, "slab", False, False),
+    "xl-zslab-int": ("xlin", 2, 3, "slab", True, False),
+    # (the rest of the cross of the three shapes with both x2 forms and both time variants; appended: the ids above
+    # keep their seeds)
+    "xl-1x1-int": ("xlin", 2, 1, 1, False, False),
+    "xl-z1x1": ("xlin", 2, 1, 1, True, False),
+    "xl-z1x1-int": ("xlin", 2, 1, 1, True, False),
+    "xl-slab-int": ("xlin", 2, 3, "slab", False, False),
+    "xl-zslab": ("xlin", 2, 3, "slab", True, False),
 }
+XL_ZERO_COMP = 2     # XLIN's bin(5) x lin(6): column 6 of x1 is 0 on its first 64-row tile, the gate is on in places
 MV_IDS = list(MV_CASES)
 
 
@@ -241,6 +264,27 @@ def mv_problem(cid):
     x1[:, 0] = torch.tensor(rng.uniform(0.0, 5.5, n1))
     tids = [Pn + 1, Pn + 4] if absent else [0, Pn + 2, Pn - 1, Pn + 5]
     x1[:, U.ID_COL] = torch.tensor([float(tids[i % len(tids)]) for i in range(n1)])
+    if name == "xlin":
+        if n1 > 64:   # the linear factor of column 6 vanishes on the whole first 64-row tile, under bin gates that
+            x1[:64, 6] = 0.0       # are on for pairs of that tile and of the rows after it
+            x1[::2, 5], x2[..., ::2, 5] = 1.0, 1.0
+        if per_dim:                # (inducing rows carry an id no subject has: give some the test rows' id 0)
+            x2[..., ::3, U.ID_COL] = 0.0
+        if n1 == 1 and n2 == 1:    # the single pair passes every gate
+            x1[0, 5], x2[..., 0, 5] = 1.0, 1.0
+            if per_dim:
+                x2[..., 0, 2], x2[..., 0, 3] = x1[0, 2], x1[0, 3]
+            else:
+                x1[0, 2], x1[0, 3] = x2[0, 2], x2[0, 3]
+        if cid.endswith("-int"):   # integer-coded times: ext_util's walk for x1, distinct integers for x2
+            x1[:, 0] = torch.tensor(ext_util.T0[np.arange(n1) % 7])
+            tz = np.stack([rng.choice(max(201, 2 * n2), n2, replace=False) for _ in range(L if per_dim else 1)])
+            if n2 == 1:
+                # one pair has one distance: 2, so that sin's argument pi d / p stays O(1).  At a drawn d ~ 100 the
+                # argument ~ 300 carries its own rounding 300-fold into the kernel value on both sides, which the
+                # bound's n2 + 16 ulps absorb at n2 = 130 but not at n2 = 1 (measured there: 6.0e-15 against 4.3e-16)
+                tz[:] = 2.0
+            x2[..., 0] = torch.tensor(tz.astype(np.float64)).reshape(x2.shape[:-1])
     return dict(spec=spec, R=R, L=L, n1=n1, n2=n2, per_dim=per_dim, absent=absent, x1=x1, x2=x2,
                 v=torch.randn(n2, L, generator=gen, dtype=torch.float64),
                 params=U.draw_hypers(rng, L, O.n_params(spec)))

@@ -7,6 +7,12 @@ mix1 / mix2), per / lin factors (ext), 18 covariate columns (wide-cols: the 32-s
 slab path (3 rows against the fewest columns at which the size query reports S >= 2, and one tile fewer: S = 1),
 per-dim x2 [L, M, Q] with M = 1 / 17 / 128, one component (R = 1), and test subjects all absent from x2 (the id
 components are then exactly zero).
+The xl-* cases run predict_comp_util.XLIN (a bare lin on a signed real column, cat x lin, bin x lin, per, per x rbf
+and the reference kinds) at 1 x 1, 65 x 130 and the slab path, with a shared and a per-dim x2 and with real and
+integer-coded times, all twelve combinations (a single pair has one distance: 2 in its integer cases,
+predict_comp_util.mv_problem says why); at 65 x 130 the column of the gated lin factors is zero on the whole first
+64-row tile of x1 while bin gates of that tile are on: the component is zero there with no gate saying so (the wave
+skip of an all-zero component), exact zeros are asserted, and the rows after the tile are not zero.
 
 Bound per component and latent dim: max_i |got - ref| <= 2^-52 (n2 + 16) max_i sum_j |K_r,ij v_j|, the a-priori
 forward error of an n2-term fp64 dot product in any order (16: the few ulps of each kernel value's exp / sin on
@@ -14,8 +20,11 @@ either side), as test_gpu_predict_exact_abi.test_gram_matvec_values bounds the s
 
 Measured on the MI355X: the worst err / bound over components and dims is 0.57 at z1 (one column: the bound is 17
 ulps of the single product), 0.27 at z17, 0.11 at L16 and at most 0.06 elsewhere; sum_r differs from
-lvae_gram_matvec_f64's result by at most 1.4e-14 absolute against bounds of 5e-13 .. 2.5e-11.  The module's 24 tests
-take under 3 s.
+lvae_gram_matvec_f64's result by at most 1.4e-14 absolute against bounds of 5e-13 .. 2.5e-11.  The xl-* cases: worst
+err / bound 0.68 (xl-1x1-int), 0.65 (xl-z65x130-int), 0.47 (xl-z1x1), 0.28 (xl-65x130-int), 0.22 (xl-1x1), 0.19
+(xl-z1x1-int), 0.17 (xl-slab-int), at most 0.11 elsewhere; sum_r within 2.9e-14 of lvae_gram_matvec_f64 against
+bounds of 1.7e-11 and more (within 1.8e-15 on the single products of the 1 x 1 cases).  The module's 36 tests take
+under 3 s.
 """
 import ctypes
 
@@ -112,7 +121,11 @@ def test_gram_matvec_comp_values(hip, cid):
     print(f"gram_matvec_comp {cid}: [{n1} x {n2}] L {L} R {R} S {C.slabs(n1, n2, L, R)} worst err / bound "
           f"{worst:.2g}; |sum_r - matvec| {float(derr.max()):.2e} bound {float(dtol.min()):.1e}")
     assert bool((derr <= dtol).all())
-    if cid == "slab":
+    if c["spec"] is C.XLIN and n1 > 64:   # a component that is zero on a whole tile with no gate saying so
+        z = C.XL_ZERO_COMP
+        assert bool((ref[z][:64] == 0).all()) and bool((got[z][:64] == 0).all()) and bool((got[z][64:] != 0).any())
+        assert bool((c["x1"][:64, 5] == 1).any()) and bool((ref[1][:64] == 0).all()) and bool((ref[0] != 0).all())
+    if cid in ("slab", "xl-slab", "xl-zslab-int", "xl-slab-int", "xl-zslab"):
         assert C.slabs(n1, n2, L, R) >= 2
     if cid == "slab-64":
         assert C.slabs(n1, n2, L, R) == 1

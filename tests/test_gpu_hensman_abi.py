@@ -106,17 +106,23 @@ FLOAT_INPUTS = ["p0", "p1", "noise", "m", "H", "mu", "logv"]
 
 def oracle(cid, dev="cpu", perturb=False):
     """Every compared quantity from the oracle (one evaluation, autograd for the gradients); perturb: the
-    floating-point inputs times 1 + 2^-50 s.  Gradients of padding rows are zeros."""
-    c = problem(cid)
+    floating-point inputs times 1 + 2^-50 s.  Gradients of padding rows are zeros.  cid: a case id, or a problem
+    in problem()'s keys (ext_util.hensman_problem; its perturb_cols names covariate columns perturbed as well)."""
+    c = problem(cid) if isinstance(cid, str) else cid
     v = {k: c[k] for k in FLOAT_INPUTS}
+    x, z = c["x"], c["z"]
     if perturb:
         gen = torch.Generator().manual_seed(77)
         v = {k: U.perturbed(t, gen) for k, t in v.items()}
         v["H"] = 0.5 * (v["H"] + v["H"].transpose(1, 2))
+        x, z = x.clone(), z.clone()
+        for q in c.get("perturb_cols", []):
+            x[..., q] = U.perturbed(x[..., q], gen)
+            z[..., q] = U.perturbed(z[..., q], gen)
     ok = c["valid"]
     v["mu"], v["logv"] = v["mu"][ok], v["logv"][ok]
     v = {k: t.detach().clone().to(dev).requires_grad_() for k, t in v.items()}
-    x, z = c["x"][ok].to(dev), c["z"].to(dev)
+    x, z = x[ok].to(dev), z.to(dev)
     if c["seg"] is None:
         kld, gm, gH = O.hensman_kld(c["s0"], v["p0"], c["s1"], v["p1"], v["noise"], v["m"], v["H"], x, v["mu"],
                                     v["logv"], z, c["P_tot"], c["P_b"], c["T"], True, c["eps"])
@@ -218,7 +224,7 @@ def run(hip, cid, ng, pad=float("nan"), fill_seed=1, gk=1.0, n_total=None, share
     """Forward then backward on one sentinel-tailed workspace, every output pre-filled with sentinels.  Returns
     ({name: CPU tensor}, info, H^-1 as left in the workspace)."""
     from lvae_amd import _lib as P
-    c = problem(cid)
+    c = problem(cid) if isinstance(cid, str) else cid
     L, M, T, P_b, B = c["L"], c["M"], c["T"], c["P_b"], c["B"]
     s0, s1 = P.make_spec(c["s0"]), P.make_spec(c["s1"])
     t = {k: c[k].clone() for k in FLOAT_INPUTS}

@@ -15,6 +15,7 @@ Measured on the MI355X (yardstick = max of the two figures above, bound = max(10
     limits          8.73e-14     5.55e-14    1.6               2.0e-12
     none-included   4.54e-14     2.79e-14    1.6               2.0e-12
     chunked         2.61e-13     9.29e-14    2.8               2.0e-12
+    ext-b           9.63e-15     2.22e-14    0.43              2.0e-12   (ext_util's ext-b: per / lin in both kernels)
 Before lvae_predict_f64 refined its two products with explicit inverses (H^-1 w, K0zz^-1 a; cond ~1e5 at
 eps = 1e-3) by one residual step, "limits" measured 4.59e-12 (83 x its yardstick) and "none-included" 4.33e-12
 (160 x): beyond the bound, where the oracle's solves are not.  The chunked case (workspace ~130 MiB, 7711 test rows
@@ -30,11 +31,12 @@ import pytest
 import torch
 
 import abi_util as U
+import ext_util
 from oracle import lvae_oracle as O
 
 gpu = pytest.mark.gpu
 DEV = U.DEV
-PAIRS = U.spec_pairs()
+PAIRS = ext_util.all_spec_pairs()
 EPS = 1e-3
 
 # id: (pair, L, M, P, T, Nt, seg_len, subject ids of the test rows (cycled over the rows))
@@ -46,6 +48,8 @@ CASES = {
     "none-included": ("mix1", 2, 33, 5, 16, 7, (16, 1, 7, 12, 16), (9, 11)),    # the k1 term vanishes
     "chunked": ("mix2", 1, 16, 17, 128, 7711, tuple([128, 1, 77] + [128 - 7 * p for p in range(14)]),
                 tuple(range(0, 20, 2))),
+    # periodic and linear factors in both kernels, a (16, 4) id kernel, Nt not a multiple of 64
+    "ext-b": ("ext-b", 3, 17, 4, 17, 70, (17, 1, 9, 16), (2, 0, 7)),
 }
 CASE_IDS = list(CASES)
 

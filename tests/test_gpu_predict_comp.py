@@ -10,7 +10,9 @@ its CPU / device spread.
 Exact-route cases: test_gpu_predict_exact_abi.problem()'s smallest, tile-edge, mix1, ext, few-rows (the slab path)
 and no-test-rows.  Inducing-route cases (predict_comp_util.IND_CASES): M = 1, 3, 17 and 128, ragged subjects up to
 64 rows with a one-row subject among them, test subjects inside and outside the prediction set, none inside (the k1
-components are exact zeros) and no test rows.
+components are exact zeros) and no test rows.  Periodic and linear factors: the exact route on ext_util's ext-a as one
+kernel (spec0 + spec1, 9 components: bucket (16, 4)), the inducing route on ext-a and ext-c (13 components), each
+with 70 / 67 test rows (no multiple of 64) and a test subject outside the prediction set.
 
 Measured on the MI355X (err and yardstick relative to max |oracle|; every bound is the 2e-12 floor but one):
     case                  err        yardstick   err / yardstick   bound
@@ -24,7 +26,10 @@ Measured on the MI355X (err and yardstick relative to max |oracle|; every bound 
     inducing m128-ragged  2.52e-13   2.34e-13    1.1               2.3e-12
     inducing none-incl.   5.78e-15   5.03e-15    1.1               2.0e-12
     inducing ref-ragged   3.36e-15   2.59e-15    1.3               2.0e-12
-The module's 21 tests take under 4 s.
+    exact ext-a           8.39e-15   1.31e-14    0.64              2.0e-12
+    inducing ext-a        3.27e-15   2.54e-14    0.13              2.0e-12
+    inducing ext-c        3.37e-15   7.23e-15    0.47              2.0e-12
+The module's 24 tests take under 4 s.
 """
 import ctypes
 

@@ -5,7 +5,8 @@ Exact: n in {1, 63, 65, 130} (across the 64-row blocks of potrf / trsm), nt in {
 blocks of the solve and of the variance kernel), chunks in {1, 16, nt}, L in {1, 3}, both template buckets;
 non-unit ldx / ldt / ld_mu / ld_out / ld_var on sentinel buffers.  Inducing-point: M in {1, 20, 128}, T in
 {1, 5, 20} with ragged seg_len, Nt in {1, 37}, a subject with 70 test rows (five 16-column tiles, the last partial),
-test subjects absent from the prediction set (some, and all), L in {1, 3}.
+test subjects absent from the prediction set (some, and all), L in {1, 3}; ext_util's ext-b pair (periodic and
+linear factors in both kernels, a (16, 4) id kernel) on the ragged layout: err 3.98e-15 against a yardstick of 2.40e-15.
 
 Tolerance: the project's rule min(max(10 x yardstick, 2e-12), 1e-6) on max |got - ref| / max prior, the yardstick
 being the larger of the oracle's change under a relative 2^-50 perturbation of its inputs and its CPU / device

@@ -154,6 +154,8 @@ IND_CASES = {
     "all-absent": ("ref", 3, 20, 3, 5, (5, 2, 4), tuple([9, 11] * 18 + [9])),                    # Nt = 37
     "one-row": ("mix1", 1, 20, 2, 20, (20, 7), (1,)),                                            # Nt = 1
     "no-test-rows": ("ref", 3, 20, 3, 5, (5, 2, 4), ()),
+    # ext_util's ext-b: periodic and linear factors in both kernels, a (16, 4) id kernel
+    "ext-b": ("ext-b", 3, 20, 4, 5, (5, 1, 3, 4), tuple([2, 0, 7, 3, 1, 9] * 6 + [2])),          # Nt = 37
 }
 
 
@@ -192,8 +194,9 @@ def exact_oracle(cid, dev="cpu", perturb=False):
 def ind_problem(cid):
     """The [P, T] subject layout with ragged seg_len (padding rows of mu zero) and the test rows grouped by
     subject (stable), with the layout arrays lvae_predict_var_f64 takes."""
+    import ext_util
     pair, L, M, Pn, T, seg, tids = IND_CASES[cid]
-    s0, s1 = U.spec_pairs()[pair]
+    s0, s1 = ext_util.all_spec_pairs()[pair]
     k = list(IND_CASES).index(cid)
     rng = np.random.default_rng(8000 + k)
     gen = torch.Generator().manual_seed(8100 + k)

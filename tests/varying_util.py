@@ -257,8 +257,9 @@ S_ABI = 3
 
 def padded_inputs(cid, dirty):
     """The [P * T, .] padded layout of a case.  dirty = False: padding rows of mu / logv / y are 0 and those of x
-    repeat the subject's first row; True: they are NaN, and x's padding rows hold the NEXT subject's covariates."""
-    c = problem(cid)
+    repeat the subject's first row; True: they are NaN, and x's padding rows hold the NEXT subject's covariates.
+    cid: a case id, or a ragged problem given whole (ext_util.problem: this module's keys, p0 / p1, ys / g, eps)."""
+    c = as_problem(cid)
     P, T, valid = c["P"], c["T"], c["valid"]
     Q = c["X"].shape[1]
     xf = c["Xfull"].reshape(P, T, Q)
@@ -270,15 +271,24 @@ def padded_inputs(cid, dirty):
         out = torch.full(t.shape[:-2] + (P * T, L), fill, dtype=torch.float64)
         out[..., valid, :] = t
         return out
-    return dict(x=x, mu=pad(c["mu"]), lv=pad(c["lv"]), y=pad(samples(cid, S_ABI)[0]))
+    return dict(x=x, mu=pad(c["mu"]), lv=pad(c["lv"]), y=pad(abi_samples(cid)[0]))
+
+
+def as_problem(cid):
+    return problem(cid) if isinstance(cid, str) else cid
+
+
+def abi_samples(cid):
+    """(y, g) of the C-ABI runs: S_ABI seeded samples of a case, a given problem's own"""
+    return samples(cid, S_ABI) if isinstance(cid, str) else (cid["ys"], cid["g"])
 
 
 def _abi_common(cid, dirty):
     from lvae_amd import _lib as P
-    c = problem(cid)
+    c = as_problem(cid)
     s0, s1 = P.make_spec(c["s0"]), P.make_spec(c["s1"])
-    t = dict(padded_inputs(cid, dirty), z=c["Z"], p0=O.constrain(torch.tensor(c["raw0"])),
-             p1=O.constrain(torch.tensor(c["raw1"])), noise=torch.tensor(c["noise"], dtype=torch.float64))
+    p0, p1, nz, _ = D.positive(c)
+    t = dict(padded_inputs(cid, dirty), z=c["Z"], p0=p0, p1=p1, noise=nz)
     d = {k: v.to(DEV).contiguous() for k, v in t.items()}
     d["seg"] = torch.tensor(c["seg"], dtype=torch.int32, device=DEV)
     return c, s0, s1, d
@@ -296,7 +306,7 @@ def abi_dubo(hip, cid, dirty, seg=True):
     from lvae_amd import _lib as P
     c, s0, s1, d = _abi_common(cid, dirty)
     NP, Q = c["P"] * c["T"], c["X"].shape[1]
-    dims = P.DuboDims(L, c["M"], c["P"], c["T"], Q, EPS)
+    dims = P.DuboDims(L, c["M"], c["P"], c["T"], Q, c.get("eps", EPS))
     n = dict(dubo=L, dmu=NP * L, dlogv=NP * L, dp0=L * s0.n_params, dp1=L * s1.n_params, dnoise=L)
     o = {k: U.sentinel(v + TAIL) for k, v in n.items()}
     info = U.sentinel(L + TAIL, torch.int32)
@@ -330,13 +340,14 @@ def abi_elbo(hip, cid, dirty, seg=True):
     """the same for lvae_gp_elbo_fwd_seg_f64, lvae_gp_elbo_bwd_seg_f64 and lvae_gp_elbo_bwd_z_f64 (S_ABI samples)"""
     from lvae_amd import _lib as P
     c, s0, s1, d = _abi_common(cid, dirty)
-    S, NP, Q = S_ABI, c["P"] * c["T"], c["X"].shape[1]
-    dims = P.GpElboDims(L, c["M"], c["P"], c["T"], Q, S, EPS)
+    ys, gs = abi_samples(cid)
+    S, NP, Q = ys.shape[0], c["P"] * c["T"], c["X"].shape[1]
+    dims = P.GpElboDims(L, c["M"], c["P"], c["T"], Q, S, c.get("eps", EPS))
     n = dict(elbo=S * L, dy=S * NP * L, dp0=L * s0.n_params, dp1=L * s1.n_params, dnoise=L)
     o = {k: U.sentinel(v + TAIL) for k, v in n.items()}
     info = U.sentinel(L + TAIL, torch.int32)
     ws, tail = U.workspace(hip.lvae_gp_elbo_workspace_size(ctypes.byref(dims)))
-    g = samples(cid, S)[1].contiguous().to(DEV)
+    g = gs.contiguous().to(DEV)
     st = P.stream_ptr()
     common = (ctypes.byref(s0), ctypes.byref(s1), ctypes.byref(dims), P.ptr(d["seg"]) if seg else None, P.ptr(d["x"]),
               P.ptr(d["z"]), P.ptr(d["y"]), P.ptr(d["p0"]), P.ptr(d["p1"]), P.ptr(d["noise"]))
