@@ -824,6 +824,83 @@ int lvae_predict_comp_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec*
                           const double* params1, const double* noise, double eps, double* out, double* out_comp,
                           int64_t ld_comp, int64_t cstride_r, int32_t* info, void* workspace, void* stream);
 
+/* Joint posterior covariance of the R additive component functions f_1(x*_t) .. f_R(x*_t) at each test row, under
+ * both predictors, fp64: an R x R block per (latent dim, test row).  The component means stay those of the two
+ * functions above; the observation noise belongs to no component and is never added.  Both return the raw
+ * difference (not clamped), in blocks that are symmetric bit for bit ([r][s] and [s][r] are one computed value) and
+ * laid out as the sibling covariances' [L, n_groups, n_max, n_max] with a group = one test row and n_max = R, without
+ * padding.  Covariances between components at different test rows are not formed.
+ *
+ * lvae_predict_exact_comp_cov_f64: lvae_predict_exact_comp_f64's arguments plus chunk and out_ccov.  With
+ * K_l = k_l(x, x) + noise_l I = L_l L_l^T and V_r = L_l^-1 k_{l,r}(x, tx_t),
+ *   out_ccov[l, t, r, s] = (r == s) k_{l,r}(tx_t, tx_t) - V_r . V_s            r, s < R = spec->n_comp (1 .. 16)
+ * block (l, t) at out_ccov[(l*nt + t)*R*R]; sum_{r,s} out_ccov[l, t] = lvae_predict_exact_var_f64's out_var[t, l]
+ * (add_noise = 0) up to rounding.  out may be NULL (then mu may be too, as for lvae_predict_exact_var_f64) and
+ * out_comp may be NULL; out_comp needs out.  When given, out, out_comp and info receive
+ * lvae_predict_exact_comp_f64's bits (the same launches).  Route: the Gram, lvae_potrf_f64 and the means as there;
+ * then per chunk of c = min(chunk, nt) test rows one kernel writes the component-resolved panel k_{l,r}(x, tx_chunk)
+ * as [L, n, c R], column t R + r (row-major, component-minor; the spec is evaluated once per (i, t) pair and the R
+ * component values scattered), lvae_trsm_f64 (trans = 0) runs in place on the c R columns, and an fp64 matrix-core
+ * kernel (v_mfma_f64_16x16x4) forms each row's V^T V as one 16 x 16 tile (columns r >= R zero), the n prediction rows
+ * cut into slabs of 512 whose partial tiles go to the workspace and are added in slab order under the prior
+ * variances k_{l,r}(tx_t, tx_t) evaluated through the spec (lvae_predict_exact_cov_f64's V^T V step with a test
+ * row's components in the role of a group's rows).  No atomics, every sum in a fixed order: the bits depend on
+ * neither the grid nor the chunk.  A component whose cross-Gram vanishes everywhere (an id component for an unseen
+ * subject) gives exact zeros off the diagonal and its exact prior on it.  n^2 R nt fp64 flops per dim in the
+ * solves.  nt == 0: the factor runs (info is written), nothing else is touched.  workspace:
+ * lvae_predict_exact_comp_cov_workspace_size(n, nt, L, R, chunk) bytes (lvae_predict_exact_comp_f64's + 8 L n c R
+ * for the panel + 2048 L c ceil(n / 512) for the partial tiles; 0 for n < 1, nt < 0, L < 1, R outside 1 .. 16 or,
+ * with nt > 0, chunk < 1), 256-B aligned.
+ * Returns 0, LVAE_ERR_LAUNCH, or before any launch, in this order: -1 .. -7 as lvae_predict_exact_comp_f64 (-1 also
+ * for a spec without components, -5 also for L > 65535); with out: -8 (mu NULL) -9 (ld_mu < L); -12 (nt < 0); with
+ * nt > 0: -10 (tx NULL) -11 (ldt) -13 (out_comp given and out NULL); with out: -14 (ld_out < L); -15 (info NULL) -16
+ * (workspace NULL or misaligned); with nt > 0 and out_comp: -18 (ld_comp < L) -19 (R > 1 and cstride_r < nt*ld_comp);
+ * with nt > 0: -20 (chunk < 1) -21 (out_ccov NULL).
+ *
+ * lvae_predict_comp_cov_f64: lvae_predict_comp_f64's arguments plus the test-row groups of lvae_predict_var_f64
+ * (n_groups, group_subject, group_start: test_x's rows grouped by subject) and out_ccov.  The model is
+ * lvae_predict_var_f64's structured one, its algebra run with one column per (test row i, component r), column
+ * i R + r, R = R0 + R1 <= 32, the components of spec0 first: a column r < R0 has K0zX* = k0_r(z, x*_i) and c = 0, a
+ * column r >= R0 has K0zX* = 0 and c = k1_{r-R0}(x_s(i), x*_i) on the subject's valid rows (0 for an absent
+ * subject); d, e, q, w, v follow from those columns by lvae_predict_var_f64's own kernels on the Nt R columns, and
+ *   out_ccov[l, i, r, s] = K0zX*_(i,r) . q_(i,s) + [r = s >= R0] k1_{r-R0}(x*_i, x*_i)
+ *                          - (q_(i,r) . w_(i,s) + e_(i,r) . q_(i,s) + c_(i,r) . d_(i,s)) + w_(i,r) . v_(i,s)
+ * by lvae_predict_cov_f64's tile products with a test row as the group and its components as the group's rows (up
+ * to 2 x 2 tiles of 16, on or below the diagonal and mirrored); block (l, i) at out_ccov[(l*Nt + i)*R*R];
+ * sum_{r,s} out_ccov[l, i] = lvae_predict_var_f64's out_var[i, l] (add_noise = 0) up to rounding.  The prior of the
+ * shared components is the Nystrom form k0_r(x*, z) K0zz^-1 k0_s(z, x*): in this model two different components of
+ * spec0 are correlated a priori, and a shared component's prior variance is not k0_r(x*, x*).  Every reduction runs
+ * over M or T in index order and a column's results do not depend on its neighbours, so a row's block does not
+ * depend on which other rows are in the call.  A component whose column is zero (an id component for an absent
+ * subject) gives exact zeros off the diagonal and its exact prior on it.  out (the mean) may be NULL (then mu may
+ * be too) and out_comp may be NULL; out_comp needs out.  When given, out, out_comp and info receive
+ * lvae_predict_comp_f64's bits (the same launches).  Nt == 0: info is written, nothing else is touched.
+ * workspace: lvae_predict_comp_cov_workspace_size(L, M, P, T, Nt, R0, R1) bytes = lvae_predict_var_workspace_size(L,
+ * M, P, T, Nt R) + the component products' slab partials (lvae_predict_comp_workspace_size -
+ * lvae_predict_workspace_size at Nt rows); 0 for sizes the call rejects (L < 1, M or T outside 1 .. 128, P < 1, Nt < 0, R0 or R1 outside 1 .. 16,
+ * Nt R > 2^31 - 1); 256-B aligned.
+ * Return codes (before any launch), in this order: -1 (a spec NULL, outside every template bucket, without
+ * components, or a factor dim outside 0 .. 31) -3 (L outside 1 .. 65535 or M outside 1 .. 128) -6 (P < 1, T outside
+ * 1 .. 128, Q < 1 + the largest column either spec reads) -8 (seg_len or include NULL) -9 (out given and mu NULL)
+ * -10 (x or z NULL) -11 (params0, params1 or noise NULL) -13 (Nt < 0 or Nt R > 2^31 - 1) -12 (Nt > 0 and test_x
+ * NULL) -14 (n_groups < 0) -15 (n_groups > 0 and group_subject or group_start NULL) -20 (workspace NULL or
+ * misaligned); with Nt > 0: -21 (out_comp given and out NULL) -22 (out_comp given and ld_comp < L) -23 (out_comp
+ * given and cstride_r < Nt*ld_comp) -24 (out_ccov NULL).  0 = ok.                                            */
+size_t lvae_predict_exact_comp_cov_workspace_size(int n, int nt, int L, int n_comp, int chunk);
+int lvae_predict_exact_comp_cov_f64(const lvae_kernel_spec* spec, const double* x, int64_t ldx, int n, int L,
+                                    const double* params, const double* noise, const double* mu, int64_t ld_mu,
+                                    const double* tx, int64_t ldt, int nt, double* out, int64_t ld_out,
+                                    double* out_comp, int64_t ld_comp, int64_t cstride_r, int chunk, double* out_ccov,
+                                    int32_t* info, void* workspace, void* stream);
+size_t lvae_predict_comp_cov_workspace_size(int L, int M, int P, int T, int Nt, int n_comp0, int n_comp1);
+int lvae_predict_comp_cov_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, int L, int M, int Q, int P,
+                              int T, const int32_t* seg_len, const int32_t* include, const double* x, const double* mu,
+                              const double* z, int Nt, const double* test_x, int n_groups,
+                              const int32_t* group_subject, const int32_t* group_start, const double* params0,
+                              const double* params1, const double* noise, double eps, double* out, double* out_comp,
+                              int64_t ld_comp, int64_t cstride_r, double* out_ccov, int32_t* info, void* workspace,
+                              void* stream);
+
 /* Exact-GP predictive variance (and, optionally, the mean) of the latent functions at test covariates, fp64.  With
  * K_l = k_l(x, x) + noise_l I = L_l L_l^T:
  *   out_var[t, l] = k_l(tx_t, tx_t) - |L_l^-1 k_l(x, tx_t)|^2  (+ noise_l when add_noise = 1)

@@ -20,10 +20,13 @@
 // same buffers, and lvae_predict_sample_f64 draws whole trajectories from it (kernels in predict_cov.hpp).
 // lvae_predict_exact_comp_f64 and lvae_predict_comp_f64 split the two means by additive component of the kernel
 // (both are linear in it): the same launches, then gram.hip's component-resolved cross-Gram x vector.
+// lvae_predict_exact_comp_cov_f64 and lvae_predict_comp_cov_f64 add the joint posterior covariance of the components
+// at each test row (kernels in predict_ccov.hpp).
 #include "small.hpp"
 #include "prof.hpp"
 #include "predict_var.hpp"
 #include "predict_cov.hpp"
+#include "predict_ccov.hpp"
 
 namespace lvae {
 namespace {
@@ -220,6 +223,13 @@ inline size_t exact_cov_part_bytes(int n, int nt, int L, int chunk) {
   return align256((size_t)L * (c > 0 ? c : 0) * exact_cov_slabs(n) * 256 * sizeof(double));
 }
 
+// workspace of lvae_predict_exact_comp_cov_f64 behind lvae_predict_exact_comp_f64's own: the component-resolved panel
+// k_r(X, X*_chunk) [L, n, c R], solved in place, and the slabs' partial tiles [L, c, nslab, 16, 16] (one tile a row)
+inline size_t exact_ccov_panel_bytes(int n, int nt, int L, int R, int chunk) {
+  const int c = chunk < nt ? chunk : nt;
+  return align256((size_t)L * n * (c > 0 ? c : 0) * R * sizeof(double));
+}
+
 // workspace of lvae_predict_sample_f64: the factors Lc [L, G, n_max, n_max] and their log-determinants [L G]
 struct SWs {
   double *Lc, *logdet;
@@ -346,40 +356,17 @@ static int exact_core(const lvae_kernel_spec* spec, const double* x, int64_t ldx
   return 0;
 }
 
-// The launches of lvae_predict_var_f64 up to its last kernel, on the carved workspaces w and v (arguments checked by
-// the caller): lvae_predict_f64's own (and the mean when out is given), then C, D, E, K0zX*, Q, W and V [rows, Nt].
-static int var_pipeline(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, int L, int M, int Q, int P, int T,
-                        const int32_t* seg_len, const int32_t* include, const double* x, const double* mu,
-                        const double* z, int Nt, const double* test_x, int n_groups, const int32_t* group_subject,
-                        const int32_t* group_start, const double* params0, const double* params1,
-                        const double* noise, double eps, double* out, int32_t* info, PWs& w, VWs& v, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  // the Grams, iB, K0zz^-1, H^-1 (and the mean) by lvae_predict_f64's own launches; G kept aside
-  LVAE_TRY(predict_core(spec0, spec1, L, M, Q, P, T, seg_len, include, x, mu, z, Nt, test_x, params0, params1, noise,
-                        eps, out, out != nullptr, v.Gm, info, w, stream));
-  if (Nt == 0) return 0;
+// Q, W and V of the variance routes from K0zX* (v.KzX) and E, each [L, M, N] with the N columns on the workspaces w
+// and v (after predict_core's launches); a column's results do not depend on its neighbours.
+static int var_solves(int L, int M, int N, PWs& w, VWs& v, hipStream_t st) {
+  const int Nt = N;
   const int64_t MM = (int64_t)M * M, MN = (int64_t)M * Nt;
   const size_t mn_bytes = (size_t)L * MN * sizeof(double);
-  const int b1 = spec_bucket(spec1);
-  const DevSpec d1 = to_dev(spec1);
-  // c_i, d_i = iB_s c_i, e_i = K0zx_s d_i per subject group (rows of no group, or of an absent subject: 0)
-  pv_rowsubj_kernel<<<nblk(Nt), 256, 0, st>>>(Nt, P, n_groups, group_subject, group_start, v.rs);
-  if (b1 == 1)
-    pv_c_kernel<8, 2><<<nblk((int64_t)L * T * Nt), 256, 0, st>>>(d1, L, T, Nt, Q, seg_len, v.rs, x, test_x, params1, v.C);
-  else
-    pv_c_kernel<16, 4><<<nblk((int64_t)L * T * Nt), 256, 0, st>>>(d1, L, T, Nt, Q, seg_len, v.rs, x, test_x, params1, v.C);
-  LVAE_TRY(zero_async(v.D, (size_t)L * T * Nt * sizeof(double), st));
-  LVAE_TRY(zero_async(v.E, mn_bytes, st));
-  if (n_groups > 0)
-    pv_group_kernel<<<dim3(Nt / kPvC + n_groups, L), 256, 0, st>>>(M, P, T, Nt, n_groups, group_subject, group_start,
-                                                                  v.C, w.iB, w.K0xz, v.D, v.E);
   // Q = K0zz^-1 K0zX* with one refinement step Q += K0zz^-1 (K0zX* - K0zz Q), as the mean refines its two products
   // with explicit inverses: the bare product is cond(K0zz) ulps off, and q enters the variance three times in
   // terms that cancel.  With this step and the one for V below, an fp64 emulation of the route against the dense
   // oracle gives 5e-15 of the largest prior variance at M = 128, eps = 1e-3 (cond K0zz 5e5) where the bare
-  // products give 1.5e-10; the tests' bound is 2e-12.  K0zX* [L, M, Nt] is its own Gram (test rows as columns).
-  const lvae_xview zv{z, 0, (int64_t)M * Q, Q}, tv{test_x, 0, 0, Q};
-  LVAE_TRY(lvae_gram_f64(spec0, zv, tv, 1, L, M, Nt, params0, nullptr, v.KzX, 0, MN, Nt, stream));
+  // products give 1.5e-10; the tests' bound is 2e-12.
   LVAE_TRY(gemm_small_f64(0, 0, M, Nt, M, 1.0, w.iK, M, MM, 0, v.KzX, Nt, MN, 0, 0.0, v.Qm, Nt, MN, 0, L, 1, st));
   LVAE_TRY(copy_words_async(v.R, v.KzX, mn_bytes, st));
   LVAE_TRY(gemm_small_f64(0, 0, M, Nt, M, -1.0, w.K0zz, M, MM, 0, v.Qm, Nt, MN, 0, 1.0, v.R, Nt, MN, 0, L, 1, st));
@@ -393,6 +380,38 @@ static int var_pipeline(const lvae_kernel_spec* spec0, const lvae_kernel_spec* s
   LVAE_TRY(gemm_small_f64(0, 0, M, Nt, M, 1.0, w.iH, M, MM, 0, v.R, Nt, MN, 0, 1.0, v.V, Nt, MN, 0, L, 1, st));
   LVAE_CHECK_LAUNCH();
   return 0;
+}
+
+// The launches of lvae_predict_var_f64 up to its last kernel, on the carved workspaces w and v (arguments checked by
+// the caller): lvae_predict_f64's own (and the mean when out is given), then C, D, E, K0zX*, Q, W and V [rows, Nt].
+static int var_pipeline(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, int L, int M, int Q, int P, int T,
+                        const int32_t* seg_len, const int32_t* include, const double* x, const double* mu,
+                        const double* z, int Nt, const double* test_x, int n_groups, const int32_t* group_subject,
+                        const int32_t* group_start, const double* params0, const double* params1,
+                        const double* noise, double eps, double* out, int32_t* info, PWs& w, VWs& v, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  // the Grams, iB, K0zz^-1, H^-1 (and the mean) by lvae_predict_f64's own launches; G kept aside
+  LVAE_TRY(predict_core(spec0, spec1, L, M, Q, P, T, seg_len, include, x, mu, z, Nt, test_x, params0, params1, noise,
+                        eps, out, out != nullptr, v.Gm, info, w, stream));
+  if (Nt == 0) return 0;
+  const size_t mn_bytes = (size_t)L * M * Nt * sizeof(double);
+  const int b1 = spec_bucket(spec1);
+  const DevSpec d1 = to_dev(spec1);
+  // c_i, d_i = iB_s c_i, e_i = K0zx_s d_i per subject group (rows of no group, or of an absent subject: 0)
+  pv_rowsubj_kernel<<<nblk(Nt), 256, 0, st>>>(Nt, P, n_groups, group_subject, group_start, v.rs);
+  if (b1 == 1)
+    pv_c_kernel<8, 2><<<nblk((int64_t)L * T * Nt), 256, 0, st>>>(d1, L, T, Nt, Q, seg_len, v.rs, x, test_x, params1, v.C);
+  else
+    pv_c_kernel<16, 4><<<nblk((int64_t)L * T * Nt), 256, 0, st>>>(d1, L, T, Nt, Q, seg_len, v.rs, x, test_x, params1, v.C);
+  LVAE_TRY(zero_async(v.D, (size_t)L * T * Nt * sizeof(double), st));
+  LVAE_TRY(zero_async(v.E, mn_bytes, st));
+  if (n_groups > 0)
+    pv_group_kernel<<<dim3(Nt / kPvC + n_groups, L), 256, 0, st>>>(M, P, T, Nt, n_groups, 1, group_subject,
+                                                                  group_start, v.C, w.iB, w.K0xz, v.D, v.E);
+  // K0zX* [L, M, Nt] is its own Gram (test rows as columns); then Q, W and V
+  const lvae_xview zv{z, 0, (int64_t)M * Q, Q}, tv{test_x, 0, 0, Q};
+  LVAE_TRY(lvae_gram_f64(spec0, zv, tv, 1, L, M, Nt, params0, nullptr, v.KzX, 0, (int64_t)M * Nt, Nt, stream));
+  return var_solves(L, M, Nt, w, v, st);
 }
 
 extern "C" {
@@ -525,6 +544,76 @@ int lvae_predict_exact_comp_f64(const lvae_kernel_spec* spec, const double* x, i
                               (char*)workspace + w.bytes, (hipStream_t)stream);
 }
 
+size_t lvae_predict_exact_comp_cov_workspace_size(int n, int nt, int L, int n_comp, int chunk) {
+  if (n < 1 || nt < 0 || L < 1 || n_comp < 1 || n_comp > LVAE_MAX_COMP || (nt > 0 && chunk < 1)) return 0;
+  return lvae_predict_exact_comp_workspace_size(n, nt, L, n_comp) + exact_ccov_panel_bytes(n, nt, L, n_comp, chunk) +
+         exact_cov_part_bytes(n, nt, L, chunk);
+}
+
+int lvae_predict_exact_comp_cov_f64(const lvae_kernel_spec* spec, const double* x, int64_t ldx, int n, int L,
+                                    const double* params, const double* noise, const double* mu, int64_t ld_mu,
+                                    const double* tx, int64_t ldt, int nt, double* out, int64_t ld_out,
+                                    double* out_comp, int64_t ld_comp, int64_t cstride_r, int chunk, double* out_ccov,
+                                    int32_t* info, void* workspace, void* stream) {
+  const int ld_min = spec ? gram_matvec_spec_ld(spec) : 0;
+  if (ld_min < 1 || ld_min > 32 || spec->n_comp < 1) return -1;  // (before any launch)
+  if (!x) return -2;
+  if (ldx < ld_min) return -3;
+  if (n < 1) return -4;
+  if (L < 1 || L > 65535) return -5;
+  if (!params) return -6;
+  if (!noise) return -7;
+  if (out && !mu) return -8;
+  if (out && ld_mu < L) return -9;
+  if (nt < 0) return -12;
+  if (nt > 0 && !tx) return -10;
+  if (nt > 0 && ldt < ld_min) return -11;
+  if (nt > 0 && out_comp && !out) return -13;
+  if (out && ld_out < L) return -14;
+  if (!info) return -15;
+  if (!workspace || ((uintptr_t)workspace & 255)) return -16;
+  if (nt > 0 && out_comp && ld_comp < L) return -18;
+  if (nt > 0 && out_comp && spec->n_comp > 1 && cstride_r < (int64_t)nt * ld_comp) return -19;
+  if (nt > 0 && chunk < 1) return -20;
+  if (nt > 0 && !out_ccov) return -21;
+  hipStream_t st = (hipStream_t)stream;
+  const int R = spec->n_comp;
+  EWs w((char*)workspace, n, nt, L);
+  char* mv = (char*)workspace + w.bytes;
+  double* panel = (double*)((char*)workspace + lvae_predict_exact_comp_workspace_size(n, nt, L, R));
+  double* part = (double*)((char*)panel + exact_ccov_panel_bytes(n, nt, L, R, chunk));
+  // the factor of K, and when wanted the mean and its split, by lvae_predict_exact_comp_f64's own launches
+  LVAE_TRY(exact_core(spec, x, ldx, n, L, params, noise, mu, ld_mu, tx, ldt, nt, out, ld_out, info, w, stream));
+  if (nt == 0) return 0;
+  if (out && out_comp)
+    LVAE_TRY(gram_matvec_comp_f64(spec, tx, ldt, nt, x, ldx, 0, n, L, params, w.a, n, 1, out_comp, ld_comp, 0,
+                                  cstride_r, mv, st));
+  // c test rows at a time: the component-resolved panel k_r(X, X*_chunk) [L, n, c R] (column t R + r), one
+  // triangular solve in place on its c R columns, then per row the slabs' partial tiles of V^T V and their sum in
+  // slab order under the components' prior variances.  A column's solve does not depend on its neighbours and a
+  // tile's slabs depend on n alone, so the bits do not depend on the chunk.
+  const int c = chunk < nt ? chunk : nt, nslab = exact_cov_slabs(n), bucket = spec_bucket(spec);
+  const DevSpec ds = to_dev(spec);
+  const int64_t ldp = (int64_t)c * R;
+  for (int c0 = 0; c0 < nt; c0 += c) {
+    const int nr = nt - c0 < c ? nt - c0 : c;
+    const double* tc = tx + (int64_t)c0 * ldt;
+    const int pb = nblk((int64_t)L * n * nr);
+    if (bucket == 1)
+      pcc_panel_kernel<2><<<pb, 256, 0, st>>>(ds, L, n, nr, x, ldx, tc, ldt, params, panel, ldp);
+    else
+      pcc_panel_kernel<4><<<pb, 256, 0, st>>>(ds, L, n, nr, x, ldx, tc, ldt, params, panel, ldp);
+    LVAE_TRY(lvae_trsm_f64(0, n, nr * R, L, w.K, n, (int64_t)n * n, panel, ldp, (int64_t)n * ldp, w.trsm, stream));
+    pcc_partial_kernel<<<dim3(nr, nslab, L), 64, 0, st>>>(n, R, panel, ldp, c, part);
+    if (bucket == 1)
+      pcc_reduce_kernel<2><<<dim3(nr, L), 256, 0, st>>>(ds, nslab, c, part, tc, ldt, params, c0, nt, out_ccov);
+    else
+      pcc_reduce_kernel<4><<<dim3(nr, L), 256, 0, st>>>(ds, nslab, c, part, tc, ldt, params, c0, nt, out_ccov);
+  }
+  LVAE_CHECK_LAUNCH();
+  return 0;
+}
+
 size_t lvae_predict_exact_var_workspace_size(int n, int nt, int L, int chunk) {
   if (n < 1 || nt < 0 || L < 1 || (nt > 0 && chunk < 1)) return 0;
   return EWs(nullptr, n, nt, L).bytes + exact_var_panel_bytes(n, nt, L, chunk);
@@ -625,6 +714,88 @@ int lvae_predict_var_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* 
   else
     pv_var_kernel<16, 4><<<nblk((int64_t)L * Nt), 256, 0, st>>>(d1, L, M, T, Nt, Q, v.KzX, v.Qm, v.W, v.E, v.V, v.C, v.D,
                                                                 test_x, params1, noise, add_noise, out_var);
+  LVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+size_t lvae_predict_comp_cov_workspace_size(int L, int M, int P, int T, int Nt, int n_comp0, int n_comp1) {
+  const int64_t R = (int64_t)n_comp0 + n_comp1;
+  if (L < 1 || M < 1 || M > 128 || P < 1 || T < 1 || T > 128 || Nt < 0 || n_comp0 < 1 || n_comp1 < 1 ||
+      n_comp0 > LVAE_MAX_COMP || n_comp1 > LVAE_MAX_COMP || Nt * R > INT32_MAX)
+    return 0;
+  return lvae_predict_var_workspace_size(L, M, P, T, (int)(Nt * R)) +
+         predict_comp_mv_bytes(L, M, P, T, Nt, n_comp0, n_comp1);
+}
+
+int lvae_predict_comp_cov_f64(const lvae_kernel_spec* spec0, const lvae_kernel_spec* spec1, int L, int M, int Q, int P,
+                              int T, const int32_t* seg_len, const int32_t* include, const double* x, const double* mu,
+                              const double* z, int Nt, const double* test_x, int n_groups,
+                              const int32_t* group_subject, const int32_t* group_start, const double* params0,
+                              const double* params1, const double* noise, double eps, double* out, double* out_comp,
+                              int64_t ld_comp, int64_t cstride_r, double* out_ccov, int32_t* info, void* workspace,
+                              void* stream) {
+  if (!spec0 || !spec1 || !spec_bucket(spec0) || !spec_bucket(spec1)) return -1;  // (before any launch)
+  const int ld0 = gram_matvec_spec_ld(spec0), ld1 = gram_matvec_spec_ld(spec1);
+  if (ld0 < 1 || ld1 < 1 || spec0->n_comp < 1 || spec1->n_comp < 1) return -1;
+  if (L < 1 || L > 65535 || M < 1 || M > 128) return -3;
+  if (P < 1 || T < 1 || T > 128 || Q < 1 || Q < ld0 || Q < ld1) return -6;
+  if (!seg_len || !include) return -8;
+  if (out && !mu) return -9;
+  if (!x || !z) return -10;
+  if (!params0 || !params1 || !noise) return -11;
+  const int R0 = spec0->n_comp, R1 = spec1->n_comp, R = R0 + R1;
+  if (Nt < 0 || (int64_t)Nt * R > INT32_MAX) return -13;
+  if (Nt > 0 && !test_x) return -12;
+  if (n_groups < 0) return -14;
+  if (n_groups > 0 && (!group_subject || !group_start)) return -15;
+  if (!workspace || ((uintptr_t)workspace & 255)) return -20;
+  if (Nt > 0 && out_comp && !out) return -21;
+  if (Nt > 0 && out_comp && ld_comp < L) return -22;
+  if (Nt > 0 && out_comp && cstride_r < (int64_t)Nt * ld_comp) return -23;
+  if (Nt > 0 && !out_ccov) return -24;
+  hipStream_t st = (hipStream_t)stream;
+  const int Nc = Nt * R, nc1 = Nc > 0 ? Nc : 1;  // one column per (test row, component)
+  PWs w((char*)workspace, L, M, P, T, nc1);
+  VWs v((char*)workspace, w.bytes, L, M, T, nc1);
+  void* mv = (char*)workspace + v.bytes;
+  // the Grams, iB, K0zz^-1, H^-1 and, when wanted, the mean by lvae_predict_f64's own launches (a workspace carved
+  // for Nt R rows leaves them as they are); G kept aside; then the mean's split as lvae_predict_comp_f64
+  LVAE_TRY(predict_core(spec0, spec1, L, M, Q, P, T, seg_len, include, x, mu, z, Nt, test_x, params0, params1, noise,
+                        eps, out, out != nullptr, v.Gm, info, w, stream));
+  if (Nt == 0) return 0;
+  if (out && out_comp) {
+    LVAE_TRY(gram_matvec_comp_f64(spec0, test_x, Q, Nt, z, Q, (int64_t)M * Q, M, L, params0, w.b, M, 1, out_comp,
+                                  ld_comp, 0, cstride_r, mv, st));
+    LVAE_TRY(gram_matvec_comp_f64(spec1, test_x, Q, Nt, x, Q, 0, P * T, L, params1, w.muTm, (int64_t)P * T, 1,
+                                  out_comp + (int64_t)R0 * cstride_r, ld_comp, 0, cstride_r, mv, st));
+  }
+  // the columns' K0zX* and C through the specs, D and E per subject group (group g: the columns
+  // [R group_start[g], R group_start[g + 1])), Q, W and V by the variance route's own launches, then the blocks
+  const DevSpec d0 = to_dev(spec0), d1 = to_dev(spec1);
+  pv_rowsubj_kernel<<<nblk(Nt), 256, 0, st>>>(Nt, P, n_groups, group_subject, group_start, v.rs);
+  if (spec_bucket(spec0) == 1)
+    pcc_kzx_kernel<2><<<nblk((int64_t)L * M * Nt), 256, 0, st>>>(d0, L, M, Nt, Q, R, z, test_x, params0, v.KzX);
+  else
+    pcc_kzx_kernel<4><<<nblk((int64_t)L * M * Nt), 256, 0, st>>>(d0, L, M, Nt, Q, R, z, test_x, params0, v.KzX);
+  if (spec_bucket(spec1) == 1)
+    pcc_c_kernel<2><<<nblk((int64_t)L * T * Nt), 256, 0, st>>>(d1, L, T, Nt, Q, R0, seg_len, v.rs, x, test_x, params1,
+                                                               v.C);
+  else
+    pcc_c_kernel<4><<<nblk((int64_t)L * T * Nt), 256, 0, st>>>(d1, L, T, Nt, Q, R0, seg_len, v.rs, x, test_x, params1,
+                                                               v.C);
+  LVAE_TRY(zero_async(v.D, (size_t)L * T * Nc * sizeof(double), st));
+  LVAE_TRY(zero_async(v.E, (size_t)L * M * Nc * sizeof(double), st));
+  if (n_groups > 0)
+    pv_group_kernel<<<dim3(Nc / kPvC + n_groups, L), 256, 0, st>>>(M, P, T, Nc, n_groups, R, group_subject,
+                                                                  group_start, v.C, w.iB, w.K0xz, v.D, v.E);
+  LVAE_TRY(var_solves(L, M, Nc, w, v, st));
+  const dim3 grid((unsigned)Nt * cov_tiles(R), L);
+  if (spec_bucket(spec1) == 1)
+    pcc_ind_kernel<2><<<grid, 64, 0, st>>>(d1, M, T, Nt, Q, R0, v.KzX, v.Qm, v.W, v.E, v.V, v.C, v.D, test_x, params1,
+                                           out_ccov);
+  else
+    pcc_ind_kernel<4><<<grid, 64, 0, st>>>(d1, M, T, Nt, Q, R0, v.KzX, v.Qm, v.W, v.E, v.V, v.C, v.D, test_x, params1,
+                                           out_ccov);
   LVAE_CHECK_LAUNCH();
   return 0;
 }

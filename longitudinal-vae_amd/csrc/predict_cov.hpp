@@ -54,12 +54,48 @@ __global__ __launch_bounds__(256) void pc_eye_kernel(int64_t nb, int n_max, doub
 }
 
 // ---- inducing-point route ----
-// One 64-lane workgroup per (tile, group, dim) on v_mfma_f64_16x16x4 (operand layout as pv_group_kernel:
+// The five products of one 16 x 16 tile on v_mfma_f64_16x16x4 (operand layout as pv_group_kernel:
 // A[row = lane & 15][k = lane >> 4], B[k = lane >> 4][col = lane & 15], acc[r] = C[(lane >> 4) + 4 r][lane & 15]).
-// Every operand is a [rows, Nt] matrix with the test rows as columns, so the 16 lanes of a k step read contiguous
-// doubles straight from memory (each element is read once per workgroup: no LDS stage).  Group g: the columns
-// [gstart[g], gstart[g + 1]) clamped to 0 .. Nt, of which the first n_max are used.  Tiles past the group's rows
-// do nothing.  The five products keep an accumulator each and are combined as pv_var_kernel combines its sums.
+// Every operand is a [rows, ld] matrix with the tile's rows and columns among its columns, so the 16 lanes of a k
+// step read contiguous doubles straight from memory (each element is read once per workgroup: no LDS stage).  om /
+// ot: the dim's [M, ld] / [T, ld] matrix at the group's first column; this lane holds column i of the A operands
+// and column j of the B operands (vi / vj: inside the group).  The sums run over M and T in index order.  Shared
+// with predict_ccov.hpp, where a test row's components take the role of a group's rows.
+struct CovAcc {
+  pv_f64x4 kq, qw, eq, cd, wv;
+};
+__device__ inline CovAcc cov_products(int M, int T, int64_t ld, int64_t om, int64_t ot, int i, int j, bool vi, bool vj,
+                                      const double* __restrict__ KzX, const double* __restrict__ Qm,
+                                      const double* __restrict__ W, const double* __restrict__ E,
+                                      const double* __restrict__ V, const double* __restrict__ C,
+                                      const double* __restrict__ D) {
+  const int lk = threadIdx.x >> 4;
+  pv_f64x4 kq = {0.0, 0.0, 0.0, 0.0}, qw = kq, eq = kq, cd = kq, wv = kq;
+  for (int kk = 0; kk < M; kk += 4) {
+    const int m = kk + lk;
+    const bool ok = m < M;
+    const int64_t oi = om + (int64_t)m * ld + i, oj = om + (int64_t)m * ld + j;
+    const double k_i = (ok && vi) ? KzX[oi] : 0.0, q_i = (ok && vi) ? Qm[oi] : 0.0;
+    const double e_i = (ok && vi) ? E[oi] : 0.0, w_i = (ok && vi) ? W[oi] : 0.0;
+    const double q_j = (ok && vj) ? Qm[oj] : 0.0, w_j = (ok && vj) ? W[oj] : 0.0, v_j = (ok && vj) ? V[oj] : 0.0;
+    kq = __builtin_amdgcn_mfma_f64_16x16x4f64(k_i, q_j, kq, 0, 0, 0);
+    qw = __builtin_amdgcn_mfma_f64_16x16x4f64(q_i, w_j, qw, 0, 0, 0);
+    eq = __builtin_amdgcn_mfma_f64_16x16x4f64(e_i, q_j, eq, 0, 0, 0);
+    wv = __builtin_amdgcn_mfma_f64_16x16x4f64(w_i, v_j, wv, 0, 0, 0);
+  }
+  for (int kk = 0; kk < T; kk += 4) {
+    const int t = kk + lk;
+    const bool ok = t < T;
+    const double c_i = (ok && vi) ? C[ot + (int64_t)t * ld + i] : 0.0;
+    const double d_j = (ok && vj) ? D[ot + (int64_t)t * ld + j] : 0.0;
+    cd = __builtin_amdgcn_mfma_f64_16x16x4f64(c_i, d_j, cd, 0, 0, 0);
+  }
+  return CovAcc{kq, qw, eq, cd, wv};
+}
+
+// One 64-lane workgroup per (tile, group, dim).  Group g: the columns [gstart[g], gstart[g + 1]) clamped to
+// 0 .. Nt, of which the first n_max are used.  Tiles past the group's rows do nothing.  The five products
+// (cov_products) keep an accumulator each and are combined as pv_var_kernel combines its sums.
 template <int MC, int MF>
 __global__ __launch_bounds__(64) void pc_cov_kernel(DevSpec s, int M, int T, int Nt, int Q, int n_max,
                                                     const int32_t* __restrict__ gstart,
@@ -81,26 +117,8 @@ __global__ __launch_bounds__(64) void pc_cov_kernel(DevSpec s, int M, int T, int
   const int i = ti * kPvC + li, j = tj * kPvC + li;  // this lane's row of the A operands, column of the B operands
   const bool vi = i < ng, vj = j < ng;
   const int64_t om = (int64_t)l * M * Nt + a, ot = (int64_t)l * T * Nt + a;
-  pv_f64x4 kq = {0.0, 0.0, 0.0, 0.0}, qw = kq, eq = kq, cd = kq, wv = kq;
-  for (int kk = 0; kk < M; kk += 4) {
-    const int m = kk + lk;
-    const bool ok = m < M;
-    const int64_t oi = om + (int64_t)m * Nt + i, oj = om + (int64_t)m * Nt + j;
-    const double k_i = (ok && vi) ? KzX[oi] : 0.0, q_i = (ok && vi) ? Qm[oi] : 0.0;
-    const double e_i = (ok && vi) ? E[oi] : 0.0, w_i = (ok && vi) ? W[oi] : 0.0;
-    const double q_j = (ok && vj) ? Qm[oj] : 0.0, w_j = (ok && vj) ? W[oj] : 0.0, v_j = (ok && vj) ? V[oj] : 0.0;
-    kq = __builtin_amdgcn_mfma_f64_16x16x4f64(k_i, q_j, kq, 0, 0, 0);
-    qw = __builtin_amdgcn_mfma_f64_16x16x4f64(q_i, w_j, qw, 0, 0, 0);
-    eq = __builtin_amdgcn_mfma_f64_16x16x4f64(e_i, q_j, eq, 0, 0, 0);
-    wv = __builtin_amdgcn_mfma_f64_16x16x4f64(w_i, v_j, wv, 0, 0, 0);
-  }
-  for (int kk = 0; kk < T; kk += 4) {
-    const int t = kk + lk;
-    const bool ok = t < T;
-    const double c_i = (ok && vi) ? C[ot + (int64_t)t * Nt + i] : 0.0;
-    const double d_j = (ok && vj) ? D[ot + (int64_t)t * Nt + j] : 0.0;
-    cd = __builtin_amdgcn_mfma_f64_16x16x4f64(c_i, d_j, cd, 0, 0, 0);
-  }
+  const CovAcc p = cov_products(M, T, Nt, om, ot, i, j, vi, vj, KzX, Qm, W, E, V, C, D);
+  const pv_f64x4 kq = p.kq, qw = p.qw, eq = p.eq, cd = p.cd, wv = p.wv;
   double* blk = cov + ((int64_t)l * G + g) * n_max * n_max;
   const double* pl = params + (int64_t)l * s.n_params;
 #pragma unroll
@@ -123,6 +141,23 @@ __device__ inline int cov_batch_group(const CovBatch& cb, int x) {
   return b;
 }
 
+// One slab's share of a 16 x 16 tile of V^T V: sum over the rows r0 <= r < r1 of pl[r][i] pl[r][j], four rows a step
+// in index order; this lane holds column i of the A operand and column j of the B operand (vi / vj: inside the
+// group).  Shared with predict_ccov.hpp, where a test row's components take the role of a group's rows.
+__device__ inline pv_f64x4 cov_slab_tile(const double* __restrict__ pl, int64_t ldp, int i, int j, bool vi, bool vj,
+                                         int r0, int r1) {
+  const int lk = threadIdx.x >> 4;
+  pv_f64x4 acc = {0.0, 0.0, 0.0, 0.0};
+  for (int kk = r0; kk < r1; kk += 4) {
+    const int r = kk + lk;
+    const bool ok = r < r1;
+    const double v_i = (ok && vi) ? pl[(int64_t)r * ldp + i] : 0.0;
+    const double v_j = (ok && vj) ? pl[(int64_t)r * ldp + j] : 0.0;
+    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(v_i, v_j, acc, 0, 0, 0);
+  }
+  return acc;
+}
+
 // part[l][tile0 + x][slab][16][16] = the slab's share of V_g^T V_g on tile x: one 64-lane workgroup per
 // (tile, slab, dim), panel [L, n, ldp] (this chunk's solved columns), tcap tiles per dim in part
 __global__ __launch_bounds__(64) void pcx_partial_kernel(CovBatch cb, int n, const double* __restrict__ panel,
@@ -136,14 +171,7 @@ __global__ __launch_bounds__(64) void pcx_partial_kernel(CovBatch cb, int n, con
   const bool vi = i < ng, vj = j < ng;
   const int r0 = slab * kCovSlab, r1 = r0 + kCovSlab < n ? r0 + kCovSlab : n;
   const double* pl = panel + (int64_t)l * n * ldp + c0;
-  pv_f64x4 acc = {0.0, 0.0, 0.0, 0.0};
-  for (int kk = r0; kk < r1; kk += 4) {
-    const int r = kk + lk;
-    const bool ok = r < r1;
-    const double v_i = (ok && vi) ? pl[(int64_t)r * ldp + i] : 0.0;
-    const double v_j = (ok && vj) ? pl[(int64_t)r * ldp + j] : 0.0;
-    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(v_i, v_j, acc, 0, 0, 0);
-  }
+  const pv_f64x4 acc = cov_slab_tile(pl, ldp, i, j, vi, vj, r0, r1);
   double* po = part + ((((int64_t)l * tcap + tile0 + blockIdx.x) * nslab + slab) << 8);
 #pragma unroll
   for (int r = 0; r < 4; ++r) po[(lk + 4 * r) * kPvC + li] = acc[r];

@@ -91,8 +91,9 @@ __global__ __launch_bounds__(256) void pv_c_kernel(DevSpec s, int L, int T, int 
 // walking the groups (ceil(len / 16) tiles each); tiles past the last group and groups of absent subjects do
 // nothing (D and E are zeroed beforehand).  iB is read through its symmetry, iB[k][row], so that the 16 lanes of
 // a k read contiguous doubles; K0xz [NP, M] gives K0zx[m][t] the same way.  Padding rows (t >= seg_len) carry
-// C = 0 and the identity in iB, and zero rows of K0xz: they add nothing to D or E.
-__global__ __launch_bounds__(256) void pv_group_kernel(int M, int P, int T, int Nt, int G,
+// C = 0 and the identity in iB, and zero rows of K0xz: they add nothing to D or E.  cpr: columns per test row (1
+// here; the component-resolved route of predict_ccov.hpp has n_comp columns a row, and Nt counts columns).
+__global__ __launch_bounds__(256) void pv_group_kernel(int M, int P, int T, int Nt, int G, int cpr,
                                                        const int32_t* __restrict__ gsub,
                                                        const int32_t* __restrict__ gstart,
                                                        const double* __restrict__ C, const double* __restrict__ iB,
@@ -105,14 +106,14 @@ __global__ __launch_bounds__(256) void pv_group_kernel(int M, int P, int T, int 
   if (tid == 0) {
     int left = blockIdx.x, p = -1, i0 = 0, nc = 0;
     for (int g = 0; g < G; ++g) {
-      int a = gstart[g], b = gstart[g + 1];
+      int64_t a = (int64_t)gstart[g] * cpr, b = (int64_t)gstart[g + 1] * cpr;
       a = a < 0 ? 0 : (a > Nt ? Nt : a);
       b = b < a ? a : (b > Nt ? Nt : b);
-      const int ntile = (b - a + kPvC - 1) / kPvC;
+      const int ntile = (int)((b - a + kPvC - 1) / kPvC);
       if (left < ntile) {
         p = gsub[g];
-        i0 = a + kPvC * left;
-        nc = b - i0 < kPvC ? b - i0 : kPvC;
+        i0 = (int)a + kPvC * left;
+        nc = (int)b - i0 < kPvC ? (int)b - i0 : kPvC;
         break;
       }
       left -= ntile;

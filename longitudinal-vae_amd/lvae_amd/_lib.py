@@ -218,6 +218,16 @@ SIGNATURES = {
     "lvae_predict_comp_workspace_size": (_SZ, [_I32, _I32, _I32, _I32, _I32, _I32, _I32]),
     "lvae_predict_comp_f64": (_I32, [_SPEC, _SPEC, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _I32, _VP,
                                      _VP, _VP, _VP, _D, _VP, _VP, _I64, _I64, _VP, _VP, _VP]),
+    # the components' joint covariance per test row: lvae_predict_exact_comp_f64's arguments with (chunk, out_ccov)
+    # after cstride_r; lvae_predict_comp_f64's with (n_groups, group_subject, group_start) after test_x and out_ccov
+    # after cstride_r
+    "lvae_predict_exact_comp_cov_workspace_size": (_SZ, [_I32, _I32, _I32, _I32, _I32]),
+    "lvae_predict_exact_comp_cov_f64": (_I32, [_SPEC, _VP, _I64, _I32, _I32, _VP, _VP, _VP, _I64, _VP, _I64, _I32,
+                                               _VP, _I64, _VP, _I64, _I64, _I32, _VP, _VP, _VP, _VP]),
+    "lvae_predict_comp_cov_workspace_size": (_SZ, [_I32, _I32, _I32, _I32, _I32, _I32, _I32]),
+    "lvae_predict_comp_cov_f64": (_I32, [_SPEC, _SPEC, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _I32,
+                                         _VP, _I32, _VP, _VP, _VP, _VP, _VP, _D, _VP, _VP, _I64, _I64, _VP, _VP, _VP,
+                                         _VP]),
     "lvae_predict_exact_var_workspace_size": (_SZ, [_I32, _I32, _I32, _I32]),
     "lvae_predict_exact_var_f64": (_I32, [_SPEC, _VP, _I64, _I32, _I32, _VP, _VP, _VP, _I64, _VP, _I64, _I32, _VP,
                                           _I64, _VP, _I64, _I32, _I32, _VP, _VP, _VP]),

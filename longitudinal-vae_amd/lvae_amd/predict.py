@@ -11,6 +11,11 @@ draws from the resulting marginals.  ``return_cov=True`` returns the joint covar
 lvae_predict_exact_cov_f64), and ``sample_trajectories`` draws each group's rows jointly from it
 (lvae_predict_sample_f64).  Groups are independent of each other: the covariance between rows of different groups
 is not zero in the model, and is neither returned nor drawn from.
+
+``predict_exact_components`` and ``batch_predict_components`` split the two means by additive component of the kernel
+(a ``LatentComponents``); with ``return_cov=True`` they add the joint posterior covariance of the components at each
+test row (lvae_predict_exact_comp_cov_f64, lvae_predict_comp_cov_f64): per-effect credible bands, and the
+uncertainty of the reconstruction after the first k effects.
 """
 import ctypes
 
@@ -334,10 +339,16 @@ class LatentComponents:
     ``values`` [R, Nt, L] fp64: component r's share of Z_pred, in the caller's row order.  ``labels`` [R]: the
     component's factors, e.g. ``"rbf(0)"`` or ``"cat(3)*rbf(0)"`` (kind(covariate column); a masked factor carries
     its ``*bin(d)``).  ``module`` [R]: 0 for a component of ``covar_module0`` (or of the exact route's one kernel),
-    1 for one of ``covar_module1``; the components of module 0 come first."""
+    1 for one of ``covar_module1``; the components of module 0 come first.
 
-    def __init__(self, values, labels, module):
-        self.values, self.labels, self.module = values, list(labels), list(module)
+    ``cov`` [L, Nt, R, R] fp64 or None (``return_cov=True``): block (l, i) is the joint posterior covariance of the R
+    component functions at test row i in latent dim l, the raw difference prior - explained (not clamped),
+    symmetric bit for bit; the observation noise belongs to no component and is not in it.  Covariances between
+    components at different test rows are not held.  ``variance``, ``total_variance``, ``partial_variance`` and
+    ``credible_interval`` read it and raise ValueError without it."""
+
+    def __init__(self, values, labels, module, cov=None):
+        self.values, self.labels, self.module, self.cov = values, list(labels), list(module), cov
 
     def total(self):
         """[Nt, L]: the sum over components, Z_pred up to rounding"""
@@ -353,6 +364,47 @@ class LatentComponents:
         den = var.sum(0, keepdim=True)
         return torch.where(den > 0, var / torch.where(den > 0, den, torch.ones_like(den)), torch.zeros_like(var))
 
+    def _need_cov(self, what):
+        if self.cov is None:
+            raise ValueError(f"LatentComponents.{what}() needs the components' covariance: predict with "
+                             "return_cov=True")
+        return self.cov
+
+    def variance(self):
+        """[R, Nt, L]: each component's posterior variance at each test row (the blocks' diagonals), clamped at 0"""
+        cov = self._need_cov("variance")
+        return torch.diagonal(cov, dim1=2, dim2=3).permute(2, 1, 0).clamp(min=0.0)
+
+    def total_variance(self):
+        """[Nt, L]: the sum of a block over both component indices, the predictive variance of the latent function
+        itself (``return_var=True`` without noise, up to rounding; not clamped)"""
+        return self._need_cov("total_variance").sum(dim=(2, 3)).T
+
+    def partial_variance(self, order=None):
+        """[R', Nt, L]: entry k is the posterior variance of the sum of the first k + 1 components of ``order``
+        (default: all R as stored, the order of ``generate_component_sequences``), the uncertainty of the
+        reconstruction after those effects; with every component in ``order`` the last entry is
+        ``total_variance()`` up to rounding.  Clamped at 0."""
+        cov = self._need_cov("partial_variance")
+        R = int(cov.shape[2])
+        order = list(range(R)) if order is None else [int(r) for r in order]
+        if not order or any(r < 0 or r >= R for r in order) or len(set(order)) != len(order):
+            raise ValueError(f"order {order} must name at least one component, each in 0 .. {R - 1}, none twice")
+        idx = torch.tensor(order, dtype=torch.long, device=cov.device)
+        sub = cov.index_select(2, idx).index_select(3, idx)
+        lead = torch.diagonal(sub.cumsum(2).cumsum(3), dim1=2, dim2=3)      # [L, Nt, R']: the leading blocks' sums
+        return lead.permute(2, 1, 0).clamp(min=0.0)
+
+    def credible_interval(self, level=0.95):
+        """``(lo, hi)``, each [R, Nt, L]: ``values -+ z sqrt(variance())`` with z the standard normal quantile of
+        (1 + level) / 2 (1.959964 at 0.95): each component's marginal credible band at each test row"""
+        if not 0.0 < float(level) < 1.0:
+            raise ValueError(f"level {level} must lie in (0, 1)")
+        var = self.variance()
+        z = torch.special.ndtri(torch.tensor(0.5 + 0.5 * float(level), dtype=torch.float64, device=var.device))
+        half = z * torch.sqrt(var)
+        return self.values - half, self.values + half
+
 
 def component_labels(covar_module):
     """The labels of a kernel's additive components, from ``kernel.components()`` (a per-dim list: its first
@@ -363,27 +415,53 @@ def component_labels(covar_module):
 
 
 def predict_exact_components(covar_module, likelihoods, prediction_x, test_x, prediction_mu,
-                             max_workspace_bytes=4 << 30):
+                             max_workspace_bytes=4 << 30, return_cov=False):
     """``(Z_pred, comps)``: ``predict_exact``'s Z_pred [N_test, L] (the same launches, the same bits) and its split
     by additive component of ``covar_module`` as a LatentComponents, ``comps.values[r] = k_r(X*, X) alpha`` with
     alpha = (k(X, X) + noise I)^-1 mu as the mean uses it (lvae_predict_exact_comp_f64: one fused pass over the
     cross-Gram for all components, no [N_test, N] Gram formed).  Arguments, the dim groups under
-    ``max_workspace_bytes`` and the errors are ``predict_exact``'s; the groups do not change the bits."""
+    ``max_workspace_bytes`` and the errors are ``predict_exact``'s; the groups do not change the bits.
+
+    ``return_cov=True`` also fills ``comps.cov`` [L, N_test, R, R]: per latent dim and test row the joint posterior
+    covariance of the R component functions, ``delta_rs k_r(x*, x*) - V_r . V_s`` with V_r = L^-1 k_r(X, x*)
+    (lvae_predict_exact_comp_cov_f64; N^2 R N_test flops a dim in the solves, R times the variance's).  The test
+    rows are then solved in chunks (8 N R bytes a row and dim) sized, after the dim groups, to keep the workspace
+    under ``max_workspace_bytes``; neither choice changes the bits.  With the default nothing new runs and the
+    result is today's bit for bit, ``comps.cov`` None."""
     lib = _lib.lib()
     spec, L, dev, x, tx, mu, p, noise, n, nt, n_params = _exact_inputs(covar_module, likelihoods, prediction_x, test_x,
                                                                        prediction_mu)
     R = int(spec.n_comp)
-    size = lambda g: int(lib.lvae_predict_exact_comp_workspace_size(n, nt, g, R))
+    chunk = 1   # (the smallest panel decides the dim groups; the chunk then takes what is left)
+    if return_cov:
+        size = lambda g: int(lib.lvae_predict_exact_comp_cov_workspace_size(n, nt, g, R, chunk))
+    else:
+        size = lambda g: int(lib.lvae_predict_exact_comp_workspace_size(n, nt, g, R))
     group = L
     while group > 1 and size(group) > max_workspace_bytes:
         group -= 1
+    if return_cov and nt:
+        chunk = nt
+        while chunk > 1 and size(group) > max_workspace_bytes:
+            chunk = (chunk + 1) // 2
     out = torch.empty(nt, L, dtype=torch.float64, device=dev)
     vals = torch.empty(R, nt, L, dtype=torch.float64, device=dev)
+    cov = torch.empty(L, nt, R, R, dtype=torch.float64, device=dev) if return_cov else None
     info = torch.empty(L, dtype=torch.int32, device=dev)
     ws = torch.empty(size(group), dtype=torch.uint8, device=dev)
     at = lambda t, off: ctypes.c_void_p(t.data_ptr() + 8 * off)
     for l0 in range(0, L, group):
         g = min(group, L - l0)
+        if return_cov:
+            rc = lib.lvae_predict_exact_comp_cov_f64(spec, _lib.ptr(x), x.stride(0), n, g, at(p, l0 * n_params),
+                                                     at(noise, l0), at(mu, l0), L, _lib.ptr(tx) if nt else None,
+                                                     tx.stride(0), nt, at(out, l0) if nt else None, L,
+                                                     at(vals, l0) if nt else None, L, nt * L, chunk,
+                                                     at(cov, l0 * nt * R * R) if nt else None,
+                                                     ctypes.c_void_p(info.data_ptr() + 4 * l0), _lib.ptr(ws),
+                                                     _lib.stream_ptr())
+            _lib.check(rc, "predict_exact_comp_cov")
+            continue
         rc = lib.lvae_predict_exact_comp_f64(spec, _lib.ptr(x), x.stride(0), n, g, at(p, l0 * n_params),
                                              at(noise, l0), at(mu, l0), L, _lib.ptr(tx) if nt else None,
                                              tx.stride(0), nt, at(out, l0) if nt else None, L,
@@ -392,32 +470,107 @@ def predict_exact_components(covar_module, likelihoods, prediction_x, test_x, pr
                                              _lib.stream_ptr())
         _lib.check(rc, "predict_exact_comp")
     _check_info(info, "predict_exact cholesky of k(X, X) + noise I")
-    return out, LatentComponents(vals, component_labels(covar_module), [0] * R)
+    return out, LatentComponents(vals, component_labels(covar_module), [0] * R, cov)
 
 
 def batch_predict_components(latent_dim, covar_module0, covar_module1, likelihoods, prediction_x, test_x, mu,
-                             zt_list, id_covariate, eps):
+                             zt_list, id_covariate, eps, return_cov=False, max_workspace_bytes=4 << 30):
     """``(Z_pred, comps)``: ``batch_predict_varying_T``'s Z_pred [N_test, L] (the same launches, the same bits) and
     its split by additive component as a LatentComponents: the components of ``covar_module0`` first,
     ``k0_r(X*, z) K0zz^-1 K0zx mu~``, then those of ``covar_module1``, ``k1_r(X*, x) mu~`` over the prediction rows
-    of the test subjects (lvae_predict_comp_f64).  Arguments and errors are ``batch_predict_varying_T``'s."""
+    of the test subjects (lvae_predict_comp_f64).  Arguments and errors are ``batch_predict_varying_T``'s.
+
+    ``return_cov=True`` also fills ``comps.cov`` [L, N_test, R, R], R = R0 + R1: per latent dim and test row the
+    joint posterior covariance of the component functions in the structured model of ``return_var=True``
+    (lvae_predict_comp_cov_f64: that route's algebra with one column per (test row, component)).  In that model
+    the prior of the shared components is the Nystrom form ``k0_r(x*, z) K0zz^-1 k0_s(z, x*)``, so two different
+    components of ``covar_module0`` are correlated already a priori and a shared component's prior variance is not
+    ``k0_r(x*, x*)``; the components of ``covar_module1`` keep their own prior ``k1_r(x*, x*)``.  The test rows are
+    cut into chunks of whole subjects whose workspace stays under ``max_workspace_bytes`` (a chunk holds at least
+    one subject); each chunk repeats the pass over the prediction set, and the chunks do not change the bits.  With
+    the default nothing new runs and the result is today's bit for bit, ``comps.cov`` None."""
     lib = _lib.lib()
     (L, spec0, spec1, p0, p1, dev, z, M, Q, noise, seg_d, inc_d, T, P, pred_ids, x_pad, mu_pad, tx,
      Nt) = _inducing_inputs(latent_dim, covar_module0, covar_module1, likelihoods, prediction_x, test_x, mu, zt_list,
                             id_covariate)
     R0, R1 = int(spec0.n_comp), int(spec1.n_comp)
-    out = torch.empty(Nt, L, dtype=torch.float64, device=dev)
-    vals = torch.empty(R0 + R1, Nt, L, dtype=torch.float64, device=dev)
-    info = torch.empty(L, dtype=torch.int32, device=dev)
-    ws = torch.empty(int(lib.lvae_predict_comp_workspace_size(L, M, P, T, Nt, R0, R1)), dtype=torch.uint8, device=dev)
-    rc = lib.lvae_predict_comp_f64(spec0, spec1, L, M, Q, P, T, _lib.ptr(seg_d), _lib.ptr(inc_d), _lib.ptr(x_pad),
-                                   _lib.ptr(mu_pad), _lib.ptr(z), Nt, _lib.ptr(tx), _lib.ptr(p0), _lib.ptr(p1),
-                                   _lib.ptr(noise), float(eps), _lib.ptr(out), _lib.ptr(vals) if Nt else None, L,
-                                   Nt * L, _lib.ptr(info), _lib.ptr(ws), _lib.stream_ptr())
-    _lib.check(rc, "predict_comp")
-    _check_info(info, "batch_predict_varying_T cholesky (10000+col: K0zz, 20000+col: B_st, 30000+col: H)")
+    R = R0 + R1
     labels = component_labels(covar_module0) + component_labels(covar_module1)
-    return out, LatentComponents(vals, labels, [0] * R0 + [1] * R1)
+    what = "batch_predict_varying_T cholesky (10000+col: K0zz, 20000+col: B_st, 30000+col: H)"
+    out = torch.empty(Nt, L, dtype=torch.float64, device=dev)
+    vals = torch.empty(R, Nt, L, dtype=torch.float64, device=dev)
+    info = torch.empty(L, dtype=torch.int32, device=dev)
+    if not return_cov:
+        ws = torch.empty(int(lib.lvae_predict_comp_workspace_size(L, M, P, T, Nt, R0, R1)), dtype=torch.uint8,
+                         device=dev)
+        rc = lib.lvae_predict_comp_f64(spec0, spec1, L, M, Q, P, T, _lib.ptr(seg_d), _lib.ptr(inc_d), _lib.ptr(x_pad),
+                                       _lib.ptr(mu_pad), _lib.ptr(z), Nt, _lib.ptr(tx), _lib.ptr(p0), _lib.ptr(p1),
+                                       _lib.ptr(noise), float(eps), _lib.ptr(out), _lib.ptr(vals) if Nt else None, L,
+                                       Nt * L, _lib.ptr(info), _lib.ptr(ws), _lib.stream_ptr())
+        _lib.check(rc, "predict_comp")
+        _check_info(info, what)
+        return out, LatentComponents(vals, labels, [0] * R0 + [1] * R1)
+    # test rows grouped by subject (stable), each group with its subject's index in the prediction layout or -1, as
+    # batch_predict_varying_T(return_var=True); the grouping is undone on the way out
+    tid = test_x[:, id_covariate].detach().to("cpu", torch.float64)
+    order = torch.argsort(tid, stable=True)
+    ids, counts = torch.unique_consecutive(tid[order], return_counts=True)
+    where = torch.searchsorted(pred_ids, ids).clamp(max=P - 1)
+    subj = torch.where(pred_ids[where] == ids, where, torch.full_like(where, -1)).to(torch.int32)
+    start = torch.zeros(ids.numel() + 1, dtype=torch.int64)
+    start[1:] = torch.cumsum(counts, 0)
+    G = int(ids.numel())
+    order_d = order.to(dev)
+    txg = tx[order_d].contiguous()
+    outg, valsg = torch.empty_like(out), torch.empty_like(vals)
+    covg = torch.empty(L, Nt, R, R, dtype=torch.float64, device=dev)
+    size = lambda rows: int(lib.lvae_predict_comp_cov_workspace_size(L, M, P, T, rows, R0, R1))
+    cuts = [0]   # chunks of whole subject groups: groups cuts[k] .. cuts[k + 1] - 1
+    while cuts[-1] < G:
+        g1 = cuts[-1] + 1
+        while g1 < G and size(int(start[g1 + 1] - start[cuts[-1]])) <= max_workspace_bytes:
+            g1 += 1
+        cuts.append(g1)
+
+    def call(g0, g1, mean):
+        r0, r1 = int(start[g0]), int(start[g1])
+        nr = r1 - r0
+        gs = (start[g0:g1 + 1] - r0).to(torch.int32).to(dev)
+        sb = subj[g0:g1].to(dev)
+        cv = covg if nr == Nt else torch.empty(L, nr, R, R, dtype=torch.float64, device=dev)
+        ws = torch.empty(size(nr), dtype=torch.uint8, device=dev)
+        rc = lib.lvae_predict_comp_cov_f64(spec0, spec1, L, M, Q, P, T, _lib.ptr(seg_d), _lib.ptr(inc_d),
+                                           _lib.ptr(x_pad), _lib.ptr(mu_pad) if mean else None, _lib.ptr(z), nr,
+                                           ctypes.c_void_p(txg.data_ptr() + 8 * r0 * Q) if nr else None, g1 - g0,
+                                           _lib.ptr(sb), _lib.ptr(gs), _lib.ptr(p0), _lib.ptr(p1), _lib.ptr(noise),
+                                           float(eps), _lib.ptr(outg) if mean else None,
+                                           _lib.ptr(valsg) if mean and nr else None, L, nr * L,
+                                           _lib.ptr(cv) if nr else None, _lib.ptr(info), _lib.ptr(ws),
+                                           _lib.stream_ptr())
+        _lib.check(rc, "predict_comp_cov")
+        if nr != Nt:
+            covg[:, r0:r1] = cv
+
+    if len(cuts) <= 2:
+        call(0, G, True)   # one chunk (or no test rows): the means and the covariance in one pass
+    else:
+        # the means by lvae_predict_comp_f64 over all rows (a chunk's own would be the same bits row by row only
+        # where the component product cuts its columns the same way), then the chunks' covariances alone
+        ws = torch.empty(int(lib.lvae_predict_comp_workspace_size(L, M, P, T, Nt, R0, R1)), dtype=torch.uint8,
+                         device=dev)
+        rc = lib.lvae_predict_comp_f64(spec0, spec1, L, M, Q, P, T, _lib.ptr(seg_d), _lib.ptr(inc_d), _lib.ptr(x_pad),
+                                       _lib.ptr(mu_pad), _lib.ptr(z), Nt, _lib.ptr(txg), _lib.ptr(p0), _lib.ptr(p1),
+                                       _lib.ptr(noise), float(eps), _lib.ptr(outg), _lib.ptr(valsg), L, Nt * L,
+                                       _lib.ptr(info), _lib.ptr(ws), _lib.stream_ptr())
+        _lib.check(rc, "predict_comp")
+        for g0, g1 in zip(cuts[:-1], cuts[1:]):
+            call(g0, g1, False)
+    _check_info(info, what)
+    out[order_d] = outg
+    vals[:, order_d] = valsg
+    cov = torch.empty_like(covg)
+    cov[:, order_d] = covg
+    return out, LatentComponents(vals, labels, [0] * R0 + [1] * R1, cov)
 
 
 def sample_predictions(mean, var, eps=None, generator=None):
