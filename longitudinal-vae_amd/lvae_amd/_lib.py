@@ -86,6 +86,19 @@ _DIMS = ctypes.POINTER(HensmanDims)
 _DDIMS = ctypes.POINTER(DuboDims)
 _GDIMS = ctypes.POINTER(GpElboDims)
 
+# the argument runs the latent predictors' entry points are made of (include/lvae_hip.h): the exact route's head
+# (spec, x, ldx, n, L, params, noise, mu, ld_mu, tx, ldt, nt) and its mean (out, ld_out); the inducing route's head
+# (spec0, spec1, L, M, Q, P, T, seg_len, include, x, mu, z, Nt, test_x) and (params0, params1, noise, eps); the test
+# rows' subject groups (n_groups, group_subject, group_start); the split by component (out_comp, ld_comp, cstride_r);
+# every entry's end (info, workspace, stream)
+_P_EX = [_SPEC, _VP, _I64, _I32, _I32, _VP, _VP, _VP, _I64, _VP, _I64, _I32]
+_P_OUT = [_VP, _I64]
+_P_IND = [_SPEC, _SPEC] + [_I32] * 5 + [_VP] * 5 + [_I32, _VP]
+_P_PAR = [_VP, _VP, _VP, _D]
+_P_GRP = [_I32, _VP, _VP]
+_P_COMP = [_VP, _I64, _I64]
+_P_END = [_VP, _VP, _VP]
+
 # name -> (restype, argtypes); every symbol include/lvae_hip.h declares
 SIGNATURES = {
     "lvae_gram_f64": (_I32, [_SPEC, XView, XView, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _I64, _I64, _I64, _VP]),
@@ -201,48 +214,36 @@ SIGNATURES = {
     "lvae_potrs_f64": (_I32, [_I32, _I32, _I32, _VP, _I64, _I64, _VP, _I64, _I64, _VP, _VP]),
     "lvae_potrs_f32": (_I32, [_I32, _I32, _I32, _VP, _I64, _I64, _VP, _I64, _I64, _VP, _VP]),
     "lvae_predict_workspace_size": (_SZ, [_I32, _I32, _I32, _I32, _I32]),
-    "lvae_predict_f64": (_I32, [_SPEC, _SPEC, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP,
-                                _VP, _VP, _D, _VP, _VP, _VP, _VP]),
+    "lvae_predict_f64": (_I32, _P_IND + _P_PAR + [_VP] + _P_END),
     "lvae_gram_matvec_workspace_size": (_SZ, [_I32, _I32, _I32]),
     "lvae_gram_matvec_f64": (_I32, [_SPEC, _VP, _I64, _I32, _VP, _I64, _I32, _I32, _VP, _VP, _VP, _I64, _VP, _I64,
                                     _VP, _VP]),
     "lvae_predict_exact_workspace_size": (_SZ, [_I32, _I32, _I32]),
-    "lvae_predict_exact_f64": (_I32, [_SPEC, _VP, _I64, _I32, _I32, _VP, _VP, _VP, _I64, _VP, _I64, _I32, _VP, _I64,
-                                      _VP, _VP, _VP]),
+    "lvae_predict_exact_f64": (_I32, _P_EX + _P_OUT + _P_END),
     "lvae_gram_matvec_comp_workspace_size": (_SZ, [_I32, _I32, _I32, _I32]),
     "lvae_gram_matvec_comp_f64": (_I32, [_SPEC, _VP, _I64, _I32, _VP, _I64, _I64, _I32, _I32, _VP, _VP, _I64, _VP,
                                          _I64, _I64, _VP, _VP]),
     "lvae_predict_exact_comp_workspace_size": (_SZ, [_I32, _I32, _I32, _I32]),
-    "lvae_predict_exact_comp_f64": (_I32, [_SPEC, _VP, _I64, _I32, _I32, _VP, _VP, _VP, _I64, _VP, _I64, _I32, _VP,
-                                           _I64, _VP, _I64, _I64, _VP, _VP, _VP]),
+    "lvae_predict_exact_comp_f64": (_I32, _P_EX + _P_OUT + _P_COMP + _P_END),
     "lvae_predict_comp_workspace_size": (_SZ, [_I32, _I32, _I32, _I32, _I32, _I32, _I32]),
-    "lvae_predict_comp_f64": (_I32, [_SPEC, _SPEC, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _I32, _VP,
-                                     _VP, _VP, _VP, _D, _VP, _VP, _I64, _I64, _VP, _VP, _VP]),
-    # the components' joint covariance per test row: lvae_predict_exact_comp_f64's arguments with (chunk, out_ccov)
-    # after cstride_r; lvae_predict_comp_f64's with (n_groups, group_subject, group_start) after test_x and out_ccov
-    # after cstride_r
+    "lvae_predict_comp_f64": (_I32, _P_IND + _P_PAR + [_VP] + _P_COMP + _P_END),
+    # the components' joint covariance per test row: + (chunk, out_ccov) / + out_ccov
     "lvae_predict_exact_comp_cov_workspace_size": (_SZ, [_I32, _I32, _I32, _I32, _I32]),
-    "lvae_predict_exact_comp_cov_f64": (_I32, [_SPEC, _VP, _I64, _I32, _I32, _VP, _VP, _VP, _I64, _VP, _I64, _I32,
-                                               _VP, _I64, _VP, _I64, _I64, _I32, _VP, _VP, _VP, _VP]),
+    "lvae_predict_exact_comp_cov_f64": (_I32, _P_EX + _P_OUT + _P_COMP + [_I32, _VP] + _P_END),
     "lvae_predict_comp_cov_workspace_size": (_SZ, [_I32, _I32, _I32, _I32, _I32, _I32, _I32]),
-    "lvae_predict_comp_cov_f64": (_I32, [_SPEC, _SPEC, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _I32,
-                                         _VP, _I32, _VP, _VP, _VP, _VP, _VP, _D, _VP, _VP, _I64, _I64, _VP, _VP, _VP,
-                                         _VP]),
+    "lvae_predict_comp_cov_f64": (_I32, _P_IND + _P_GRP + _P_PAR + [_VP] + _P_COMP + [_VP] + _P_END),
+    # the variance: + (out_var, ld_var, add_noise, chunk) / + (out_var, add_noise)
     "lvae_predict_exact_var_workspace_size": (_SZ, [_I32, _I32, _I32, _I32]),
-    "lvae_predict_exact_var_f64": (_I32, [_SPEC, _VP, _I64, _I32, _I32, _VP, _VP, _VP, _I64, _VP, _I64, _I32, _VP,
-                                          _I64, _VP, _I64, _I32, _I32, _VP, _VP, _VP]),
+    "lvae_predict_exact_var_f64": (_I32, _P_EX + _P_OUT + [_VP, _I64, _I32, _I32] + _P_END),
     "lvae_predict_var_workspace_size": (_SZ, [_I32, _I32, _I32, _I32, _I32]),
-    "lvae_predict_var_f64": (_I32, [_SPEC, _SPEC, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _I32, _VP,
-                                    _I32, _VP, _VP, _VP, _VP, _VP, _D, _VP, _VP, _I32, _VP, _VP, _VP]),
-    # the groups' joint covariance: lvae_predict_var_f64's arguments with n_max after group_start and out_cov for
-    # out_var; lvae_predict_exact_var_f64's with (n_groups, host group_start, n_max) after nt and out_cov for
-    # (out_var, ld_var); the draws (L, G, n_max, Nt, S, cov, index, mean, eps, jitter, out, info, workspace, stream)
+    "lvae_predict_var_f64": (_I32, _P_IND + _P_GRP + _P_PAR + [_VP, _VP, _I32] + _P_END),
+    # the groups' joint covariance: n_max after the groups, + (out_cov, add_noise) / (n_groups, host group_start,
+    # n_max) after nt, + (out_cov, add_noise, chunk); the draws (L, G, n_max, Nt, S, cov, index, mean, eps, jitter,
+    # out, info, workspace, stream)
     "lvae_predict_cov_workspace_size": (_SZ, [_I32, _I32, _I32, _I32, _I32]),
-    "lvae_predict_cov_f64": (_I32, [_SPEC, _SPEC, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _I32, _VP,
-                                    _I32, _VP, _VP, _I32, _VP, _VP, _VP, _D, _VP, _VP, _I32, _VP, _VP, _VP]),
+    "lvae_predict_cov_f64": (_I32, _P_IND + _P_GRP + [_I32] + _P_PAR + [_VP, _VP, _I32] + _P_END),
     "lvae_predict_exact_cov_workspace_size": (_SZ, [_I32, _I32, _I32, _I32]),
-    "lvae_predict_exact_cov_f64": (_I32, [_SPEC, _VP, _I64, _I32, _I32, _VP, _VP, _VP, _I64, _VP, _I64, _I32, _I32,
-                                          _VP, _I32, _VP, _I64, _VP, _I32, _I32, _VP, _VP, _VP]),
+    "lvae_predict_exact_cov_f64": (_I32, _P_EX + [_I32, _VP, _I32] + _P_OUT + [_VP, _I32, _I32] + _P_END),
     "lvae_predict_sample_workspace_size": (_SZ, [_I32, _I32, _I32]),
     "lvae_predict_sample_f64": (_I32, [_I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _D, _VP, _VP, _VP, _VP]),
     "lvae_prof_enable": (_I32, [_I32]),

@@ -18,6 +18,7 @@ test row (lvae_predict_exact_comp_cov_f64, lvae_predict_comp_cov_f64): per-effec
 uncertainty of the reconstruction after the first k effects.
 """
 import ctypes
+from types import SimpleNamespace
 
 import torch
 
@@ -25,6 +26,9 @@ from . import _lib
 from .elbo import _check_info, _noise_vector, _stack_modules, _subject_layout
 
 MAX_GROUP_ROWS = 128   # the largest group of test rows a joint covariance is formed for (kPvT)
+# what _check_info names when a factorisation of a route fails
+_INDUCING_INFO = "batch_predict_varying_T cholesky (10000+col: K0zz, 20000+col: B_st, 30000+col: H)"
+_EXACT_INFO = "predict_exact cholesky of k(X, X) + noise I"
 
 
 class PredictiveCovariance:
@@ -59,21 +63,31 @@ class PredictiveCovariance:
         return self.blocks[:, g, :n, :n]
 
 
-def _row_groups(labels, what):
+def _row_groups(labels, what, max_rows=MAX_GROUP_ROWS):
     """Test rows grouped by label, stable (a group's rows keep their order of appearance): (order [Nt], the
-    groups' labels [G], counts [G], start [G + 1] int32, n_max), all on the CPU; a group above MAX_GROUP_ROWS
-    raises ValueError"""
+    groups' labels [G], counts [G], start [G + 1] int32, n_max), all on the CPU; a group above ``max_rows``
+    (MAX_GROUP_ROWS where a joint covariance of the group is formed, None where none is) raises ValueError"""
     lab = labels.detach().to("cpu", torch.float64).reshape(-1)
     order = torch.argsort(lab, stable=True)
     ids, counts = torch.unique_consecutive(lab[order], return_counts=True)
     start = torch.zeros(ids.numel() + 1, dtype=torch.int32)
     start[1:] = torch.cumsum(counts, 0)
     n_max = int(counts.max()) if counts.numel() else 1
-    if n_max > MAX_GROUP_ROWS:
+    if max_rows is not None and n_max > max_rows:
         g = int(counts.argmax())
         raise ValueError(f"{what}: group {g} (label {float(ids[g]):g}) has {n_max} test rows; a joint covariance "
-                         f"is formed for groups of at most {MAX_GROUP_ROWS}")
+                         f"is formed for groups of at most {max_rows}")
     return order, ids, counts, start, n_max
+
+
+def _subject_groups(labels, pred_ids, what, max_rows):
+    """_row_groups of the test rows' subject labels as a namespace (order, ids, counts, start, n_max, G) with
+    ``subj`` [G] int32: each group's subject index in the sorted prediction-set ids ``pred_ids``, -1 where the
+    subject is not in the prediction set.  The caller undoes the grouping on the way out."""
+    order, ids, counts, start, n_max = _row_groups(labels, what, max_rows)
+    where = torch.searchsorted(pred_ids, ids).clamp(max=pred_ids.numel() - 1)
+    subj = torch.where(pred_ids[where] == ids, where, torch.full_like(where, -1)).to(torch.int32)
+    return SimpleNamespace(order=order, ids=ids, counts=counts, start=start, n_max=n_max, G=int(ids.numel()), subj=subj)
 
 
 def _group_index(order, counts, start, n_max, dev):
@@ -86,8 +100,21 @@ def _group_index(order, counts, start, n_max, dev):
     return index.to(dev)
 
 
+class _InducingInputs(SimpleNamespace):
+    """_inducing_inputs' result; ``head`` and ``params`` are the argument runs every entry of the route shares"""
+
+    def head(self, tx, nt, mean=True):
+        """(spec0 .. test_x): the leading arguments for ``nt`` test rows at the pointer ``tx``"""
+        return (self.spec0, self.spec1, self.L, self.M, self.Q, self.P, self.T, _lib.ptr(self.seg), _lib.ptr(self.inc),
+                _lib.ptr(self.x_pad), _lib.ptr(self.mu_pad) if mean else None, _lib.ptr(self.z), nt, tx)
+
+    def params(self):
+        """(params0, params1, noise, eps)"""
+        return _lib.ptr(self.p0), _lib.ptr(self.p1), _lib.ptr(self.noise), self.eps
+
+
 def _inducing_inputs(latent_dim, covar_module0, covar_module1, likelihoods, prediction_x, test_x, mu, zt_list,
-                     id_covariate):
+                     id_covariate, eps):
     """The arguments of batch_predict_varying_T as lvae_predict_f64 and its siblings take them: the modules in eval
     mode, everything fp64 on mu's device, the prediction set gathered into the padded [P, T] subject layout"""
     L = int(latent_dim)
@@ -120,8 +147,9 @@ def _inducing_inputs(latent_dim, covar_module0, covar_module1, likelihoods, pred
     x_pad = f64(prediction_x)[g].contiguous()
     mu_pad = (f64(mu)[g] * valid.to(dev, torch.float64).unsqueeze(1)).contiguous()
     tx = f64(test_x)
-    return (L, spec0, spec1, f64(params0), f64(params1), dev, z, M, Q, noise, seg.to(dev), include.to(dev), T, P,
-            pred_ids, x_pad, mu_pad, tx, int(tx.shape[0]))
+    return _InducingInputs(L=L, spec0=spec0, spec1=spec1, p0=f64(params0), p1=f64(params1), dev=dev, z=z, M=M, Q=Q,
+                           noise=noise, seg=seg.to(dev), inc=include.to(dev), T=T, P=P, pred_ids=pred_ids, x_pad=x_pad,
+                           mu_pad=mu_pad, tx=tx, Nt=int(tx.shape[0]), eps=float(eps))
 
 
 def batch_predict_varying_T(latent_dim, covar_module0, covar_module1, likelihoods, prediction_x, test_x, mu,
@@ -145,66 +173,47 @@ def batch_predict_varying_T(latent_dim, covar_module0, covar_module1, likelihood
     if return_var and return_cov:
         raise ValueError("return_var and return_cov are exclusive: cov.diagonal() holds the variances")
     lib = _lib.lib()
-    (L, spec0, spec1, p0, p1, dev, z, M, Q, noise, seg_d, inc_d, T, P, pred_ids, x_pad, mu_pad, tx,
-     Nt) = _inducing_inputs(latent_dim, covar_module0, covar_module1, likelihoods, prediction_x, test_x, mu, zt_list,
-                            id_covariate)
+    a = _inducing_inputs(latent_dim, covar_module0, covar_module1, likelihoods, prediction_x, test_x, mu, zt_list,
+                         id_covariate, eps)
+    L, M, P, T, Nt, dev = a.L, a.M, a.P, a.T, a.Nt, a.dev
+    noisy = 1 if add_noise else 0
     out = torch.empty(Nt, L, dtype=torch.float64, device=dev)
     info = torch.empty(L, dtype=torch.int32, device=dev)
+    if not (return_var or return_cov):
+        ws = torch.empty(int(lib.lvae_predict_workspace_size(L, M, P, T, Nt)), dtype=torch.uint8, device=dev)
+        rc = lib.lvae_predict_f64(*a.head(_lib.ptr(a.tx), Nt), *a.params(), _lib.ptr(out), _lib.ptr(info),
+                                  _lib.ptr(ws), _lib.stream_ptr())
+        _lib.check(rc, "predict")
+        _check_info(info, _INDUCING_INFO)
+        return out
+    # test rows grouped by subject (stable: a subject's rows keep their order), each group with its subject's index
+    # in the prediction layout or -1; the grouping is undone on the way out.  Only the joint covariance caps a group.
+    g = _subject_groups(test_x[:, id_covariate], a.pred_ids, "batch_predict_varying_T",
+                        MAX_GROUP_ROWS if return_cov else None)
+    order_d = g.order.to(dev)
+    txg = a.tx[order_d].contiguous()
+    outg = torch.empty_like(out)
+    subj_d, start_d = g.subj.to(dev), g.start.to(dev)
+    groups = (g.G, _lib.ptr(subj_d), _lib.ptr(start_d))
     if return_cov:
-        order, ids, counts, start, n_max = _row_groups(test_x[:, id_covariate], "batch_predict_varying_T")
-        G = int(ids.numel())
-        where = torch.searchsorted(pred_ids, ids).clamp(max=P - 1)
-        subj = torch.where(pred_ids[where] == ids, where, torch.full_like(where, -1)).to(torch.int32)
-        order_d = order.to(dev)
-        txg = tx[order_d].contiguous()
-        outg = torch.empty_like(out)
-        blocks = torch.empty(L, G, n_max, n_max, dtype=torch.float64, device=dev)
-        subj_d, start_d = subj.to(dev), start.to(dev)
+        blocks = torch.empty(L, g.G, g.n_max, g.n_max, dtype=torch.float64, device=dev)
         ws = torch.empty(int(lib.lvae_predict_cov_workspace_size(L, M, P, T, Nt)), dtype=torch.uint8, device=dev)
-        rc = lib.lvae_predict_cov_f64(spec0, spec1, L, M, Q, P, T, _lib.ptr(seg_d), _lib.ptr(inc_d), _lib.ptr(x_pad),
-                                      _lib.ptr(mu_pad), _lib.ptr(z), Nt, _lib.ptr(txg), G, _lib.ptr(subj_d),
-                                      _lib.ptr(start_d), n_max, _lib.ptr(p0), _lib.ptr(p1), _lib.ptr(noise),
-                                      float(eps), _lib.ptr(outg), _lib.ptr(blocks), 1 if add_noise else 0,
-                                      _lib.ptr(info), _lib.ptr(ws), _lib.stream_ptr())
+        rc = lib.lvae_predict_cov_f64(*a.head(_lib.ptr(txg), Nt), *groups, g.n_max, *a.params(), _lib.ptr(outg),
+                                      _lib.ptr(blocks), noisy, _lib.ptr(info), _lib.ptr(ws), _lib.stream_ptr())
         _lib.check(rc, "predict_cov")
-        _check_info(info, "batch_predict_varying_T cholesky (10000+col: K0zz, 20000+col: B_st, 30000+col: H)")
+        _check_info(info, _INDUCING_INFO)
         out[order_d] = outg
-        return out, PredictiveCovariance(blocks, _group_index(order, counts, start, n_max, dev), counts)
-    if return_var:
-        # test rows grouped by subject (stable: a subject's rows keep their order), each group with its
-        # subject's index in the prediction layout or -1; the grouping is undone on the way out
-        tid = test_x[:, id_covariate].detach().to("cpu", torch.float64)
-        order = torch.argsort(tid, stable=True)
-        ids, counts = torch.unique_consecutive(tid[order], return_counts=True)
-        where = torch.searchsorted(pred_ids, ids).clamp(max=P - 1)
-        subj = torch.where(pred_ids[where] == ids, where, torch.full_like(where, -1)).to(torch.int32)
-        start = torch.zeros(ids.numel() + 1, dtype=torch.int32)
-        start[1:] = torch.cumsum(counts, 0)
-        order_d = order.to(dev)
-        txg = tx[order_d].contiguous()
-        outg = torch.empty_like(out)
-        var = torch.empty_like(out)
-        subj_d, start_d = subj.to(dev), start.to(dev)
-        ws = torch.empty(int(lib.lvae_predict_var_workspace_size(L, M, P, T, Nt)), dtype=torch.uint8, device=dev)
-        rc = lib.lvae_predict_var_f64(spec0, spec1, L, M, Q, P, T, _lib.ptr(seg_d), _lib.ptr(inc_d), _lib.ptr(x_pad),
-                                      _lib.ptr(mu_pad), _lib.ptr(z), Nt, _lib.ptr(txg), int(ids.numel()),
-                                      _lib.ptr(subj_d), _lib.ptr(start_d), _lib.ptr(p0), _lib.ptr(p1),
-                                      _lib.ptr(noise), float(eps), _lib.ptr(outg), _lib.ptr(var),
-                                      1 if add_noise else 0, _lib.ptr(info), _lib.ptr(ws), _lib.stream_ptr())
-        _lib.check(rc, "predict_var")
-        _check_info(info, "batch_predict_varying_T cholesky (10000+col: K0zz, 20000+col: B_st, 30000+col: H)")
-        out[order_d] = outg
-        z_var = torch.empty_like(var)
-        z_var[order_d] = var.clamp_(min=0.0)
-        return out, z_var
-    ws = torch.empty(int(lib.lvae_predict_workspace_size(L, M, P, T, Nt)), dtype=torch.uint8, device=dev)
-    rc = lib.lvae_predict_f64(spec0, spec1, L, M, Q, P, T, _lib.ptr(seg_d), _lib.ptr(inc_d), _lib.ptr(x_pad),
-                              _lib.ptr(mu_pad), _lib.ptr(z), Nt, _lib.ptr(tx), _lib.ptr(p0), _lib.ptr(p1),
-                              _lib.ptr(noise), float(eps), _lib.ptr(out), _lib.ptr(info), _lib.ptr(ws),
-                              _lib.stream_ptr())
-    _lib.check(rc, "predict")
-    _check_info(info, "batch_predict_varying_T cholesky (10000+col: K0zz, 20000+col: B_st, 30000+col: H)")
-    return out
+        return out, PredictiveCovariance(blocks, _group_index(g.order, g.counts, g.start, g.n_max, dev), g.counts)
+    var = torch.empty_like(out)
+    ws = torch.empty(int(lib.lvae_predict_var_workspace_size(L, M, P, T, Nt)), dtype=torch.uint8, device=dev)
+    rc = lib.lvae_predict_var_f64(*a.head(_lib.ptr(txg), Nt), *groups, *a.params(), _lib.ptr(outg), _lib.ptr(var),
+                                  noisy, _lib.ptr(info), _lib.ptr(ws), _lib.stream_ptr())
+    _lib.check(rc, "predict_var")
+    _check_info(info, _INDUCING_INFO)
+    out[order_d] = outg
+    z_var = torch.empty_like(var)
+    z_var[order_d] = var.clamp_(min=0.0)
+    return out, z_var
 
 
 def _exact_inputs(covar_module, likelihoods, prediction_x, test_x, prediction_mu):
@@ -227,7 +236,36 @@ def _exact_inputs(covar_module, likelihoods, prediction_x, test_x, prediction_mu
     n, nt, n_params = int(x.shape[0]), int(tx.shape[0]), int(p.shape[1])
     if n < 1 or mu.shape[0] != n:
         raise ValueError(f"prediction_mu rows {mu.shape[0]} != prediction_x rows {n} (>= 1)")
-    return spec, L, dev, x, tx, mu, p, noise, n, nt, n_params
+    return SimpleNamespace(spec=spec, L=L, dev=dev, x=x, tx=tx, mu=mu, p=p, noise=noise, n=n, nt=nt, n_params=n_params)
+
+
+def _exact_run(lib, a, tx, max_workspace_bytes, size, entry, what, extra, floor=None):
+    """The exact route's one driver: plan the dim groups and the test-row chunk under ``max_workspace_bytes``, then
+    call ``entry`` once per group of dims.  ``size(dims, chunk)`` is the entry's workspace query.  The dim group is
+    sized at the smallest chunk, ``floor`` rows (1 for the variance and the components' covariance, the largest
+    group of test rows for the joint covariance); the chunk then starts at all test rows and is halved down to
+    ``floor`` while the workspace is too large.  ``floor=None``: the entry takes no chunk.  ``extra(at, l0, chunk)``
+    gives the entry's arguments between nt and info for the dims from l0 on, ``at(t, off)`` being the pointer
+    ``off`` doubles into t (None without test rows); ``tx`` are the test rows in the order the entry takes them.
+    Neither choice changes the bits."""
+    L, nt = a.L, a.nt
+    group = L
+    while group > 1 and size(group, floor or 1) > max_workspace_bytes:
+        group -= 1
+    chunk = max(nt, 1) if floor else 1
+    while floor and chunk > floor and size(group, chunk) > max_workspace_bytes:
+        chunk = max((chunk + 1) // 2, floor)
+    info = torch.empty(L, dtype=torch.int32, device=a.dev)
+    ws = torch.empty(size(group, chunk), dtype=torch.uint8, device=a.dev)
+    ptr = lambda t, off: ctypes.c_void_p(t.data_ptr() + 8 * off)
+    at = lambda t, off: ptr(t, off) if nt else None
+    for l0 in range(0, L, group):
+        g = min(group, L - l0)
+        rc = entry(a.spec, _lib.ptr(a.x), a.x.stride(0), a.n, g, ptr(a.p, l0 * a.n_params), ptr(a.noise, l0),
+                   ptr(a.mu, l0), L, _lib.ptr(tx) if nt else None, tx.stride(0), nt, *extra(at, l0, chunk),
+                   ctypes.c_void_p(info.data_ptr() + 4 * l0), _lib.ptr(ws), _lib.stream_ptr())
+        _lib.check(rc, what)
+    _check_info(info, _EXACT_INFO)
 
 
 def predict_exact(covar_module, likelihoods, prediction_x, test_x, prediction_mu, max_workspace_bytes=4 << 30,
@@ -256,79 +294,37 @@ def predict_exact(covar_module, likelihoods, prediction_x, test_x, prediction_mu
     if return_var and return_cov:
         raise ValueError("return_var and return_cov are exclusive: cov.diagonal() holds the variances")
     lib = _lib.lib()
-    spec, L, dev, x, tx, mu, p, noise, n, nt, n_params = _exact_inputs(covar_module, likelihoods, prediction_x, test_x,
-                                                                       prediction_mu)
-    chunk = 1   # (the smallest panel decides the dim groups; the chunk then takes what is left)
+    a = _exact_inputs(covar_module, likelihoods, prediction_x, test_x, prediction_mu)
+    L, dev, n, nt = a.L, a.dev, a.n, a.nt
+    noisy = 1 if add_noise else 0
     if return_cov:
         labels = torch.zeros(nt) if groups is None else groups
         if labels.numel() != nt:
             raise ValueError(f"groups has {labels.numel()} labels for {nt} test rows")
         order, ids, counts, start, n_max = _row_groups(labels, "predict_exact")
         G = int(ids.numel())
-        txg = tx[order.to(dev)].contiguous()
-        size = lambda g, c: int(lib.lvae_predict_exact_cov_workspace_size(n, nt, g, c))
-        group = L
-        while group > 1 and size(group, n_max) > max_workspace_bytes:
-            group -= 1
-        chunk = max(nt, 1)
-        while chunk > n_max and size(group, chunk) > max_workspace_bytes:
-            chunk = max((chunk + 1) // 2, n_max)
+        txg = a.tx[order.to(dev)].contiguous()
         outg = torch.empty(nt, L, dtype=torch.float64, device=dev)
         blocks = torch.empty(L, G, n_max, n_max, dtype=torch.float64, device=dev)
-        info = torch.empty(L, dtype=torch.int32, device=dev)
-        ws = torch.empty(size(group, chunk), dtype=torch.uint8, device=dev)
         start_h = (ctypes.c_int32 * (G + 1))(*start.tolist())   # host memory: the chunks are cut on the host
-        at = lambda t, off: ctypes.c_void_p(t.data_ptr() + 8 * off)
-        for l0 in range(0, L, group):
-            g = min(group, L - l0)
-            rc = lib.lvae_predict_exact_cov_f64(spec, _lib.ptr(x), x.stride(0), n, g, at(p, l0 * n_params),
-                                                at(noise, l0), at(mu, l0), L, _lib.ptr(txg) if nt else None,
-                                                txg.stride(0), nt, G, ctypes.cast(start_h, ctypes.c_void_p), n_max,
-                                                at(outg, l0) if nt else None, L,
-                                                at(blocks, l0 * G * n_max * n_max) if nt else None,
-                                                1 if add_noise else 0, chunk,
-                                                ctypes.c_void_p(info.data_ptr() + 4 * l0), _lib.ptr(ws),
-                                                _lib.stream_ptr())
-            _lib.check(rc, "predict_exact_cov")
-        _check_info(info, "predict_exact cholesky of k(X, X) + noise I")
+        _exact_run(lib, a, txg, max_workspace_bytes,
+                   lambda g, c: int(lib.lvae_predict_exact_cov_workspace_size(n, nt, g, c)),
+                   lib.lvae_predict_exact_cov_f64, "predict_exact_cov",
+                   lambda at, l0, c: (G, ctypes.cast(start_h, ctypes.c_void_p), n_max, at(outg, l0), L,
+                                      at(blocks, l0 * G * n_max * n_max), noisy, c), floor=n_max)
         out = torch.empty_like(outg)
         out[order.to(dev)] = outg
         return out, PredictiveCovariance(blocks, _group_index(order, counts, start, n_max, dev), counts)
-    if return_var:
-        size = lambda g: int(lib.lvae_predict_exact_var_workspace_size(n, nt, g, chunk))
-    else:
-        size = lambda g: int(lib.lvae_predict_exact_workspace_size(n, nt, g))
-    group = L
-    while group > 1 and size(group) > max_workspace_bytes:
-        group -= 1
-    if return_var and nt:
-        chunk = nt
-        while chunk > 1 and size(group) > max_workspace_bytes:
-            chunk = (chunk + 1) // 2
     out = torch.empty(nt, L, dtype=torch.float64, device=dev)
-    var = torch.empty(nt, L, dtype=torch.float64, device=dev) if return_var else None
-    info = torch.empty(L, dtype=torch.int32, device=dev)
-    ws = torch.empty(size(group), dtype=torch.uint8, device=dev)
-    at = lambda t, off: ctypes.c_void_p(t.data_ptr() + 8 * off)
-    for l0 in range(0, L, group):
-        g = min(group, L - l0)
-        if return_var:
-            rc = lib.lvae_predict_exact_var_f64(spec, _lib.ptr(x), x.stride(0), n, g, at(p, l0 * n_params),
-                                                at(noise, l0), at(mu, l0), L, _lib.ptr(tx) if nt else None,
-                                                tx.stride(0), nt, at(out, l0) if nt else None, L,
-                                                at(var, l0) if nt else None, L, 1 if add_noise else 0, chunk,
-                                                ctypes.c_void_p(info.data_ptr() + 4 * l0), _lib.ptr(ws),
-                                                _lib.stream_ptr())
-            _lib.check(rc, "predict_exact_var")
-            continue
-        rc = lib.lvae_predict_exact_f64(spec, _lib.ptr(x), x.stride(0), n, g, at(p, l0 * n_params), at(noise, l0),
-                                        at(mu, l0), L, _lib.ptr(tx) if nt else None, tx.stride(0), nt,
-                                        at(out, l0) if nt else None, L,
-                                        ctypes.c_void_p(info.data_ptr() + 4 * l0), _lib.ptr(ws), _lib.stream_ptr())
-        _lib.check(rc, "predict_exact")
-    _check_info(info, "predict_exact cholesky of k(X, X) + noise I")
     if return_var:
+        var = torch.empty(nt, L, dtype=torch.float64, device=dev)
+        _exact_run(lib, a, a.tx, max_workspace_bytes,
+                   lambda g, c: int(lib.lvae_predict_exact_var_workspace_size(n, nt, g, c)),
+                   lib.lvae_predict_exact_var_f64, "predict_exact_var",
+                   lambda at, l0, c: (at(out, l0), L, at(var, l0), L, noisy, c), floor=1)
         return out, var.clamp_(min=0.0)
+    _exact_run(lib, a, a.tx, max_workspace_bytes, lambda g, c: int(lib.lvae_predict_exact_workspace_size(n, nt, g)),
+               lib.lvae_predict_exact_f64, "predict_exact", lambda at, l0, c: (at(out, l0), L))
     return out
 
 
@@ -429,47 +425,21 @@ def predict_exact_components(covar_module, likelihoods, prediction_x, test_x, pr
     under ``max_workspace_bytes``; neither choice changes the bits.  With the default nothing new runs and the
     result is today's bit for bit, ``comps.cov`` None."""
     lib = _lib.lib()
-    spec, L, dev, x, tx, mu, p, noise, n, nt, n_params = _exact_inputs(covar_module, likelihoods, prediction_x, test_x,
-                                                                       prediction_mu)
-    R = int(spec.n_comp)
-    chunk = 1   # (the smallest panel decides the dim groups; the chunk then takes what is left)
-    if return_cov:
-        size = lambda g: int(lib.lvae_predict_exact_comp_cov_workspace_size(n, nt, g, R, chunk))
-    else:
-        size = lambda g: int(lib.lvae_predict_exact_comp_workspace_size(n, nt, g, R))
-    group = L
-    while group > 1 and size(group) > max_workspace_bytes:
-        group -= 1
-    if return_cov and nt:
-        chunk = nt
-        while chunk > 1 and size(group) > max_workspace_bytes:
-            chunk = (chunk + 1) // 2
+    a = _exact_inputs(covar_module, likelihoods, prediction_x, test_x, prediction_mu)
+    L, dev, n, nt, R = a.L, a.dev, a.n, a.nt, int(a.spec.n_comp)
     out = torch.empty(nt, L, dtype=torch.float64, device=dev)
     vals = torch.empty(R, nt, L, dtype=torch.float64, device=dev)
     cov = torch.empty(L, nt, R, R, dtype=torch.float64, device=dev) if return_cov else None
-    info = torch.empty(L, dtype=torch.int32, device=dev)
-    ws = torch.empty(size(group), dtype=torch.uint8, device=dev)
-    at = lambda t, off: ctypes.c_void_p(t.data_ptr() + 8 * off)
-    for l0 in range(0, L, group):
-        g = min(group, L - l0)
-        if return_cov:
-            rc = lib.lvae_predict_exact_comp_cov_f64(spec, _lib.ptr(x), x.stride(0), n, g, at(p, l0 * n_params),
-                                                     at(noise, l0), at(mu, l0), L, _lib.ptr(tx) if nt else None,
-                                                     tx.stride(0), nt, at(out, l0) if nt else None, L,
-                                                     at(vals, l0) if nt else None, L, nt * L, chunk,
-                                                     at(cov, l0 * nt * R * R) if nt else None,
-                                                     ctypes.c_void_p(info.data_ptr() + 4 * l0), _lib.ptr(ws),
-                                                     _lib.stream_ptr())
-            _lib.check(rc, "predict_exact_comp_cov")
-            continue
-        rc = lib.lvae_predict_exact_comp_f64(spec, _lib.ptr(x), x.stride(0), n, g, at(p, l0 * n_params),
-                                             at(noise, l0), at(mu, l0), L, _lib.ptr(tx) if nt else None,
-                                             tx.stride(0), nt, at(out, l0) if nt else None, L,
-                                             at(vals, l0) if nt else None, L, nt * L,
-                                             ctypes.c_void_p(info.data_ptr() + 4 * l0), _lib.ptr(ws),
-                                             _lib.stream_ptr())
-        _lib.check(rc, "predict_exact_comp")
-    _check_info(info, "predict_exact cholesky of k(X, X) + noise I")
+    split = lambda at, l0: (at(out, l0), L, at(vals, l0), L, nt * L)
+    if return_cov:
+        _exact_run(lib, a, a.tx, max_workspace_bytes,
+                   lambda g, c: int(lib.lvae_predict_exact_comp_cov_workspace_size(n, nt, g, R, c)),
+                   lib.lvae_predict_exact_comp_cov_f64, "predict_exact_comp_cov",
+                   lambda at, l0, c: split(at, l0) + (c, at(cov, l0 * nt * R * R)), floor=1)
+    else:
+        _exact_run(lib, a, a.tx, max_workspace_bytes,
+                   lambda g, c: int(lib.lvae_predict_exact_comp_workspace_size(n, nt, g, R)),
+                   lib.lvae_predict_exact_comp_f64, "predict_exact_comp", lambda at, l0, c: split(at, l0))
     return out, LatentComponents(vals, component_labels(covar_module), [0] * R, cov)
 
 
@@ -490,38 +460,35 @@ def batch_predict_components(latent_dim, covar_module0, covar_module1, likelihoo
     one subject); each chunk repeats the pass over the prediction set, and the chunks do not change the bits.  With
     the default nothing new runs and the result is today's bit for bit, ``comps.cov`` None."""
     lib = _lib.lib()
-    (L, spec0, spec1, p0, p1, dev, z, M, Q, noise, seg_d, inc_d, T, P, pred_ids, x_pad, mu_pad, tx,
-     Nt) = _inducing_inputs(latent_dim, covar_module0, covar_module1, likelihoods, prediction_x, test_x, mu, zt_list,
-                            id_covariate)
-    R0, R1 = int(spec0.n_comp), int(spec1.n_comp)
+    a = _inducing_inputs(latent_dim, covar_module0, covar_module1, likelihoods, prediction_x, test_x, mu, zt_list,
+                         id_covariate, eps)
+    L, M, Q, P, T, Nt, dev = a.L, a.M, a.Q, a.P, a.T, a.Nt, a.dev
+    R0, R1 = int(a.spec0.n_comp), int(a.spec1.n_comp)
     R = R0 + R1
     labels = component_labels(covar_module0) + component_labels(covar_module1)
-    what = "batch_predict_varying_T cholesky (10000+col: K0zz, 20000+col: B_st, 30000+col: H)"
     out = torch.empty(Nt, L, dtype=torch.float64, device=dev)
     vals = torch.empty(R, Nt, L, dtype=torch.float64, device=dev)
     info = torch.empty(L, dtype=torch.int32, device=dev)
-    if not return_cov:
+
+    def means(tx_, out_, vals_):
+        """lvae_predict_comp_f64 over all test rows ``tx_``"""
         ws = torch.empty(int(lib.lvae_predict_comp_workspace_size(L, M, P, T, Nt, R0, R1)), dtype=torch.uint8,
                          device=dev)
-        rc = lib.lvae_predict_comp_f64(spec0, spec1, L, M, Q, P, T, _lib.ptr(seg_d), _lib.ptr(inc_d), _lib.ptr(x_pad),
-                                       _lib.ptr(mu_pad), _lib.ptr(z), Nt, _lib.ptr(tx), _lib.ptr(p0), _lib.ptr(p1),
-                                       _lib.ptr(noise), float(eps), _lib.ptr(out), _lib.ptr(vals) if Nt else None, L,
-                                       Nt * L, _lib.ptr(info), _lib.ptr(ws), _lib.stream_ptr())
+        rc = lib.lvae_predict_comp_f64(*a.head(_lib.ptr(tx_), Nt), *a.params(), _lib.ptr(out_),
+                                       _lib.ptr(vals_) if Nt else None, L, Nt * L, _lib.ptr(info), _lib.ptr(ws),
+                                       _lib.stream_ptr())
         _lib.check(rc, "predict_comp")
-        _check_info(info, what)
+
+    if not return_cov:
+        means(a.tx, out, vals)
+        _check_info(info, _INDUCING_INFO)
         return out, LatentComponents(vals, labels, [0] * R0 + [1] * R1)
-    # test rows grouped by subject (stable), each group with its subject's index in the prediction layout or -1, as
-    # batch_predict_varying_T(return_var=True); the grouping is undone on the way out
-    tid = test_x[:, id_covariate].detach().to("cpu", torch.float64)
-    order = torch.argsort(tid, stable=True)
-    ids, counts = torch.unique_consecutive(tid[order], return_counts=True)
-    where = torch.searchsorted(pred_ids, ids).clamp(max=P - 1)
-    subj = torch.where(pred_ids[where] == ids, where, torch.full_like(where, -1)).to(torch.int32)
-    start = torch.zeros(ids.numel() + 1, dtype=torch.int64)
-    start[1:] = torch.cumsum(counts, 0)
-    G = int(ids.numel())
-    order_d = order.to(dev)
-    txg = tx[order_d].contiguous()
+    # test rows grouped by subject as batch_predict_varying_T(return_var=True) groups them (no cap on a group: no
+    # joint covariance over a group's rows is formed)
+    g = _subject_groups(test_x[:, id_covariate], a.pred_ids, "batch_predict_components", None)
+    G, start = g.G, g.start
+    order_d = g.order.to(dev)
+    txg = a.tx[order_d].contiguous()
     outg, valsg = torch.empty_like(out), torch.empty_like(vals)
     covg = torch.empty(L, Nt, R, R, dtype=torch.float64, device=dev)
     size = lambda rows: int(lib.lvae_predict_comp_cov_workspace_size(L, M, P, T, rows, R0, R1))
@@ -535,15 +502,13 @@ def batch_predict_components(latent_dim, covar_module0, covar_module1, likelihoo
     def call(g0, g1, mean):
         r0, r1 = int(start[g0]), int(start[g1])
         nr = r1 - r0
-        gs = (start[g0:g1 + 1] - r0).to(torch.int32).to(dev)
-        sb = subj[g0:g1].to(dev)
+        gs = (start[g0:g1 + 1] - r0).to(dev)
+        sb = g.subj[g0:g1].to(dev)
         cv = covg if nr == Nt else torch.empty(L, nr, R, R, dtype=torch.float64, device=dev)
         ws = torch.empty(size(nr), dtype=torch.uint8, device=dev)
-        rc = lib.lvae_predict_comp_cov_f64(spec0, spec1, L, M, Q, P, T, _lib.ptr(seg_d), _lib.ptr(inc_d),
-                                           _lib.ptr(x_pad), _lib.ptr(mu_pad) if mean else None, _lib.ptr(z), nr,
-                                           ctypes.c_void_p(txg.data_ptr() + 8 * r0 * Q) if nr else None, g1 - g0,
-                                           _lib.ptr(sb), _lib.ptr(gs), _lib.ptr(p0), _lib.ptr(p1), _lib.ptr(noise),
-                                           float(eps), _lib.ptr(outg) if mean else None,
+        rc = lib.lvae_predict_comp_cov_f64(*a.head(ctypes.c_void_p(txg.data_ptr() + 8 * r0 * Q) if nr else None, nr,
+                                                   mean), g1 - g0, _lib.ptr(sb), _lib.ptr(gs), *a.params(),
+                                           _lib.ptr(outg) if mean else None,
                                            _lib.ptr(valsg) if mean and nr else None, L, nr * L,
                                            _lib.ptr(cv) if nr else None, _lib.ptr(info), _lib.ptr(ws),
                                            _lib.stream_ptr())
@@ -556,16 +521,10 @@ def batch_predict_components(latent_dim, covar_module0, covar_module1, likelihoo
     else:
         # the means by lvae_predict_comp_f64 over all rows (a chunk's own would be the same bits row by row only
         # where the component product cuts its columns the same way), then the chunks' covariances alone
-        ws = torch.empty(int(lib.lvae_predict_comp_workspace_size(L, M, P, T, Nt, R0, R1)), dtype=torch.uint8,
-                         device=dev)
-        rc = lib.lvae_predict_comp_f64(spec0, spec1, L, M, Q, P, T, _lib.ptr(seg_d), _lib.ptr(inc_d), _lib.ptr(x_pad),
-                                       _lib.ptr(mu_pad), _lib.ptr(z), Nt, _lib.ptr(txg), _lib.ptr(p0), _lib.ptr(p1),
-                                       _lib.ptr(noise), float(eps), _lib.ptr(outg), _lib.ptr(valsg), L, Nt * L,
-                                       _lib.ptr(info), _lib.ptr(ws), _lib.stream_ptr())
-        _lib.check(rc, "predict_comp")
+        means(txg, outg, valsg)
         for g0, g1 in zip(cuts[:-1], cuts[1:]):
             call(g0, g1, False)
-    _check_info(info, what)
+    _check_info(info, _INDUCING_INFO)
     out[order_d] = outg
     vals[:, order_d] = valsg
     cov = torch.empty_like(covg)
