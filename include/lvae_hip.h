@@ -592,6 +592,48 @@ int lvae_dubo_cond_prepare_f64(const lvae_kernel_spec* spec0, const lvae_kernel_
 int lvae_dubo_cond_eval_f64(int L, int Pn, int T, const void* state, const double* m, const double* logv,
                             const double* g, double* dubo, double* dm, double* dlogv, void* stream);
 
+/* The exact N x N prior KL (lvae_kl_closed_*, elbo_functions.py:8-34) conditioned on a frozen prior and frozen training
+ * latents, for inferring the latents of new rows under the loss a KL_closed-trained model was trained with: the joint
+ * KL of cat(new, train) as a function of the nn new rows' mean m and log-variance l alone.  Per latent dim, with t the
+ * n training rows (mu_t, v_t = exp(logv_t)) and K = k(., .) + noise I on the joint rows (the new rows carry the noise):
+ *   W = K_tt^-1 K_tn [n, nn],  S = K_nn - K_nt W,  A = S^-1,  a = diag(A),  abar = W^T mu_t,  r = A abar
+ *   c = 1/2 (abar^T A abar - nn + log|S| + tr(A W^T diag(v_t) W))
+ *   cond_l(m, l) = c + 1/2 (m^T A m - 2 r^T m + sum_i a_i e^{l_i} - sum_i l_i)
+ *                = KL_closed(joint rows, new rows = (m, l)) - KL_closed(training rows alone)
+ * -- values and gradients with respect to (m, l).  The state is lvae_dubo_cond_eval_f64's own, with Pn = nn, T = 1 and
+ * the mask all ones: size it with lvae_dubo_cond_state_size(L_state, nn, 1) and evaluate it with
+ * lvae_dubo_cond_eval_f64(L_state, nn, 1, ...).  All fp64, on lvae_predict_exact_f64's route (lvae_gram_f64,
+ * lvae_potrf_f64, lvae_trsm_f64 / lvae_potrs_f64); S and W^T diag(v_t) W come from a weighted tall-skinny SYRK on the
+ * fp64 matrix cores (kl_cond.hip: 64 x 64 output blocks, slabs of 512 panel rows staged through LDS, the slabs'
+ * partials added in slab order).
+ *
+ * lvae_kl_cond_workspace_size: bytes of the workspace for n training rows, nn new rows and L dims a call (about
+ *   8 L (n^2 + n nn + 2 nn^2) + the SYRK's partials); a multiple of 256; 0 for n < 0, nn < 1 or L < 1.  Needs no device.
+ *
+ * lvae_kl_cond_prepare_f64 READS x_train [n, ldx], x_new [nn, ldn], params [L, n_params], noise [L], and mu_train /
+ *   logv_train element (i, l) at [i*ld_mu + l] / [i*ld_lv + l], l < L: the L dims of this call, which fill the dims
+ *   l0 .. l0 + L - 1 of a state sized for L_state dims (a caller under a workspace cap processes the dims in groups,
+ *   passing each group's params, noise, mu_train, logv_train and info at its first dim; the bits of a dim do not depend
+ *   on its group).  n == 0 is legal (every row new: cond is the plain exact KL of the new rows); x_train, mu_train and
+ *   logv_train are then never read and may be NULL.  It WRITES c, r, a and A of those dims (A symmetric bit for bit),
+ *   the state's mask (all ones), info [L] and the workspace; no other dim of the state is touched.  info[l]: 0, or
+ *   col (LAPACK-style, the first failing column + 1) when K_tt of dim l is not positive definite, or 20000 + col when
+ *   S is not; such a dim's state is meaningless, the other dims are unaffected.
+ *   Returns 0, LVAE_ERR_LAUNCH, or before any launch (nothing is written), checked in this order: -1 (spec NULL or
+ *   outside the family of lvae_gram_matvec_f64); with n > 0: -2 (x_train NULL) -3 (ldx < 1 + the largest column the
+ *   spec reads); -4 (n < 0) -5 (x_new NULL) -6 (ldn, as ldx) -7 (nn < 1) -8 (L < 1 or L > 65535) -9 (params NULL)
+ *   -10 (noise NULL); with n > 0: -11 (mu_train NULL) -12 (ld_mu < L) -13 (logv_train NULL) -14 (ld_lv < L);
+ *   -15 (state NULL or not 256-byte aligned) -16 (L_state < 1, l0 < 0 or l0 + L > L_state) -17 (info NULL)
+ *   -18 (workspace NULL or not 256-byte aligned).
+ * Kernel launches only, on the caller's stream; nothing is allocated; no atomics and every sum in a fixed order: the
+ * same inputs give the same bits on every call.                                                            */
+size_t lvae_kl_cond_workspace_size(int n, int nn, int L);
+int lvae_kl_cond_prepare_f64(const lvae_kernel_spec* spec, const double* x_train, int64_t ldx, int n,
+                             const double* x_new, int64_t ldn, int nn, int L, const double* params,
+                             const double* noise, const double* mu_train, int64_t ld_mu, const double* logv_train,
+                             int64_t ld_lv, void* state, int L_state, int l0, int32_t* info, void* workspace,
+                             void* stream);
+
 /* Learnable inducing points: the gradient of the three inducing-point bounds with respect to z [L, M, Q] (the
  * reference gets it from autograd once LVAE.py:204-208, 269 / training.py:349 are uncommented).  Each bound's
  * backward leaves the cotangents of X = k0(x, z) [L, N, M] and of Kz = k0(z, z) + eps I [L, M, M] in its

@@ -16,6 +16,7 @@
 // both m^T y and the gradient, A is read once.
 // Subjects of varying length: the padding rows of iBK are zero and iB is the identity there, so U G^T vanishes on
 // the padding and the finish kernel zeroes iB's identity; eval skips the rows the state's mask marks as padding.
+#include "cond_state.hpp"
 #include "dubo_ws.hpp"
 
 namespace lvae {
@@ -23,22 +24,6 @@ namespace {
 
 constexpr int kCondRows = 256;     // rows of A per workgroup of the eval
 constexpr int kCondChunk = 2048;   // columns of A whose m is staged in LDS at a time (16 KiB)
-
-struct CondState {
-  double *c, *r, *a, *A;   // [L], [L,Nn], [L,Nn], [L,Nn,Nn]
-  int32_t* mask;           // [Nn]: 1 on the valid rows
-  size_t bytes;
-  CondState(char* base, int L, int Pn, int T) {
-    WsCarve w(base);
-    const size_t Nn = (size_t)Pn * T;
-    c = w.take(L);
-    r = w.take(L * Nn);
-    a = w.take(L * Nn);
-    A = w.take(L * Nn * Nn);
-    mask = (int32_t*)w.take((Nn + 1) / 2);
-    bytes = w.off;
-  }
-};
 
 // subject of the k-th free slot, clamped to [0, P): a bad free_idx gives wrong numbers, never an out-of-range access
 __device__ __forceinline__ int cond_subject(const int32_t* __restrict__ free_idx, int k, int P) {

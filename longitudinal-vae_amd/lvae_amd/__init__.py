@@ -32,5 +32,6 @@ from .data import HealthMNISTDataset, HealthMNISTDatasetConv, PhysionetDataset  
 from .gpapprox import (DuboCondition, condition_dubo, condition_dubo_varying_T, deviance_upper_bound,  # noqa: F401
                        deviance_upper_bound_batched, deviance_upper_bound_varying_T, elbo, elbo_batched,
                        elbo_varying_T, spd_inverse, subject_layout, validation_dubo)
+from .kl_cond import condition_kl_closed  # noqa: F401
 
 __version__ = "0.1.0"

@@ -175,6 +175,9 @@ SIGNATURES = {
     "lvae_dubo_cond_prepare_f64": (_I32, [_SPEC, _SPEC, _DDIMS, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                           _VP, _VP, _VP, _VP]),
     "lvae_dubo_cond_eval_f64": (_I32, [_I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "lvae_kl_cond_workspace_size": (_SZ, [_I32, _I32, _I32]),
+    "lvae_kl_cond_prepare_f64": (_I32, [_SPEC, _VP, _I64, _I32, _VP, _I64, _I32, _I32, _VP, _VP, _VP, _I64, _VP, _I64,
+                                        _VP, _I32, _I32, _VP, _VP, _VP]),
     "lvae_relu_maxpool2_fwd_f32": (_I32, [_VP, _I64, _I32, _I32, _VP, _VP, _VP]),
     "lvae_relu_maxpool2_bwd_f32": (_I32, [_VP, _VP, _VP, _I64, _I32, _I32, _VP, _VP]),
     "lvae_relu_maxpool2_bias_workspace_size": (_SZ, [_I32, _I32]),

@@ -417,13 +417,18 @@ class LatentInferenceStep:
     gpapprox.DuboCondition: the joint DUBO of cat(new, train) as a function of the new rows alone),
     gp = sum_l dubo_l / L in BOTH branches as the reference does in this function (DuboStep's 'nll' does not divide):
     recon + weight * gp ('mse') or nll + gp ('nll').  Only mu.grad and log_var.grad are assigned: the network's
-    parameters and their .grad stay exactly as they were.  ``apply`` is the optimiser step."""
+    parameters and their .grad stay exactly as they were.  ``apply`` is the optimiser step.
 
-    def __init__(self, vae, cond, mu, log_var, optimiser, weight=0.15, loss_function="mse"):
+    ``cond`` may equally come from kl_cond.condition_kl_closed (the exact KL of a KL_closed-trained model, conditioned
+    the same way).  ``gp_divisor``: None divides the summed GP term by L as above; a number divides by it instead.
+    standard_training's 'nll' branch with the exact KL adds sum_l KL_l undivided (training.py:549-566), so inferring
+    under the loss such a model was trained with takes ``gp_divisor=1``."""
+
+    def __init__(self, vae, cond, mu, log_var, optimiser, weight=0.15, loss_function="mse", gp_divisor=None):
         if loss_function not in ("mse", "nll"):
             raise ValueError(f"loss_function must be 'mse' or 'nll', got {loss_function!r}")
         self.vae, self.cond, self.mu, self.log_var, self.opt = vae, cond, mu, log_var, optimiser
-        self.weight, self.loss_function = weight, loss_function
+        self.weight, self.loss_function, self.gp_divisor = weight, loss_function, gp_divisor
 
     def forward_backward(self, img, mask, eps=None):
         self.opt.zero_grad(set_to_none=True)
@@ -431,7 +436,7 @@ class LatentInferenceStep:
         Z = self.vae.sample_latent(mu.to(img.dtype), log_var.to(img.dtype), eps)
         mse, nll = self.vae.loss_function(self.vae.decode(Z), img, mask)
         recon_loss, nll_loss = mse.sum(), nll.sum()
-        gp = self.cond(mu, log_var).sum() / self.cond.L
+        gp = self.cond(mu, log_var).sum() / (self.cond.L if self.gp_divisor is None else self.gp_divisor)
         net = recon_loss + self.weight * gp if self.loss_function == "mse" else nll_loss + gp
         mu.grad, log_var.grad = torch.autograd.grad(net, (mu, log_var))
         return net.detach(), recon_loss.detach(), nll_loss.detach(), gp.detach()
@@ -445,9 +450,11 @@ class LatentInferenceStep:
         return out
 
 
-def infer_new_subjects(vae, cond, img, mask, iters=1000, lr=1e-3, weight=0.15, loss_function="mse", eps=None):
+def infer_new_subjects(vae, cond, img, mask, iters=1000, lr=1e-3, weight=0.15, loss_function="mse", eps=None,
+                       gp_divisor=None):
     """The latents of new subjects (training.py:688-749): (mu, log_var) start at ``vae.encode(img)``, Adam(lr) over
     the two runs ``iters`` LatentInferenceSteps.  eps: optional [iters, Nn, L] draws (else drawn per iteration).
+    ``gp_divisor``: as LatentInferenceStep's (None: the GP term is divided by L; 1 for the undivided exact KL).
     Returns (mu, log_var, losses): the fp64 nn.Parameters and losses [iters, 4] fp64 on the device, the columns
     (net, recon, nll, gp) -- no host sync inside the loop."""
     with torch.no_grad():
@@ -457,7 +464,7 @@ def infer_new_subjects(vae, cond, img, mask, iters=1000, lr=1e-3, weight=0.15, l
     if eps is not None and tuple(eps.shape) != (iters,) + tuple(mu.shape):
         raise ValueError(f"eps must be [{iters}, {mu.shape[0]}, {mu.shape[1]}], got {tuple(eps.shape)}")
     opt = torch.optim.Adam([{"params": mu}, {"params": log_var}], lr=lr)
-    step = LatentInferenceStep(vae, cond, mu, log_var, opt, weight, loss_function)
+    step = LatentInferenceStep(vae, cond, mu, log_var, opt, weight, loss_function, gp_divisor)
     losses = torch.empty(iters, 4, dtype=torch.float64, device=mu.device)
     for it in range(iters):
         out = step(img, mask, None if eps is None else eps[it])
