@@ -40,6 +40,7 @@
 // row-major Y planes -- tiles (i, j), i >= j: lower and diagonal; the same tile offsets, so the two sets
 // are disjoint; lauum reads neither and overwrites it), scratch (CiScratch): C planes 2 x [L, np, 256] by
 // pass parity, the pivot's X block, D [L, nt, 256, 256], the L planes [L, np, np] and the per-tile scales.
+#include "chol_inv.hpp"
 #include "prof.hpp"
 #include "pv_lds.hpp"
 #include "side_stream.hpp"
@@ -63,8 +64,8 @@ namespace lvae {
 // (row-major Y, read only by the doubling's Y step) are not produced.
 // (The inverse alone at np = 4096: L = 2 2.18 vs 2.60 ms; L = 4 2.84 either way.)
 constexpr int kCiPipeMaxL = 2;
-// The ONE decision for the pipelined schedule: the scratch layout (the XR planes), the factor's schedule, the
-// lauum's `pre` flag and the exact KL's early-reduce gate (kl_closed.hip) all ask here.
+// The ONE decision for the pipelined schedule (chol_inv.hpp): here the scratch layout (the XR planes), the factor's
+// schedule and the lauum's `pre` flag ask it.
 bool ci_pipe_mode(int np_, int L) { return L <= kCiPipeMaxL && np_ >= 512; }  // (implies schedule (a))
 
 struct CiScratch {
@@ -1393,11 +1394,9 @@ static int ci_trtri_tail(int np_, int L, const CiScratch& S, const CiPlanes& P, 
   return 0;
 }
 
-// potrf + trtri: Y = L^-1 as the Y^T planes YT (+ the per-tile scales in the scratch); A and Kinv are
-// overwritten (Kinv holds the X^T planes)
-// (lout: potrf only -- no trtri, no pipelined schedule -- with L written in fp32 into lout's lower tiles)
+// potrf + trtri, or with lout potrf alone (the contract: chol_inv.hpp)
 int ci_factor_f32(int np_, int L, float* A, void* scratch, _Float16* YT, float* Kinv, double* logdet,
-                  int32_t* info, hipStream_t st, float* lout = nullptr) {
+                  int32_t* info, hipStream_t st, float* lout) {
   if (np_ <= 0 || np_ % kSwB || np_ / kSwB > 64) return -1;
   if (L <= 0) return -2;
   CiScratch S((char*)scratch, np_, L);
@@ -1469,8 +1468,6 @@ __global__ __launch_bounds__(64) void ci_bscale_kernel(CiScratch S, const float*
   if (t == 0) bsc[l] = x3_scale(d * v);
 }
 
-// lauum, K^-1 = Y^T Y from ci_factor_f32's Y^T planes.  With mu (the exact KL's reduce): also the
-// partials of K^-1 mu (apart) and, if Bh, the planes of B = K^-1 diag(sqrt v) with their scale bsc[L].
 int ci_lauum_f32(int np_, int L, void* scratch, const _Float16* YT, float* Kinv, const double* mu, const float* sv,
                  float* apart, _Float16* Bh, float* bsc, hipStream_t st, const int* hbon) {
   if (np_ <= 0 || np_ % kSwB || np_ / kSwB > 64) return -1;
@@ -1511,11 +1508,8 @@ int ci_lauum_flagged_f32(int np_, int L, void* scratch, const _Float16* YT, floa
   return 0;
 }
 
-// the per-tile split scales of Y (ysc(l, i, j), both plane orientations) in the factor's scratch
 const float* ci_ysc_ptr(void* scratch, int np_, int L) { return CiScratch((char*)scratch, np_, L).ysc; }
 
-// potrf alone (lvae_potrf_f32): A [L, np, np] -> L in A's lower tiles (fp32; zero strict upper part of the
-// diagonal tiles; the other upper tiles untouched), log|A|, info
 int ci_potrf_f32(int np_, int L, float* A, void* scratch, double* logdet, int32_t* info, hipStream_t st) {
   return ci_factor_f32(np_, L, A, scratch, nullptr, nullptr, logdet, info, st, A);
 }

@@ -7,7 +7,7 @@
 #pragma once
 #include "common.hpp"
 #include "blkinv.hpp"
-#include "gram_bwd.hpp"
+#include "gram.hpp"
 #include "small.hpp"
 
 namespace lvae {

@@ -1,5 +1,5 @@
 // gram_tab.hpp -- the table description of an additive kernel whose components are Cat / Bin gates times at
-// most one RBF / periodic factor of an integer-coded covariate (gram.hip's table path, kl_hyper.hip's binned
+// most one RBF / periodic factor of an integer-coded covariate (kl_gram.hip's table path, kl_hyper.hip's binned
 // hyper-parameter gradient): per-workgroup LDS tables of the factors and their parameter derivatives as
 // functions of (the pair's gate bits, the integer distance).
 #pragma once

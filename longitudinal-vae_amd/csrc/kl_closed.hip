@@ -3,7 +3,7 @@
 //
 // factor (needs only the covariates and hyper-parameters: launched before the encoder has run):
 //   K_l = Gram_l(x, x) + noise_l I                (kl_gram_fill, f32, padded to np; table / fp32 / fp64
-//                                                   covariate paths chosen on the device, gram.hip)
+//                                                   covariate paths chosen on the device, kl_gram.hip)
 //   Y = L^-1, log|K|                               (ci_factor_f32: blocked Cholesky + trtri, f16 x3 MFMA,
 //                                                   chol_inv.hip)
 //   the binned residual's plan                     (kl_resid_bins_plan, on the side stream behind the
@@ -20,7 +20,7 @@
 //   planes, one power-of-two scale per dim          backward follows)
 //   a0, d = diag K^-1                              (kl_alpha0_kernel: fixed-order sum of the partials)
 //   r = mu - K a0                                  (kl_gram_resid: fp64 Gram-free residual, binned
-//                                                   O(N W) (kl_resid_bins.hip) or tiled O(N^2), gram.hip)
+//                                                   O(N W) (kl_resid_bins.hip) or tiled O(N^2), gram_matvec.hip)
 //   a = a0 + K^-1 r                                (kl_alpha_sym_kernel over the lower tiles of K^-1, f64
 //                                                   accumulation: one step of iterative refinement)
 //   kl_l = 1/2 (sum v d + mu.a - n + logdet - sum log v)
@@ -30,9 +30,15 @@
 //   G = 1/2 (K^-1 - S - a a^T) -> dtheta, dnoise   (kl_gram_bwd, fused, never materialised)
 //   dmu = g a,  dlogv = g/2 (v d - 1)
 // One reduce per factor: the backward's S overwrites the Y^T planes.
+#include "chol_inv.hpp"
 #include "common.hpp"
-#include "side_stream.hpp"
+#include "gram.hpp"
+#include "kl_hyper.hpp"
+#include "kl_refine.hpp"
+#include "kl_resid_bins.hpp"
 #include "prof.hpp"
+#include "side_stream.hpp"
+#include "syrk_x3.hpp"
 #include "x3_c16.hpp"  // c16_off: the chunk-major Y / Y^T planes
 
 #include <unordered_set>
@@ -43,49 +49,6 @@
 #endif
 
 namespace lvae {
-
-int kl_gram_fill(const lvae_kernel_spec* spec, const double* x, int ldx, int n, int np_, int L,
-                 const double* params, const double* noise, float* K, int* covflag, hipStream_t st);
-size_t kl_gram_bwd_partials_bytes(int np_, int L);
-int kl_gram_bwd(const lvae_kernel_spec* spec, const double* x, int ldx, int n, int np_, int L,
-                const double* params, const float* Kinv, const float* S, const float* Sx, int nsplit,
-                const double* alpha, const double* kdiag, const float* v, const double* gkl, double* part,
-                double* dparams, double* dnoise, const int* covflag, void* hbws, const int* hbon, hipStream_t st);
-int syrk_x3_splits(int np_, int L);
-int syrk_tiles_f32(int np_, int L, const float* bsc, const _Float16* planes, float* S, float* Sx, hipStream_t st,
-                   const int* skip);
-size_t kl_hyper_bytes(int np_, int L);
-struct HbDev;
-HbDev* kl_hyper_dev(void* base, int np_, int L);
-int kl_hyper_plan(const lvae_kernel_spec* spec, const double* x, int ldx, int n, int np_, int L, void* wsbase,
-                  const int* covflag, hipStream_t st);
-int ci_factor_f32(int np_, int L, float* A, void* scratch, _Float16* YT, float* Kinv, double* logdet,
-                  int32_t* info, hipStream_t st, float* lout = nullptr);
-int ci_lauum_f32(int np_, int L, void* scratch, const _Float16* YT, float* Kinv, const double* mu, const float* sv,
-                 float* apart, _Float16* Bh, float* bsc, hipStream_t st, const int* hbon);
-size_t ci_scratch_bytes(int np_, int L);
-size_t kl_resid_partials_bytes(int np_, int L);
-int kl_gram_resid(const lvae_kernel_spec* spec, const double* x, int ldx, int n, int np_, int L,
-                  const double* params, const double* noise, const double* alpha0, const double* muc, double* part,
-                  double* res, void* rbws, hipStream_t st);
-size_t kl_resid_bins_bytes(int np_, int L, int ncomp);
-bool kl_resid_bins_enabled(const lvae_kernel_spec* spec, int n);
-int kl_resid_bins_plan(const lvae_kernel_spec* spec, const double* x, int ldx, int n, int np_, int L, void* wsbuf,
-                       hipStream_t st);
-int* kl_resid_bins_okflag(void* wsbuf);
-size_t kl_refine_bytes(int np_, int L);
-int kl_refine_gate(const lvae_kernel_spec* spec, const double* x, int ldx, int n, int np_, int L, const double* params,
-                   const double* noise, const double* kdiag, double* est, int* flag, hipStream_t st);
-int kl_refine_apply(const lvae_kernel_spec* spec, const double* x, int ldx, int n, int np_, int L, const double* params,
-                    const double* noise, const float* Kinv, double* kdiag, double* K64, double* part, const int* flag,
-                    hipStream_t st);
-int ci_lauum_flagged_f32(int np_, int L, void* scratch, const _Float16* YT, float* Kinv, const int* flag, hipStream_t st);
-const float* ci_ysc_ptr(void* scratch, int np_, int L);
-bool ci_pipe_mode(int np_, int L);
-size_t kl_refine_part_bytes(int np_, int L);
-int kl_refine_diag(const lvae_kernel_spec* spec, const double* x, int ldx, int n, int np_, int L,
-                   const double* params, const double* noise, const float* Kinv, double* kdiag, double* K64,
-                   double* part, double* est, int* flag, hipStream_t st);
 
 struct KLWorkspace {
   float *A, *Kinv, *v, *sv;

@@ -37,10 +37,9 @@
 #include <type_traits>
 
 #include "cond_state.hpp"
+#include "gram.hpp"
 
 namespace lvae {
-
-int gram_matvec_spec_ld(const lvae_kernel_spec* spec);  // gram.hip
 
 namespace {
 

@@ -2,7 +2,7 @@
 //
 // d KL / d theta_p = sum_ij G_ij dK_ij / d theta_p,  G = (K^-1 - S - alpha alpha^T) / 2  (elbo_functions.py:22-31
 // under autograd).  The product route forms S with an N^3 GEMM (syrk_x3.hip, the step's largest kernel) and
-// contracts G with the table adjoint (gram.hip).  For the table family of kernels (every component Cat / Bin
+// contracts G with the table adjoint (kl_gram.hip).  For the table family of kernels (every component Cat / Bin
 // gates times at most one RBF / periodic factor of an integer-coded covariate -- the reference's whole
 // generate_kernel_batched family on integer covariates, GP_model.py:146-236) neither is needed:
 //
@@ -31,6 +31,7 @@
 // on the host: the slab kernel's LDS fits (hb_slab_lds).
 #include "blkinv.hpp"
 #include "gram_tab.hpp"
+#include "kl_hyper.hpp"
 #include "prof.hpp"
 
 namespace lvae {
@@ -818,7 +819,7 @@ __global__ __launch_bounds__(kHbSlabThreads, 2) void hb_slab_kernel(GramTab tb, 
 // the final contraction per latent dim: the slabs in a fixed order; raw sums into the table adjoint's slots
 // part[l][slot][0] (the other G - 1 zero) for kl_gram_bwd_reduce
 // ------------------------------------------------------------------------------------------
-constexpr int kNoiseSlotHb = 64, kBwdSlotsHb = 65;  // (gram.hip's kNoiseSlot / kBwdSlots)
+constexpr int kNoiseSlotHb = 64, kBwdSlotsHb = 65;  // (kl_gram.hip's kNoiseSlot / kBwdSlots)
 
 // the slab records summed over J in a fixed order, in place into slab 0's record: thread (e, l) owns entry e
 __global__ __launch_bounds__(256) void hb_sum_kernel(HbWs ws, int np_) {
@@ -938,7 +939,6 @@ static bool hb_host_ok(const lvae_kernel_spec* spec, GramTab& tb) {
   return gram_tab_build(spec, tb) && hb_enabled() && hb_slab_lds(tb) > 0;
 }
 
-// the plan and the pair codes (after kl_gram_fill's covariate check, on the same stream)
 int kl_hyper_plan(const lvae_kernel_spec* spec, const double* x, int ldx, int n, int np_, int L, void* wsbase,
                   const int* covflag, hipStream_t st) {
   HbWs ws((char*)wsbase, np_, L);
@@ -952,8 +952,6 @@ int kl_hyper_plan(const lvae_kernel_spec* spec, const double* x, int ldx, int n,
   return 0;
 }
 
-// the binned hyper-gradient (raw sums into part, the table adjoint's layout with G workgroup slots); its kernels
-// exit at once when the plan is off
 int kl_hyper_bwd(const lvae_kernel_spec* spec, const double* x, int ldx, int n, int np_, int L, const double* params,
                  const float* Kinv, const float* v, const double* alpha, const double* kdiag, void* wsbase, double* part,
                  int G, hipStream_t st) {

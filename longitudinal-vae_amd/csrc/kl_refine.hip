@@ -28,6 +28,7 @@
 
 #include "common.hpp"
 #include "blkinv.hpp"
+#include "kl_refine.hpp"
 
 namespace lvae {
 
@@ -295,7 +296,6 @@ size_t kl_refine_bytes(int np_, int L) { return (size_t)kl_refine_cap(L) * np_ *
 
 size_t kl_refine_part_bytes(int np_, int L) { return (size_t)L * (np_ / kRgT) * np_ * sizeof(double); }
 
-// the gate alone: est, flag from kdiag (mode 0: both zero)
 int kl_refine_gate(const lvae_kernel_spec* spec, const double* x, int ldx, int n, int np_, int L, const double* params,
                    const double* noise, const double* kdiag, double* est, int* flag, hipStream_t st) {
   const int mode = refine_mode();
@@ -312,7 +312,6 @@ int kl_refine_gate(const lvae_kernel_spec* spec, const double* x, int ldx, int n
   return 0;
 }
 
-// the refinement of the flagged dims' diag K^-1 (kdiag) from the fp32 K^-1 in Kinv (the gate ran before)
 int kl_refine_apply(const lvae_kernel_spec* spec, const double* x, int ldx, int n, int np_, int L, const double* params,
                     const double* noise, const float* Kinv, double* kdiag, double* K64, double* part, const int* flag,
                     hipStream_t st) {

@@ -1,4 +1,4 @@
-// kl_resid_bins.hip -- the exact KL's fp64 residual r = mu - K a0 (kl_gram_resid, gram.hip) in O(N W)
+// kl_resid_bins.hip -- the exact KL's fp64 residual r = mu - K a0 (kl_gram_resid, gram_matvec.hip) in O(N W)
 // instead of O(N^2) when the covariates are integer-coded.
 //
 // Every component of the reference's kernel family (GP_model.py:146-236: Cat / Bin kernels, RBF, their
@@ -19,6 +19,7 @@
 #include <stdlib.h>
 
 #include "common.hpp"
+#include "kl_resid_bins.hpp"
 
 namespace lvae {
 
@@ -65,7 +66,6 @@ struct RbWs {
 };
 
 size_t kl_resid_bins_bytes(int np_, int L, int ncomp) { return RbWs(nullptr, np_, L, ncomp).bytes; }
-// the plan's device flag (its place does not depend on the sizes); the factor zeroes it when the host gate is off
 int* kl_resid_bins_okflag(void* wsbuf) { return RbWs((char*)wsbuf, kRbMaxW, 1, 1).ok; }
 
 // structure the host can check: every component at most one continuous factor, at most kRbMaxGates gates
@@ -331,7 +331,6 @@ bool kl_resid_bins_enabled(const lvae_kernel_spec* spec, int n) {
   return on && kl_resid_bins_spec_ok(spec, n);
 }
 
-// the plan (depends on x only; kl_closed.hip enqueues it on the side stream during the factorisation)
 int kl_resid_bins_plan(const lvae_kernel_spec* spec, const double* x, int ldx, int n, int np_, int L, void* wsbuf,
                        hipStream_t st) {
   RbWs ws((char*)wsbuf, np_, L, spec->n_comp);
@@ -341,8 +340,6 @@ int kl_resid_bins_plan(const lvae_kernel_spec* spec, const double* x, int ldx, i
   return 0;
 }
 
-// the bin sums and the residual, after the plan; *okflag = the plan's device flag (1: every component
-// was binned -- else these kernels exit at once and the caller's tiled kernels, given the flag, run)
 int kl_resid_bins(const lvae_kernel_spec* spec, const double* x, int ldx, int n, int np_, int L,
                   const double* params, const double* noise, const double* alpha0, const double* muc, double* res,
                   void* wsbuf, int** okflag, hipStream_t st) {

@@ -15,13 +15,10 @@
 //                    blocked trsm of rocBLAS / LAPACK's trtri-based solve do); f32 operands are computed in fp64
 //   lvae_potrs_*     trsm(L) then trsm(L^T)
 #include "blkinv.hpp"
+#include "chol_inv.hpp"
 #include "pv_lds.hpp"  // kSwB
 
 namespace lvae {
-
-// chol_inv.hip
-size_t ci_scratch_bytes(int np_, int L);
-int ci_potrf_f32(int np_, int L, float* A, void* scratch, double* logdet, int32_t* info, hipStream_t st);
 
 constexpr int kPB = 64;        // block edge
 constexpr int kPBL = kPB + 1;  // LDS pitch (doubles)

@@ -26,6 +26,7 @@
 // checks, its carve and the launches that are its alone.
 #include <type_traits>
 
+#include "gram.hpp"
 #include "small.hpp"
 #include "prof.hpp"
 #include "predict_var.hpp"
@@ -33,15 +34,6 @@
 #include "predict_ccov.hpp"
 
 namespace lvae {
-
-int gram_matvec_f64(const lvae_kernel_spec* spec, const double* x1, int64_t ld1, int n1, const double* x2, int64_t ld2,
-                    int n2, int L, const double* params, const double* diag, const double* v, int64_t ld_v, int v_t,
-                    double* out, int64_t ld_out, int o_t, void* workspace, hipStream_t st);
-int gram_matvec_spec_ld(const lvae_kernel_spec* spec);
-int gram_matvec_comp_f64(const lvae_kernel_spec* spec, const double* x1, int64_t ld1, int n1, const double* x2,
-                         int64_t ld2, int64_t x2_stride_l, int n2, int L, const double* params, const double* v,
-                         int64_t ld_v, int v_t, double* out, int64_t ld_out, int o_t, int64_t ostride_r,
-                         void* workspace, hipStream_t st);
 
 namespace {
 

@@ -24,6 +24,7 @@
 // 128 x 128 per wave; 256 x 128 half tiles with two workgroups per CU; the 8-wave core with 16-deep
 // row-major chunks in a 4-stage ring (3.55 vs 3.18 ms at np = 4096, L = 16 and 87 vs 51 ms at np = 16384,
 // L = 4: its 32-B row segments per chunk double the L2 traffic).
+#include "syrk_x3.hpp"
 #include "x3_c16.hpp"
 
 #ifndef LVAE_SYRK_RESERVE

@@ -32,7 +32,7 @@ L = 3
 EPS = 1e-3
 S = 2                                    # samples of the sampled ELBO
 T0 = np.array([0.0, 1.0, 2.0, 64.0, 65.0, 66.0, 200.0])
-TAB = 64                                 # kGTab of csrc/gram.hip: integer distances below it are table hits
+TAB = 64                                 # kGTab of csrc/gram.hip (the generic Grams): integer distances below are hits
 CONT_COLS = [0, 1, 6]
 COT = (1.0, -0.5, 2.0)
 

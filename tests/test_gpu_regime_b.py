@@ -787,7 +787,7 @@ def test_kl_closed_resid_paths(hip, case):
     of 76 > 64 values: "wide_window").  dmu = K^-1 mu is the refined quantity: within 1e-8 of the fp64
     oracle (the refinement reaches ~1e-10 here; a residual that missed terms leaves the fp32-equivalent
     inverse's ~1e-5), and the KL within 1e-6.  The same cases select the Gram fill / adjoint paths
-    (gram.hip covariate flag): tables for "integer" / "gates_masks", fp32 covariates for "wide_window"
+    (kl_gram.hip covariate flag): tables for "integer" / "gates_masks", fp32 covariates for "wide_window"
     and "c5" (a linear factor), fp64 covariates for "half_time" -- dlogv and draw within 1e-4."""
     import lvae_amd as la
     from lvae_amd.data import health_mnist_covariates
